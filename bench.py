@@ -2,8 +2,12 @@
 """bench.py — iLQR iterations/s of the batched HIP solver on BASELINE.json's config C2
 (pendulum swing-up n=2 m=1 N=200, B=1024 seeded initial states per GPU, fp64).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+--dump-outputs DIR: after the K timed steps, rank 0 writes what the last of them computed for its batch - the arrays a
+caller of the solver reads after a Solve() - as DIR/<name>.npy (float64, see dump_outputs).  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 With --gpus N > 1 and no launcher environment (WORLD_SIZE unset) the script launches its own N ranks
 (one process per GPU, torch.distributed.run on 127.0.0.1, RCCL) and rank 0 prints the line.
@@ -555,6 +559,26 @@ def concurrent_batches(prob, x0, dev_index, handles=(2, 4), groups=12, per_group
     return {"workload": "C2, independent batches of 1024 on their own streams, pipelined cold-start solves", "runs": out}
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(s, out_dir):
+    """The results of the solver's last solve as the class hands them to a caller - x_bar (B,n,N), u_bar (B,m,N-1), cost,
+    iterations and status (B,) - written to out_dir/<name>.npy in float64.  When they exceed DUMP_CAP_BYTES, a fixed sample
+    of the problems (numpy default_rng(0), in ascending order) is written instead, with its indices in problem_index.npy."""
+    arrays = {"x_bar": s.x_bar, "u_bar": s.u_bar, "cost": s.cost, "iterations": s.iterations, "status": s.status}
+    arrays = {k: np.array(v, dtype=np.float64) for k, v in arrays.items()}       # (copies: the class reuses its result buffers)
+    per_problem = sum(a.nbytes for a in arrays.values()) // s.B + 8
+    keep = min(s.B, DUMP_CAP_BYTES // per_problem)
+    if keep < s.B:
+        idx = np.sort(np.random.default_rng(0).choice(s.B, keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["problem_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -564,7 +588,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="headline only (skip C1/C3/C4/C5 and the boundary-inclusive run)")
     ap.add_argument("--cpu-sample", type=int, default=24)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (rank 0's batch) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -746,6 +774,8 @@ def main():
     onehot = [0.0] * world
     onehot[rank] = float(iters)
     iters_per_rank = rk.reduce(onehot, "sum")              # every rank's own iteration sum over the K timed steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(s, args.dump_outputs)                 # (after the timed region: the reads cost it nothing)
     del s, s_weak
 
     # N > 1: the STRONG-scaling figure beside the weak one - north_star's "a batch of 1024 ... at 1/2/4/8 GPUs": the single-GPU run's

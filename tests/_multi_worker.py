@@ -1,8 +1,10 @@
 """One rank of tests/test_gpu_multi.py (a plain script: every rank is its own process on its own GPU).
 
-    python _multi_worker.py <rank> <world> <exchange_dir> [same]
+    python _multi_worker.py <rank> <world> <exchange_dir> [same | gloo]
 
-"same": every rank uses GPU 0 (the communicator's ranks share one device - what a one-GPU box can run).
+"same": every rank uses GPU 0 (the communicator's ranks share one device).
+"gloo": every rank uses GPU 0 and the reduction goes through torch.distributed over gloo (drake_ddp_amd.dist, the path
+bench.py falls back to) instead of the library's communicator - RCCL refuses two ranks of one node on one device.
 
 Checks, on `world` GPUs of one node, the path's one collective in the library's own RCCL communicator
 (mi_ilqr_comm_*, NativeComm) and the shard partitioning of a batched solve; writes `<exchange_dir>/ok.<rank>`
@@ -20,8 +22,8 @@ sys.path.insert(0, ROOT)
 
 def main():
     rank, world, xdir = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3]
-    same = len(sys.argv) > 4 and sys.argv[4] == "same"
-    dev = 0 if same else rank
+    mode = sys.argv[4] if len(sys.argv) > 4 else None
+    dev = 0 if mode in ("same", "gloo") else rank
     from drake_ddp_amd.dist import NativeComm, shard_range
     from drake_ddp_amd import workloads as W
     from drake_ddp_amd.ilqr import BatchedIterativeLQR
@@ -42,13 +44,21 @@ def main():
         with open(path, "rb") as f:
             return f.read()
 
-    comm = NativeComm(rank, world, dev, exchange)
+    if mode == "gloo":
+        import torch.distributed as dist
+        from drake_ddp_amd.dist import allreduce_min_vec_async
+        dist.init_process_group("gloo", init_method="file://" + os.path.join(xdir, "pg"), rank=rank, world_size=world)
+        start = allreduce_min_vec_async
+        reduce_min = lambda v_: allreduce_min_vec_async(v_).wait()
+    else:
+        comm = NativeComm(rank, world, dev, exchange)
+        start, reduce_min = comm.start, comm.allreduce_min
     # ranks contribute DIFFERENT values: min, not sum / average / max (round-2 advisor: the op code was ncclAvg)
     v = np.array([10.0 * (rank + 1), -3.0 * (rank + 1), 100.0 - rank, float(rank == world - 1)])
     want = np.array([10.0, -3.0 * world, 100.0 - (world - 1), 0.0 if world > 1 else 1.0])
-    got = comm.allreduce_min(v)
+    got = reduce_min(v)
     assert np.array_equal(got, want), (rank, got, want)
-    got = comm.start(v[:2]).wait()
+    got = start(v[:2]).wait()
     assert np.array_equal(got, want[:2]), (rank, got)
 
     # the sharded solve: each rank solves its contiguous shard of the 64-problem batch on its own GPU and the
@@ -66,7 +76,7 @@ def main():
         s.Solve()
         return s
     mine = solve(x0[lo:hi], dev)
-    best = comm.allreduce_min([mine.stats.best_cost])[0]
+    best = reduce_min([mine.stats.best_cost])[0]
     out = {"rank": rank, "best": float(best), "iters": int(mine.iterations.sum()), "lo": lo, "hi": hi}
     if rank == 0:
         whole = solve(x0, 0)
@@ -75,6 +85,8 @@ def main():
         out["whole_iters"] = int(whole.iterations.sum())
     with open(os.path.join(xdir, f"ok.{rank}"), "w") as f:
         json.dump(out, f)
+    if mode == "gloo":
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":
