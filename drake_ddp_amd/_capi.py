@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI_ILQR_LIB") or os.path.join(_HERE, "lib", "libmi_ilqr.so")
 
 MAX_PARAMS = 16
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # enums (include/mi_ilqr.h)
 OK, E_BAD_SHAPE, E_BAD_METHOD, E_LINESEARCH, E_HIP, E_NO_DEVICE, E_BAD_ARG, E_UNSUPPORTED, E_RCCL = 0, -1, -2, -3, -4, -5, -6, -7, -8
@@ -32,7 +32,7 @@ CLUSTER_WORDS = 40          # MI_ILQR_CLUSTER_WORDS
 
 EXPORTS = [
     "mi_ilqr_abi_version", "mi_ilqr_struct_sizes", "mi_ilqr_strerror", "mi_ilqr_model_info", "mi_ilqr_register_model", "mi_ilqr_create", "mi_ilqr_destroy",
-    "mi_ilqr_set_cost", "mi_ilqr_set_initial", "mi_ilqr_set_initial_shared", "mi_ilqr_host_alloc", "mi_ilqr_host_free", "mi_ilqr_set_result_sink", "mi_ilqr_solve_into", "mi_ilqr_reset", "mi_ilqr_rearm_initial_guess",
+    "mi_ilqr_set_cost", "mi_ilqr_set_control_limits", "mi_ilqr_set_initial", "mi_ilqr_set_initial_shared", "mi_ilqr_host_alloc", "mi_ilqr_host_free", "mi_ilqr_set_result_sink", "mi_ilqr_solve_into", "mi_ilqr_reset", "mi_ilqr_rearm_initial_guess",
     "mi_ilqr_solve", "mi_ilqr_solve_async", "mi_ilqr_collect_stats", "mi_ilqr_collect_stats_n",
     "mi_ilqr_rollout", "mi_ilqr_forward", "mi_ilqr_linearize", "mi_ilqr_backward", "mi_ilqr_mpc_shift",
     "mi_ilqr_mpc_run", "mi_ilqr_get_mpc_log",
@@ -92,6 +92,7 @@ def load():
     lib.mi_ilqr_destroy.restype = None
     lib.mi_ilqr_set_cost.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mi_ilqr_set_initial.argtypes = [H, C.c_void_p, C.c_void_p]
+    lib.mi_ilqr_set_control_limits.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32]
     for name in ("mi_ilqr_reset", "mi_ilqr_rearm_initial_guess", "mi_ilqr_solve_async", "mi_ilqr_linearize",
                  "mi_ilqr_backward", "mi_ilqr_synchronize"):
         getattr(lib, name).argtypes = [H]

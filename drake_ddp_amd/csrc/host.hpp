@@ -87,6 +87,10 @@ struct mi_ilqr {
   double *x_spec = nullptr, *u_spec = nullptr;   // mid-size kernels: trial trajectories of three more line-search candidates
   int32_t* bm_scratch = nullptr;   // lane-per-problem kernels with key-points: integer scratch (ilqr_batch.hpp)
   double *sink_x = nullptr, *sink_u = nullptr, *sink_cost = nullptr;   // result sink (device aliases of host arrays), optional
+  // control limits (mi_ilqr_set_control_limits; m <= 2 kernel families): `limited` selects the Limited<M> kernels
+  bool limited = false;
+  double* ulim = nullptr;          // (B, 2, m): u_min | u_max per problem (allocated on first use, kept when cleared)
+  double* s2 = nullptr;            // (B,): S2 of each problem's last limited backward pass (KArgs::s2)
 };
 
 // Small batches of the wave-per-problem kernels aggregate the batch statistics in the solve kernel
@@ -164,3 +168,9 @@ MI_INTERNAL int launch_quad3d(mi_ilqr* h, int mode, const mi::KArgs& a);
 MI_INTERNAL int launch_arm27(mi_ilqr* h, int mode, const mi::KArgs& a);
 MI_INTERNAL int launch_arm27c(mi_ilqr* h, int mode, const mi::KArgs& a);
 MI_INTERNAL int launch_batch_minor(mi_ilqr* h, int mode, const mi::KArgs& a);
+// the same with control limits (Limited<M> kernels: k_<model>_lim.hip, k_batch_lim.hip)
+MI_INTERNAL int launch_pendulum_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
+MI_INTERNAL int launch_acrobot_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
+MI_INTERNAL int launch_cartpole_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
+MI_INTERNAL int launch_cartpole_wall_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
+MI_INTERNAL int launch_batch_minor_lim(mi_ilqr* h, int mode, const mi::KArgs& a);

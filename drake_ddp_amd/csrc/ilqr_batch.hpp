@@ -60,6 +60,12 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
   double x0r[n];
 #pragma unroll
   for (int i = 0; i < n; ++i) x0r[i] = a.x0[(size_t)bb * n + i];
+  // Limited<M>: the lane's bounds in registers, and S2 of its last backward pass (box_qp_step)
+  [[maybe_unused]] double s2 = 0.0;
+  if constexpr (UsesLimits<M>::value) {
+    c.load_limits(a.ulim + (size_t)bb * 2 * m);
+    s2 = a.cold ? 0.0 : a.s2[bb];
+  }
   double Q2[n][n], R2[m][m];
 #pragma unroll
   for (int i = 0; i < n; ++i)
@@ -142,11 +148,13 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
 #pragma unroll
           for (int j = 0; j < n; ++j) acc += r.Kv[k][j] * (x[j] - r.xbv[j]);
           u[k] = (r.ubv[k] - eps * r.kv[k]) - acc;                     // :313
+          if constexpr (UsesLimits<M>::value) u[k] = c.clamp(k, u[k]);  // clip(u, u_min, u_max)
         }
         double xn[n];
         M::template step<double>(x, u, xn, a.params, a.dt);             // :316
         Lc += stage_cost<M>(c, x, u);                                   // :325
-        ex += ce * r.dv;                                                // :326
+        if constexpr (UsesLimits<M>::value) ex += r.dv;                 // sum dV (limited_expected)
+        else ex += ce * r.dv;                                           // :326
 #pragma unroll
         for (int k = 0; k < m; ++k) uw[((size_t)t * m + k) * wstep_u] = u[k];
 #pragma unroll
@@ -166,6 +174,7 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
       }
       if (t < N - 1) step(A, t);
       Lc += terminal_cost<M>(c, x);                                     // :327
+      if constexpr (UsesLimits<M>::value) ex = -(eps * ex - 0.5 * eps * eps * s2);
       if (run) {
         trials += 1;
         if ((L - Lc) > a.gamma * ex) { accepted = true; L_new = Lc; eps_acc = eps; }   // :330-331
@@ -179,6 +188,7 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
     }
     if (ok) cur ^= 1;                            // u_bar <- u, x_bar <- x (:375-376): a flip
     // ---------------- linearization fused into the backward sweep (:380-415 with setInterval/1, :623-667)
+    [[maybe_unused]] bool pd = true;             // Limited<M>: every Quu of the sweep positive definite
     if (__any(ok)) {
       const double* xb = cur ? X1 : X0;
       const double* ub = cur ? U1 : U0;
@@ -188,6 +198,7 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
       double* fxw = ok ? Fxp : sink;
       double* fuw = ok ? Fup : sink;
       const size_t ws = ok ? (size_t)B : 0;
+      [[maybe_unused]] double s2_new = 0.0;
       double Vx[n], Vxx[n][n];
       {
         double xT[n];
@@ -558,60 +569,78 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
             Qux[a_][j] = s;
           }
         }
-        double Qi[m][m];
-        invert_small<m>(Quu, Qi);
-        double kap[m], Kg[m][n], QuQi[m];
+        if constexpr (UsesLimits<M>::value) {
+          double lo[m], hi[m];
 #pragma unroll
-        for (int a_ = 0; a_ < m; ++a_) {
-          double s = 0.0, q = 0.0;
+          for (int k = 0; k < m; ++k) { lo[k] = c.umin[k] - cu.u[k]; hi[k] = c.umax[k] - cu.u[k]; }
+          double kap[m], Kg[m][n], dv;
+          pd = box_qp_step<n, m>(Qx, Qu, Qxx, Quu, Qux, lo, hi, kap, Kg, dv, s2_new, Vx, Vxx) && pd;
 #pragma unroll
-          for (int b_ = 0; b_ < m; ++b_) { s += Qi[a_][b_] * Qu[b_]; q += Qu[b_] * Qi[b_][a_]; }
-          kap[a_] = s; QuQi[a_] = q;
+          for (int a_ = 0; a_ < m; ++a_) {
+            kw[((size_t)t * m + a_) * ws] = kap[a_];
+#pragma unroll
+            for (int j = 0; j < n; ++j) Kw[((size_t)t * m * n + a_ * n + j) * ws] = Kg[a_][j];
+          }
+          dw[(size_t)t * ws] = dv;
+        } else {
+          double Qi[m][m];
+          invert_small<m>(Quu, Qi);
+          double kap[m], Kg[m][n], QuQi[m];
+#pragma unroll
+          for (int a_ = 0; a_ < m; ++a_) {
+            double s = 0.0, q = 0.0;
+#pragma unroll
+            for (int b_ = 0; b_ < m; ++b_) { s += Qi[a_][b_] * Qu[b_]; q += Qu[b_] * Qi[b_][a_]; }
+            kap[a_] = s; QuQi[a_] = q;
+#pragma unroll
+            for (int j = 0; j < n; ++j) {
+              double g = 0.0;
+#pragma unroll
+              for (int b_ = 0; b_ < m; ++b_) g += Qi[a_][b_] * Qux[b_][j];
+              Kg[a_][j] = g;
+            }
+          }
+          double dv = 0.0;
+#pragma unroll
+          for (int a_ = 0; a_ < m; ++a_) dv += QuQi[a_] * Qu[a_];
+#pragma unroll
+          for (int a_ = 0; a_ < m; ++a_) {
+            kw[((size_t)t * m + a_) * ws] = kap[a_];
+#pragma unroll
+            for (int j = 0; j < n; ++j) Kw[((size_t)t * m * n + a_ * n + j) * ws] = Kg[a_][j];
+          }
+          dw[(size_t)t * ws] = dv;
 #pragma unroll
           for (int j = 0; j < n; ++j) {
-            double g = 0.0;
+            double s = Qx[j];
 #pragma unroll
-            for (int b_ = 0; b_ < m; ++b_) g += Qi[a_][b_] * Qux[b_][j];
-            Kg[a_][j] = g;
+            for (int a_ = 0; a_ < m; ++a_) s -= QuQi[a_] * Qux[a_][j];
+            Vx[j] = s;
           }
+          double QuxTQi[n][m];
+#pragma unroll
+          for (int i = 0; i < n; ++i)
+#pragma unroll
+            for (int b_ = 0; b_ < m; ++b_) {
+              double s = 0.0;
+#pragma unroll
+              for (int a_ = 0; a_ < m; ++a_) s += Qux[a_][i] * Qi[a_][b_];
+              QuxTQi[i][b_] = s;
+            }
+#pragma unroll
+          for (int i = 0; i < n; ++i)
+#pragma unroll
+            for (int j = 0; j < n; ++j) {
+              double s = Qxx[i][j];
+#pragma unroll
+              for (int b_ = 0; b_ < m; ++b_) s -= QuxTQi[i][b_] * Qux[b_][j];
+              Vxx[i][j] = s;
+            }
         }
-        double dv = 0.0;
-#pragma unroll
-        for (int a_ = 0; a_ < m; ++a_) dv += QuQi[a_] * Qu[a_];
-#pragma unroll
-        for (int a_ = 0; a_ < m; ++a_) {
-          kw[((size_t)t * m + a_) * ws] = kap[a_];
-#pragma unroll
-          for (int j = 0; j < n; ++j) Kw[((size_t)t * m * n + a_ * n + j) * ws] = Kg[a_][j];
-        }
-        dw[(size_t)t * ws] = dv;
-#pragma unroll
-        for (int j = 0; j < n; ++j) {
-          double s = Qx[j];
-#pragma unroll
-          for (int a_ = 0; a_ < m; ++a_) s -= QuQi[a_] * Qux[a_][j];
-          Vx[j] = s;
-        }
-        double QuxTQi[n][m];
-#pragma unroll
-        for (int i = 0; i < n; ++i)
-#pragma unroll
-          for (int b_ = 0; b_ < m; ++b_) {
-            double s = 0.0;
-#pragma unroll
-            for (int a_ = 0; a_ < m; ++a_) s += Qux[a_][i] * Qi[a_][b_];
-            QuxTQi[i][b_] = s;
-          }
-#pragma unroll
-        for (int i = 0; i < n; ++i)
-#pragma unroll
-          for (int j = 0; j < n; ++j) {
-            double s = Qxx[i][j];
-#pragma unroll
-            for (int b_ = 0; b_ < m; ++b_) s -= QuxTQi[i][b_] * Qux[b_][j];
-            Vxx[i][j] = s;
-          }
         cu = nx;
+      }
+      if constexpr (UsesLimits<M>::value) {
+        if (ok) s2 = s2_new;
       }
     }
     if (ok) {
@@ -622,6 +651,9 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
       improvement = L - L_new;                                          // :706
       L = L_new;
       iters += 1;
+      if constexpr (UsesLimits<M>::value) {
+        if (!pd) { status = MI_STATUS_NOT_PD; active = false; }         // limited: no box-QP minimiser
+      }
     }
   }
   // make buffer 0 the canonical x_bar/u_bar
@@ -637,6 +669,7 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
   }
   if (live) {
     a.cost[b] = L; a.iters[b] = iters; a.status[b] = status; a.ls_trials[b] = ls_total; a.kp_count[b] = KP ? nk_lane : N - 1;
+    if constexpr (UsesLimits<M>::value) a.s2[b] = s2;
     if constexpr (KP) {
       if (iters > 0) { for (int i = 0; i < nk_lane; ++i) a.kp_list[(size_t)b * (N - 1) + i] = a.bm_scratch[(size_t)i * B + b]; }
     }

@@ -104,6 +104,10 @@ struct KArgs {
   double* lxu;
   int pd_continue;                // mi_ilqr_desc.on_indefinite
   int cost_asym;                  // workgroup-per-problem kernels, n <= 32: Q, R or Qf is not symmetric (mi_ilqr_set_cost)
+  // control limits (mi_ilqr_set_control_limits; read by the Limited<M> kernels only): (B, 2, m) - u_min | u_max per problem -
+  // and S2 = sum_t kappa_t^T Quu_t kappa_t of each problem's last backward pass, (B,), the quadratic term of the expected improvement
+  const double* ulim;
+  double* s2;
 };
 
 // threadIdx.x behind an empty asm, for the STAGES of a solve kernel (a rollout, a linearization, a backward pass): what a stage
@@ -260,8 +264,36 @@ struct UsesExactBackward : std::false_type {};
 template <class M>
 struct UsesExactBackward<M, std::void_t<decltype(M::kExactBackward)>> : std::bool_constant<M::kExactBackward> {};
 
+// The same model with box control limits u_min <= u <= u_max (mi_ilqr_set_control_limits): every rollout clamps its controls,
+// the backward pass solves a box QP per step (backward_limited).  Both are sequential in time - the n = 2 Newton rollout and
+// the Riccati scans have no form that carries an active set - so the host picks this instantiation for limited handles only,
+// like LongHorizon<M> / ExactCost<M>, and the regular kernels carry neither its code nor its registers.
 template <class M>
-struct Consts {
+struct Limited : M { static constexpr bool kLimited = true; };
+template <class M, class = void>
+struct UsesLimits : std::false_type {};
+template <class M>
+struct UsesLimits<M, std::void_t<decltype(M::kLimited)>> : std::bool_constant<M::kLimited> {};
+
+// The bounds of one problem, in registers for the whole launch (Limited<M> kernels; empty otherwise).
+template <class M, bool = UsesLimits<M>::value>
+struct LimitRegs {};
+template <class M>
+struct LimitRegs<M, true> {
+  double umin[M::m], umax[M::m];
+  __device__ inline void load_limits(const double* p) {      // p: this problem's (2, m) record
+#pragma unroll
+    for (int k = 0; k < M::m; ++k) { umin[k] = p[k]; umax[k] = p[M::m + k]; }
+  }
+  // clip(v, u_min, u_max) by comparisons: a NaN stays NaN (its trial is rejected as without limits)
+  __device__ __forceinline__ double clamp(int k, double v) const {
+    v = v < umin[k] ? umin[k] : v;
+    return v > umax[k] ? umax[k] : v;
+  }
+};
+
+template <class M>
+struct Consts : LimitRegs<M> {
   static constexpr int n = M::n, m = M::m;
   double Q[n][n], R[m][m], Qf[n][n], xnom[n];
   double qn[n];    // 2*x_nom^T Q    (ilqr.py:180)
@@ -422,6 +454,7 @@ __device__ __forceinline__ void rollout_step(const GRegs<M>& r, const Consts<M>&
 #pragma unroll
     for (int j = 0; j < n; ++j) acc += r.K[k][j] * (x[j] - r.xb[j]);
     u[k] = (r.ub[k] - eps * r.kap[k]) - acc;
+    if constexpr (UsesLimits<M>::value) u[k] = c.clamp(k, u[k]);   // clip(u, u_min, u_max)
   }
   double xnext[n];
   if constexpr (HasStepPool<M>::value) M::step_pooled(x, u, xnext, a.params, a.dt, pool);   // ilqr.py:316
@@ -429,7 +462,8 @@ __device__ __forceinline__ void rollout_step(const GRegs<M>& r, const Consts<M>&
   if (COST) {
     // stage cost (no 1/2 factor, ilqr.py:325) and expected improvement (:326)
     L += stage_cost<M>(c, x, u, a.q_diag != 0);
-    expd += ce * r.dv;
+    if constexpr (UsesLimits<M>::value) expd += r.dv;      // sum dV; the quadratic term is added once (rollout)
+    else expd += ce * r.dv;
   }
   // T_t.u = u_t ; T_{t+1}.x = x_{t+1}
 #pragma unroll
@@ -438,6 +472,15 @@ __device__ __forceinline__ void rollout_step(const GRegs<M>& r, const Consts<M>&
   for (int i = 0; i < n; ++i) tw[Ly::TS + Ly::XN + i] = xnext[i];
 #pragma unroll
   for (int i = 0; i < n; ++i) x[i] = xnext[i];
+}
+
+// Expected improvement of a limited trial: -(eps sum_t dV_t - eps^2 / 2 S2), S2 = sum_t kappa_t^T Quu_t kappa_t of the last
+// backward pass, kept in the dV slot of the last G record (no control there).  Without clamped steps it is the reference's
+// -eps (1 - eps / 2) sum_t dV_t (ilqr.py:326).
+template <int n, int m>
+__device__ __forceinline__ double limited_expected(const WS& w, double eps, double sum_dv) {
+  using Ly = Lay<n, m>;
+  return -(eps * sum_dv - 0.5 * eps * eps * w.G[(w.N - 1) * Ly::GS + Ly::DV]);
 }
 
 // `slot` >= 0: this lane stores its trajectory into T buffer `slot`; < 0: stores are parked.
@@ -481,7 +524,8 @@ __device__ inline void rollout(const WS& w, const Consts<M>& c, const KArgs& a, 
   if (t < N - 1) rollout_step<M, COST>(A, c, a, eps, ce, x, L, expd, tw, pool);
   if (COST) L += terminal_cost<M>(c, x);            // ilqr.py:327
   L_out = L;
-  exp_out = expd;
+  if constexpr (UsesLimits<M>::value) exp_out = limited_expected<n, m>(w, eps, expd);
+  else exp_out = expd;
 }
 
 // Sum over each 16-lane row, result in every lane of the row: four DPP row rotations (8, 4, 2, 1)
@@ -534,7 +578,8 @@ __device__ inline void traj_cost(const WS& w, const Consts<M>& c, double eps, do
     }
   }
   L_out = wave_sum(acc);
-  exp_out = -eps * (1.0 - eps / 2.0) * wave_sum(dvs);
+  if constexpr (UsesLimits<M>::value) exp_out = limited_expected<n, m>(w, eps, wave_sum(dvs));
+  else exp_out = -eps * (1.0 - eps / 2.0) * wave_sum(dvs);
 }
 
 // ---------------------------------------------------------------------------
@@ -1004,13 +1049,13 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
 template <class M>
 __device__ __forceinline__ bool newton_capable(const WS& w, const KArgs& a) {
   // four steps per lane: horizons up to N = 257
-  if constexpr (M::n == 2 && M::m == 1) return a.newton_rollout != 0 && w.N - 1 <= 64 * 4;
+  if constexpr (M::n == 2 && M::m == 1 && !UsesLimits<M>::value) return a.newton_rollout != 0 && w.N - 1 <= 64 * 4;
   return false;
 }
 template <class M, int JAC>
 __device__ inline int rollout_newton(const WS& w, const Consts<M>& c, const KArgs& a, const double* x0r, double eps,
                                      int fuse, double L_last, double& L_out, bool coarse = false) {
-  if constexpr (M::n == 2 && M::m == 1) {
+  if constexpr (M::n == 2 && M::m == 1 && !UsesLimits<M>::value) {
     if (newton_capable<M>(w, a)) return rollout_newton_impl<M, JAC, 4>(w, c, a, x0r, eps, fuse, L_last, L_out, coarse);
   }
   return NEWTON_FAILED;
@@ -1488,6 +1533,334 @@ __device__ inline void backward_scalar(const WS& w, const Consts<M>& c) {
     j -= 2 * Ly::JS;
   }
   if (t == 0) backward_step<M>(A, c, Q2, R2, Vx, Vxx, gw);
+}
+
+// ---------------------------------------------------------------------------
+// Backward step with box control limits (Limited<M> kernels, m <= 2): given the expansion Qx, Qu, Qxx, Quu, Qux of
+// step t (ilqr.py:651-656), solve  du* = argmin 1/2 du^T Quu du + Qu^T du  subject to  lo <= du <= hi
+// (lo = u_min - u_bar_t, hi = u_max - u_bar_t) and set kappa = -du*.
+//   m = 1: the clamp of -Qu / Quu.
+//   m = 2: the unconstrained minimiser when it lies in the box; otherwise the best of the four edges u0 = lo0, u0 = hi0,
+//          u1 = lo1, u1 = hi1 (infinite edges skipped), each with the free component's clamped 1-D minimiser (the row of
+//          Quu du + Qu = 0 it solves); the smallest objective wins, a tie goes to the earlier edge.
+// The clamped components are those the chosen candidate put on a bound - decided by that construction, never by
+// comparing floats afterwards.  Their rows of K are 0; the free rows are Quu_ff^-1 Qux_f.  With nothing clamped every
+// output is the reference's arithmetic (backward_step); otherwise dV = kappa^T Qu and the value update takes its general
+// form Vx = Qx - K^T Qu - Qux^T kappa + K^T Quu kappa, Vxx = Qxx - K^T Qux - Qux^T K + K^T Quu K.
+// s2 accumulates kappa^T Quu kappa.  Returns false when Quu is not positive definite (no minimiser; the problem stops
+// with MI_STATUS_NOT_PD).  Shared by the wave- and lane-per-problem kernels.
+// ---------------------------------------------------------------------------
+template <int n, int m>
+__device__ __forceinline__ bool box_qp_step(const double (&Qx)[n], const double (&Qu)[m], const double (&Qxx)[n][n],
+                                            const double (&Quu)[m][m], const double (&Qux)[m][n], const double (&lo)[m],
+                                            const double (&hi)[m], double (&kap)[m], double (&Kg)[m][n], double& dv,
+                                            double& s2, double (&Vx)[n], double (&Vxx)[n][n]) {
+  static_assert(m >= 1 && m <= 2, "box QP of the m <= 2 kernels");
+  bool pd;
+  if constexpr (m == 1) pd = Quu[0][0] > 0.0 && __builtin_isfinite(Quu[0][0]);
+  else {
+    const double det = Quu[0][0] * Quu[1][1] - Quu[0][1] * Quu[1][0];
+    pd = Quu[0][0] > 0.0 && det > 0.0 && __builtin_isfinite(det) && __builtin_isfinite(Quu[0][0]) && __builtin_isfinite(Quu[1][1]) &&
+         __builtin_isfinite(Quu[0][1]) && __builtin_isfinite(Quu[1][0]);
+  }
+  double Qi[m][m];
+  invert_small<m>(Quu, Qi);
+  double d[m];                                              // du*, the minimiser
+  bool cl[m];                                               // component on a bound
+#pragma unroll
+  for (int a_ = 0; a_ < m; ++a_) {
+    double s = 0.0;
+#pragma unroll
+    for (int b_ = 0; b_ < m; ++b_) s += Qi[a_][b_] * Qu[b_];
+    d[a_] = -s;
+    cl[a_] = false;
+  }
+  if constexpr (m == 1) {
+    if (d[0] < lo[0]) { d[0] = lo[0]; cl[0] = true; }
+    else if (d[0] > hi[0]) { d[0] = hi[0]; cl[0] = true; }
+  } else {
+    const bool inside = !(d[0] < lo[0]) && !(d[0] > hi[0]) && !(d[1] < lo[1]) && !(d[1] > hi[1]);
+    if (!inside) {
+      double best = __builtin_inf();
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int fx_ = e >> 1, fr = 1 - fx_;                // the component on the edge, the free one
+        const double v = (e & 1) ? hi[fx_] : lo[fx_];
+        if (!__builtin_isfinite(v)) continue;
+        double f = -(Qu[fr] + Quu[fr][fx_] * v) / Quu[fr][fr];
+        bool cf = false;
+        if (f < lo[fr]) { f = lo[fr]; cf = true; }
+        else if (f > hi[fr]) { f = hi[fr]; cf = true; }
+        double c2[2];
+        c2[fx_] = v; c2[fr] = f;
+        const double obj = 0.5 * (c2[0] * (Quu[0][0] * c2[0] + Quu[0][1] * c2[1]) + c2[1] * (Quu[1][0] * c2[0] + Quu[1][1] * c2[1])) +
+                           (Qu[0] * c2[0] + Qu[1] * c2[1]);
+        if (obj < best) {
+          best = obj;
+          d[0] = c2[0]; d[1] = c2[1];
+          cl[fx_] = true; cl[fr] = cf;
+        }
+      }
+    }
+  }
+  bool any = false;
+#pragma unroll
+  for (int a_ = 0; a_ < m; ++a_) { kap[a_] = -d[a_]; any = any || cl[a_]; }
+  double Qk[m];                                             // Quu kappa
+#pragma unroll
+  for (int a_ = 0; a_ < m; ++a_) {
+    double s = 0.0;
+#pragma unroll
+    for (int b_ = 0; b_ < m; ++b_) s += Quu[a_][b_] * kap[b_];
+    Qk[a_] = s;
+  }
+  double kqk = 0.0;
+#pragma unroll
+  for (int a_ = 0; a_ < m; ++a_) kqk += kap[a_] * Qk[a_];
+  s2 += kqk;
+  if (!any) {
+    // the reference's step (ilqr.py:659-667; backward_step)
+    double QuQi[m];
+#pragma unroll
+    for (int a_ = 0; a_ < m; ++a_) {
+      double s = 0.0, q = 0.0;
+#pragma unroll
+      for (int b_ = 0; b_ < m; ++b_) { s += Qi[a_][b_] * Qu[b_]; q += Qu[b_] * Qi[b_][a_]; }
+      kap[a_] = s;
+      QuQi[a_] = q;
+#pragma unroll
+      for (int j = 0; j < n; ++j) {
+        double g = 0.0;
+#pragma unroll
+        for (int b_ = 0; b_ < m; ++b_) g += Qi[a_][b_] * Qux[b_][j];
+        Kg[a_][j] = g;
+      }
+    }
+    dv = 0.0;
+#pragma unroll
+    for (int a_ = 0; a_ < m; ++a_) dv += QuQi[a_] * Qu[a_];
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      double s = Qx[j];
+#pragma unroll
+      for (int a_ = 0; a_ < m; ++a_) s -= QuQi[a_] * Qux[a_][j];
+      Vx[j] = s;
+    }
+    double QuxTQi[n][m];
+#pragma unroll
+    for (int i = 0; i < n; ++i)
+#pragma unroll
+      for (int b_ = 0; b_ < m; ++b_) {
+        double s = 0.0;
+#pragma unroll
+        for (int a_ = 0; a_ < m; ++a_) s += Qux[a_][i] * Qi[a_][b_];
+        QuxTQi[i][b_] = s;
+      }
+#pragma unroll
+    for (int i = 0; i < n; ++i)
+#pragma unroll
+      for (int j = 0; j < n; ++j) {
+        double s = Qxx[i][j];
+#pragma unroll
+        for (int b_ = 0; b_ < m; ++b_) s -= QuxTQi[i][b_] * Qux[b_][j];
+        Vxx[i][j] = s;
+      }
+    return pd;
+  }
+  // K: clamped rows 0, free rows Quu_ff^-1 Qux_f (at most one free component here)
+#pragma unroll
+  for (int a_ = 0; a_ < m; ++a_)
+#pragma unroll
+    for (int j = 0; j < n; ++j) Kg[a_][j] = cl[a_] ? 0.0 : Qux[a_][j] / Quu[a_][a_];
+  dv = 0.0;
+#pragma unroll
+  for (int a_ = 0; a_ < m; ++a_) dv += kap[a_] * Qu[a_];
+  double QK[m][n];                                          // Quu K
+#pragma unroll
+  for (int a_ = 0; a_ < m; ++a_)
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      double s = 0.0;
+#pragma unroll
+      for (int b_ = 0; b_ < m; ++b_) s += Quu[a_][b_] * Kg[b_][j];
+      QK[a_][j] = s;
+    }
+#pragma unroll
+  for (int j = 0; j < n; ++j) {
+    double s = Qx[j];
+#pragma unroll
+    for (int a_ = 0; a_ < m; ++a_) s += -Kg[a_][j] * Qu[a_] - Qux[a_][j] * kap[a_] + Kg[a_][j] * Qk[a_];
+    Vx[j] = s;
+  }
+#pragma unroll
+  for (int i = 0; i < n; ++i)
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      double s = Qxx[i][j];
+#pragma unroll
+      for (int a_ = 0; a_ < m; ++a_) s += -Kg[a_][i] * Qux[a_][j] - Qux[a_][i] * Kg[a_][j] + Kg[a_][i] * QK[a_][j];
+      Vxx[i][j] = s;
+    }
+  return pd;
+}
+
+// Cost-to-go expansion of one step (ilqr.py:651-656; backward_step's arithmetic) from the cost gradients lx, lu.
+template <int n, int m>
+__device__ __forceinline__ void q_expansion(const double (&lx)[n], const double (&lu)[m], const double (&fx)[n][n],
+                                            const double (&fu)[n][m], const double (&Q2)[n][n], const double (&R2)[m][m],
+                                            const double (&Vx)[n], const double (&Vxx)[n][n], double (&Qx)[n], double (&Qu)[m],
+                                            double (&Qxx)[n][n], double (&Quu)[m][m], double (&Qux)[m][n]) {
+#pragma unroll
+  for (int i = 0; i < n; ++i) {
+    double s = lx[i];
+#pragma unroll
+    for (int k = 0; k < n; ++k) s += fx[k][i] * Vx[k];
+    Qx[i] = s;
+  }
+#pragma unroll
+  for (int a_ = 0; a_ < m; ++a_) {
+    double s = lu[a_];
+#pragma unroll
+    for (int k = 0; k < n; ++k) s += fu[k][a_] * Vx[k];
+    Qu[a_] = s;
+  }
+  double A[n][n], Bm[m][n];
+#pragma unroll
+  for (int i = 0; i < n; ++i)
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < n; ++k) s += fx[k][i] * Vxx[k][j];
+      A[i][j] = s;
+    }
+#pragma unroll
+  for (int a_ = 0; a_ < m; ++a_)
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < n; ++k) s += fu[k][a_] * Vxx[k][j];
+      Bm[a_][j] = s;
+    }
+#pragma unroll
+  for (int i = 0; i < n; ++i)
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      double s = Q2[i][j];
+#pragma unroll
+      for (int k = 0; k < n; ++k) s += A[i][k] * fx[k][j];
+      Qxx[i][j] = s;
+    }
+#pragma unroll
+  for (int a_ = 0; a_ < m; ++a_) {
+#pragma unroll
+    for (int b_ = 0; b_ < m; ++b_) {
+      double s = R2[a_][b_];
+#pragma unroll
+      for (int k = 0; k < n; ++k) s += Bm[a_][k] * fu[k][b_];
+      Quu[a_][b_] = s;
+    }
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < n; ++k) s += Bm[a_][k] * fx[k][j];
+      Qux[a_][j] = s;
+    }
+  }
+}
+
+// The limited backward pass: backward_scalar's sweep (wave-uniform, one step ahead prefetch) with the box QP per step.
+// Lane 0 writes the gains, dV and - into the last G record's dV slot - S2.  Returns false when some Quu was not
+// positive definite.
+template <class M>
+struct LRegs : BRegs<M> {
+  double ub[M::m];
+  __device__ __forceinline__ void load(const double* tr, const double* j, const double* g) {
+    BRegs<M>::load(tr, j);
+#pragma unroll
+    for (int k = 0; k < M::m; ++k) ub[k] = g[Lay<M::n, M::m>::UB + k];
+  }
+};
+template <class M>
+__device__ __forceinline__ bool backward_step_limited(const LRegs<M>& r, const Consts<M>& c, const double (&Q2)[M::n][M::n],
+                                                      const double (&R2)[M::m][M::m], double (&Vx)[M::n],
+                                                      double (&Vxx)[M::n][M::n], double& s2, double* gw) {
+  constexpr int n = M::n, m = M::m;
+  using Ly = Lay<n, m>;
+  double Qx[n], Qu[m], Qxx[n][n], Quu[m][m], Qux[m][n];
+  q_expansion<n, m>(r.lx, r.lu, r.fx, r.fu, Q2, R2, Vx, Vxx, Qx, Qu, Qxx, Quu, Qux);
+  double lo[m], hi[m];
+#pragma unroll
+  for (int k = 0; k < m; ++k) { lo[k] = c.umin[k] - r.ub[k]; hi[k] = c.umax[k] - r.ub[k]; }
+  double kap[m], Kg[m][n], dv;
+  const bool ok = box_qp_step<n, m>(Qx, Qu, Qxx, Quu, Qux, lo, hi, kap, Kg, dv, s2, Vx, Vxx);
+#pragma unroll
+  for (int a_ = 0; a_ < m; ++a_) {
+    gw[Ly::KAP + a_] = kap[a_];
+#pragma unroll
+    for (int j = 0; j < n; ++j) gw[Ly::KK + a_ * n + j] = Kg[a_][j];
+  }
+  gw[Ly::DV] = dv;
+  return ok;
+}
+
+template <class M>
+__device__ inline bool backward_limited(const WS& w, const Consts<M>& c) {
+  constexpr int n = M::n, m = M::m;
+  using Ly = Lay<n, m>;
+  const int N = w.N;
+  double Q2[n][n], R2[m][m];
+#pragma unroll
+  for (int i = 0; i < n; ++i)
+#pragma unroll
+    for (int j = 0; j < n; ++j) Q2[i][j] = 2.0 * c.Q[i][j];
+#pragma unroll
+  for (int i = 0; i < m; ++i)
+#pragma unroll
+    for (int j = 0; j < m; ++j) R2[i][j] = 2.0 * c.R[i][j];
+  double Vx[n], Vxx[n][n];
+  {
+    const double* gT = w.G + (N - 1) * Ly::GS;
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j < n; ++j) { s += (2.0 * c.Qf[i][j]) * gT[Ly::XB + j]; Vxx[i][j] = 2.0 * c.Qf[i][j]; }
+      Vx[i] = s - c.qfn[i];                                 // ilqr.py:203-204
+    }
+  }
+  cost_gradients<M>(w, c, Q2, R2);
+  wave_sync();
+  const bool writer = threadIdx.x == 0;
+  const double* g = w.T + (N - 2) * Ly::TS;
+  const double* j = w.J + (N - 2) * Ly::JS;
+  const double* gb = w.G + (N - 2) * Ly::GS;
+  double* gw = writer ? (w.G + (N - 2) * Ly::GS) : (w.dump + 2 * threadIdx.x);
+  const int gstep = writer ? Ly::GS : 0;
+  double s2 = 0.0;
+  bool ok = true;
+  LRegs<M> A, B;
+  A.load(g, j, gb);
+  int t = N - 2;
+  for (; t >= 1; t -= 2) {
+    B.load(g - Ly::TS, j - Ly::JS, gb - Ly::GS);
+    __builtin_amdgcn_sched_barrier(0);                   // keep the prefetch a full step ahead
+    ok = backward_step_limited<M>(A, c, Q2, R2, Vx, Vxx, s2, gw) && ok;
+    gw -= gstep;
+    A.load(g - 2 * Ly::TS, j - 2 * Ly::JS, gb - 2 * Ly::GS);   // t-2 >= -1: the leading pad record
+    __builtin_amdgcn_sched_barrier(0);
+    ok = backward_step_limited<M>(B, c, Q2, R2, Vx, Vxx, s2, gw) && ok;
+    gw -= gstep;
+    g -= 2 * Ly::TS;
+    j -= 2 * Ly::JS;
+    gb -= 2 * Ly::GS;
+  }
+  if (t == 0) ok = backward_step_limited<M>(A, c, Q2, R2, Vx, Vxx, s2, gw) && ok;
+  wave_sync();
+  w.G[(N - 1) * Ly::GS + Ly::DV] = s2;                    // (wave-uniform value, every lane stores it)
+  return ok;
 }
 
 typedef double d4s_t __attribute__((ext_vector_type(4)));
@@ -2063,7 +2436,7 @@ __device__ inline void batch_stats_by_last_workgroup(const KArgs& a, int b, doub
   if (ticket != (int)gridDim.x - 1) return;
   const int B = a.B;
   long long it = 0, ls = 0;
-  int c = 0, mxi = 0, nm = 0, nf = 0, bi = -1;
+  int c = 0, mxi = 0, nm = 0, nf = 0, npd = 0, bi = -1;
   double bc = __builtin_inf();
   constexpr int U = 4;                                         // 4 x 4 independent loads in flight per lane
   for (int q0 = lane; q0 < B; q0 += 64 * U) {
@@ -2084,6 +2457,7 @@ __device__ inline void batch_stats_by_last_workgroup(const KArgs& a, int b, doub
         mxi = iq[u] > mxi ? iq[u] : mxi;
         if (sq[u] == MI_STATUS_CONVERGED) { c++; if (cq[u] < bc) { bc = cq[u]; bi = q; } }
         else if (sq[u] == MI_STATUS_MAX_ITERS) nm++;
+        else if (sq[u] == MI_STATUS_NOT_PD) npd++;              // (Limited<M> kernels)
         else nf++;
       }
     }
@@ -2091,7 +2465,7 @@ __device__ inline void batch_stats_by_last_workgroup(const KArgs& a, int b, doub
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     it += __shfl_xor(it, o); ls += __shfl_xor(ls, o);
-    c += __shfl_xor(c, o); nm += __shfl_xor(nm, o); nf += __shfl_xor(nf, o);
+    c += __shfl_xor(c, o); nm += __shfl_xor(nm, o); nf += __shfl_xor(nf, o); npd += __shfl_xor(npd, o);
     const int m2 = __shfl_xor(mxi, o); mxi = m2 > mxi ? m2 : mxi;
     const double bc2 = __shfl_xor(bc, o); const int bi2 = __shfl_xor(bi, o);
     if (bc2 < bc || (bc2 == bc && bi2 >= 0 && (bi < 0 || bi2 < bi))) { bc = bc2; bi = bi2; }
@@ -2099,7 +2473,7 @@ __device__ inline void batch_stats_by_last_workgroup(const KArgs& a, int b, doub
   if (lane == 0) {
     DevStats* o = a.stats_out;
     o->total_iters = it; o->total_ls = ls; o->n_conv = c; o->n_max = nm; o->n_fail = nf;
-    o->max_iters_seen = mxi; o->best_index = bi; o->best_cost = bc; o->n_internal = 0; o->n_not_pd = 0;   // (these kernels have no such exits)
+    o->max_iters_seen = mxi; o->best_index = bi; o->best_cost = bc; o->n_internal = 0; o->n_not_pd = npd;   // (no internal exits here)
     __hip_atomic_store(a.done_counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
   }
 }
@@ -2197,6 +2571,12 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
     for (int i = 0; i < n; ++i) x0r[i] = a.x0[(size_t)b * n + i];
     if constexpr (UsesScanBackward<M>::value) c.to_lds(w.cst);
   }
+  if constexpr (UsesLimits<M>::value) {
+    c.load_limits(a.ulim + (size_t)b * 2 * m);
+    // S2 of the last backward pass (limited_expected), stored by every lane: a lane-0 branch here put spill copies at its join
+    // ahead of the EXEC restore (tools/check_exec_spill.py)
+    w.G[(N - 1) * Ly::GS + Ly::DV] = cold ? 0.0 : a.s2[b];
+  }
   wave_sync();
 
   if (MODE == MODE_ROLLOUT) {
@@ -2217,7 +2597,12 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
     return;
   }
   if (MODE == MODE_BACKWARD) {
-    backward<M>(w, c, a.seq_backward);
+    if constexpr (UsesLimits<M>::value) {
+      const bool pd = backward_limited<M>(w, c);
+      if (lane == 0) { a.s2[b] = w.G[(N - 1) * Ly::GS + Ly::DV]; a.status[b] = pd ? MI_STATUS_CONVERGED : MI_STATUS_NOT_PD; }
+    } else {
+      backward<M>(w, c, a.seq_backward);
+    }
     wave_sync();
     stage_out(a.K + oK, w.G, Ly::GS, Ly::KK, m * n, N - 1);
     stage_out(a.kappa + oU, w.G, Ly::GS, Ly::KAP, m, N - 1);
@@ -2315,7 +2700,12 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
         nk = linearize<M, JAC>(w, a);                             // at the ACCEPTED trajectory (:370)
       }
       const long long c2 = clock64();
-      if (MODE != MODE_FORWARD) { backward<M>(w, c, a.seq_backward); wave_sync(); } // :697
+      bool pd = true;
+      if (MODE != MODE_FORWARD) {                                 // :697
+        if constexpr (UsesLimits<M>::value) pd = backward_limited<M>(w, c);
+        else backward<M>(w, c, a.seq_backward);
+        wave_sync();
+      }
       // LongHorizon kernels: backward() is a real call; re-reading the constants from their LDS image instead
       // of keeping 90 registers alive across it leaves the line-search loops their old allocation
       if constexpr (UsesScanBackward<M>::value) c.from_lds(w.cst);
@@ -2340,6 +2730,7 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
       improvement = L - L_new;                                    // :706
       L = L_new;
       it_this += 1;
+      if (!pd) { status = MI_STATUS_NOT_PD; break; }             // limited: no box-QP minimiser, gains unusable
       if (MODE == MODE_FORWARD) break;
     }
     iters += it_this;
@@ -2350,7 +2741,7 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
         for (int i = 0; i < n; ++i) lg[i] = x0r[i];
         lg[n] = L; lg[n + 1] = (double)it_this;
       }
-      if (status == MI_STATUS_LINESEARCH_FAILED) break;
+      if (status == MI_STATUS_LINESEARCH_FAILED || status == MI_STATUS_NOT_PD) break;
     }
   }
   if (MODE == MODE_MPC && lane < n) {               // the re-solves moved x0: keep the HBM copy consistent
@@ -2437,6 +2828,9 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
     }
   }
   for (int i = lane; i < nk; i += 64) a.kp_list[(size_t)b * (N - 1) + i] = w.kp[i];
+  if constexpr (UsesLimits<M>::value) {
+    if ((MODE == MODE_SOLVE || MODE == MODE_MPC) && lane == 0) a.s2[b] = w.G[(N - 1) * Ly::GS + Ly::DV];
+  }
   if (lane == 0) {
     a.cost[b] = L; a.iters[b] = iters; a.status[b] = status; a.ls_trials[b] = ls_total; a.kp_count[b] = nk;
     if (a.sink_cost != nullptr) a.sink_cost[b] = L;

@@ -22,4 +22,8 @@ int launch_batch(mi_ilqr* h, int mode, const KArgs& a) {
   return launch_batch_one<M, MI_JAC_FD_CENTRAL>(h, a);
 }
 
+// Handles with control limits: the Limited<M> lane-per-problem kernels (k_batch_lim.hip, the plugin units).
+template <class M>
+int launch_batch_limited(mi_ilqr* h, int mode, const KArgs& a) { return launch_batch<Limited<M>>(h, mode, a); }
+
 }  // namespace mi_host

@@ -55,4 +55,13 @@ int launch_jac(mi_ilqr* h, int mode, const KArgs& a) {
   return launch_mode<M, MI_JAC_FD_CENTRAL>(h, mode, a);
 }
 
+// Handles with control limits (mi_ilqr_set_control_limits): the Limited<M> kernels - sequential rollout with the clamp, the
+// box-QP backward pass - for every mode.  Instantiated apart from launch_jac (k_<model>_lim.hip, the plugin units) so that
+// the parallel build keeps its shape.
+template <class M>
+int launch_limited(mi_ilqr* h, int mode, const KArgs& a) {
+  if (h->d.jacobian_mode == MI_JAC_AUTODIFF) return launch_mode<Limited<M>, MI_JAC_AUTODIFF>(h, mode, a);
+  return launch_mode<Limited<M>, MI_JAC_FD_CENTRAL>(h, mode, a);
+}
+
 }  // namespace mi_host

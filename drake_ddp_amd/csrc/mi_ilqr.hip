@@ -151,6 +151,8 @@ KArgs make_args(const mi_ilqr* h) {
   a.pd_continue = h->d.on_indefinite == 1 ? 1 : 0;
   a.cost_asym = h->cost_asym ? 1 : 0;
   a.q_diag = h->q_diag ? 1 : 0;
+  a.ulim = h->limited ? h->ulim : nullptr;
+  a.s2 = h->s2;
   static const int spec = [] { const char* e = std::getenv("MI_ILQR_SPEC"); return e ? std::atoi(e) : 1; }();
   a.spec_policy = (h->x_spec && spec >= 0 && spec <= 2) ? spec : 0;
   a.cluster = 1;
@@ -220,7 +222,16 @@ int launch(mi_ilqr* h, int mode) {
   int rc;
   if (h->batch_minor) {
     if (const PluginSlot* ps = plugin_of(h->d.model_id)) return ps->p.launch(h, mode, &a);   // (family-0 plugins carry the lane-per-problem kernels too)
-    return launch_batch_minor(h, mode, a);
+    return h->limited ? launch_batch_minor_lim(h, mode, a) : launch_batch_minor(h, mode, a);
+  }
+  if (h->limited) {                                // (plugins pick their Limited<M> kernels in their own launch entry)
+    switch (h->d.model_id) {
+      case MI_MODEL_PENDULUM: return launch_pendulum_lim(h, mode, a);
+      case MI_MODEL_ACROBOT: return launch_acrobot_lim(h, mode, a);
+      case MI_MODEL_CARTPOLE: return launch_cartpole_lim(h, mode, a);
+      case MI_MODEL_CARTPOLE_WALL: return launch_cartpole_wall_lim(h, mode, a);
+      default: break;
+    }
   }
   switch (h->d.model_id) {
     case MI_MODEL_PENDULUM: rc = launch_pendulum(h, mode, a); break;
@@ -250,6 +261,7 @@ int materialize_zero_state(mi_ilqr* h) {
   HIPCHK(hipMemsetAsync(h->dV, 0, B * (N - 1) * 8, h->stream));
   HIPCHK(hipMemsetAsync(h->fx, 0, B * n * n * (N - 1) * 8, h->stream));
   HIPCHK(hipMemsetAsync(h->fu, 0, B * n * m * (N - 1) * 8, h->stream));
+  if (h->s2) HIPCHK(hipMemsetAsync(h->s2, 0, B * 8, h->stream));
   h->cold = false;
   return MI_ILQR_OK;
 }
@@ -811,7 +823,8 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
   }
   void* ptrs[] = {h->x_bar, h->u_bar, h->K, h->kappa, h->dV, h->fx, h->fu, h->x0, h->u_guess, h->cost_ring, h->hist, h->iter_cyc,
                   h->x_trial, h->u_trial, h->trial_cost, h->stage_in, h->costmat, h->iters_ring, h->status_ring, h->ls_ring,
-                  h->kp_count, h->kp_list, h->prof, h->done_counter, h->cluster_sync, h->bm_scratch, h->x_spec, h->u_spec, h->lxu};
+                  h->kp_count, h->kp_list, h->prof, h->done_counter, h->cluster_sync, h->bm_scratch, h->x_spec, h->u_spec, h->lxu,
+                  h->ulim, h->s2};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->mpc_log) (void)hipFree(h->mpc_log);
@@ -1066,6 +1079,34 @@ int mi_ilqr_reset(mi_ilqr_t* h) {
   h->cold = true;          // zeros are materialized lazily (the kernels skip the HBM read)
   h->u_zero = true;        // a fresh reference object has u_bar = 0 until SetInitialGuess (ilqr.py:71,148-156)
   h->u_pending = false;
+  return MI_ILQR_OK;
+}
+
+int mi_ilqr_set_control_limits(mi_ilqr_t* h, const double* u_min, const double* u_max, int32_t per_problem) {
+  if (!h) return MI_ILQR_E_BAD_ARG;
+  if (h->large) return MI_ILQR_E_UNSUPPORTED;      // workgroup-per-problem kernels: no box-QP backward pass (yet)
+  if (!u_min && !u_max) { h->limited = false; return MI_ILQR_OK; }   // the regular kernels again, state untouched
+  if (!u_min || !u_max) return MI_ILQR_E_BAD_ARG;
+  const int m = h->m, B = h->B;
+  const size_t rows = per_problem ? (size_t)B : 1;
+  for (size_t i = 0; i < rows * m; ++i) {
+    const double lo = u_min[i], hi = u_max[i];
+    if (lo != lo || hi != hi || lo > hi) return MI_ILQR_E_BAD_ARG;   // NaN, or an empty box
+  }
+  HIPCHK(hipSetDevice(h->d.device_id));
+  if (!h->ulim) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->ulim), (size_t)B * 2 * m * 8));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->s2), (size_t)B * 8));
+    HIPCHK(hipMemsetAsync(h->s2, 0, (size_t)B * 8, h->stream));
+  }
+  std::vector<double> box((size_t)B * 2 * m);     // (B, 2, m): u_min | u_max, shared bounds broadcast here
+  for (int b = 0; b < B; ++b) {
+    const size_t src = per_problem ? (size_t)b * m : 0;
+    for (int k = 0; k < m; ++k) { box[((size_t)b * 2) * m + k] = u_min[src + k]; box[((size_t)b * 2 + 1) * m + k] = u_max[src + k]; }
+  }
+  const int rc = stage_h2d(h, h->ulim, box.data(), box.size() * 8);
+  if (rc != MI_ILQR_OK) return rc;
+  h->limited = true;
   return MI_ILQR_OK;
 }
 

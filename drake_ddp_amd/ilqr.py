@@ -50,7 +50,8 @@ class BatchedIterativeLQR:
 
     def __init__(self, system, num_timesteps, batch, input_port_index=0, delta=1e-2, beta=0.95, gamma=0.0,
                  derivs_keypoint_method=None, jacobian_mode="fd", fd_step=1e-5, device=0,
-                 max_iters=1000, hist_cap=64, kernel_mode="auto", pinned_results=True, on_indefinite="stop"):
+                 max_iters=1000, hist_cap=64, kernel_mode="auto", pinned_results=True, on_indefinite="stop",
+                 control_limits="ignore"):
         assert isinstance(system, ModelSystem), \
             "system must be a drake_ddp_amd.models.ModelSystem (Drake systems cannot run on the GPU)"
         assert system.IsDifferenceEquationSystem()[0], "must be a discrete-time system"   # ilqr.py:37
@@ -97,6 +98,18 @@ class BatchedIterativeLQR:
         h = C.c_void_p()
         _capi.check(self._lib.mi_ilqr_create(C.byref(d), C.byref(h)), "mi_ilqr_create")
         self._h = h
+        # control_limits: "ignore" (default) keeps the reference's SetControlLimits, a no-op (ilqr.py:158-159); "enforce" makes it
+        # bound the controls (include/mi_ilqr.h: mi_ilqr_set_control_limits) - the m <= 2 kernel families only
+        if control_limits not in ("ignore", "enforce"):
+            raise ValueError(f'control_limits must be "ignore" or "enforce", got {control_limits!r}')
+        self.control_limits = control_limits
+        if control_limits == "enforce":
+            rc = self._lib.mi_ilqr_set_control_limits(h, None, None, 0)
+            if rc == _capi.E_UNSUPPORTED:
+                raise ValueError("control_limits='enforce' is served by the m <= 2 kernel families only (wave-per-problem "
+                                 "LATENCY and lane-per-problem THROUGHPUT kernels: the built-in pendulum, acrobot, cart-pole "
+                                 "models and family-0 plugins); this model runs on the workgroup-per-problem kernels")
+            _capi.check(rc, "mi_ilqr_set_control_limits")
         # pinned_results (the default): the arrays the state attributes / Solve() return are views of page-locked buffers
         # (direct DMA, no page faults of freshly allocated arrays; the wave-per-problem kernels write x_bar / u_bar / cost
         # into them themselves).  The reference REBINDS its result arrays on every forward pass and never mutates one it
@@ -142,7 +155,32 @@ class BatchedIterativeLQR:
         self._u_guess = u_guess        # aliased like the reference; copied in at Solve()
 
     def SetControlLimits(self, u_min, u_max):
-        pass                           # no-op stub in the reference too (ilqr.py:158-159)
+        """No-op stub in the reference (ilqr.py:158-159), and here unless the solver was built with
+        control_limits="enforce": then u_min <= u <= u_max for every rollout and backward pass of later solves.
+        Scalars (m = 1), (m,) or (B, m); +-inf allowed; (None, None) clears the limits."""
+        if self.control_limits != "enforce":
+            return
+        if u_min is None and u_max is None:
+            _capi.check(self._lib.mi_ilqr_set_control_limits(self._h, None, None, 0), "mi_ilqr_set_control_limits")
+            return
+        if u_min is None or u_max is None:
+            raise ValueError("SetControlLimits: give both bounds, or (None, None) to clear them")
+        lo, hi = (np.asarray(v, dtype=np.float64) for v in (u_min, u_max))
+        if lo.shape != hi.shape:
+            raise ValueError(f"SetControlLimits: u_min {lo.shape} and u_max {hi.shape} differ in shape")
+        if lo.ndim == 0 and self.m == 1:
+            lo, hi = lo.reshape(1), hi.reshape(1)
+        if lo.shape == (self.m,):
+            per_problem = 0
+        elif lo.shape == (self.B, self.m):
+            per_problem = 1
+        else:
+            raise ValueError(f"SetControlLimits: bounds must be scalars (m = 1), ({self.m},) or ({self.B}, {self.m}); got {lo.shape}")
+        if np.isnan(lo).any() or np.isnan(hi).any() or (lo > hi).any():
+            raise ValueError("SetControlLimits: u_min > u_max or NaN")
+        lo, hi = np.ascontiguousarray(lo), np.ascontiguousarray(hi)
+        _capi.check(self._lib.mi_ilqr_set_control_limits(self._h, _capi.ptr(lo), _capi.ptr(hi), per_problem),
+                    "mi_ilqr_set_control_limits")
 
     # ------------------------------------------------------------- boundary traffic
     def _push_problem(self):

@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define MI_ILQR_ABI_VERSION 9   /* 9: mi_ilqr_comm_count; partial reads of MI_F_HIST / MI_F_ITER_CYCLES; MI_I64_CLUSTER_WORDS reads as zeros where no cluster ran;
+#define MI_ILQR_ABI_VERSION 10  /* 10: mi_ilqr_set_control_limits (box control limits of the m <= 2 kernel families);
+                                   9: mi_ilqr_comm_count; partial reads of MI_F_HIST / MI_F_ITER_CYCLES; MI_I64_CLUSTER_WORDS reads as zeros where no cluster ran;
                                    7: mi_ilqr_desc.on_indefinite, mi_ilqr_model_plugin.m_user, 256 plugin slots;
                                    8: MI_STATUS_FLAG_INDEFINITE, on_indefinite = 1 inverts with partial pivoting, asymmetric costs for n <= 32,
                                       the diagnostic field MI_I64_CLUSTER_WORDS */
@@ -268,6 +269,22 @@ int mi_ilqr_host_free(void* p);
  * reference object (ilqr.py:70-83): a solve after it without mi_ilqr_set_initial(u_guess) /
  * mi_ilqr_rearm_initial_guess starts from u_bar = 0.  Without it the state persists across solves (F10). */
 int mi_ilqr_reset(mi_ilqr_t* h);
+
+/* Box control limits u_min <= u <= u_max (the reference's SetControlLimits, ilqr.py:158-159, which is a no-op there): u_min, u_max
+ * are (m,) shared by the batch, or (B,m) when `per_problem` is non-zero; +-inf is allowed, u_min == u_max fixes an input;
+ * u_min > u_max or a NaN is MI_ILQR_E_BAD_ARG.  NULL, NULL clears them: the handle is then bitwise a never-limited one again.
+ * Problem data like mi_ilqr_set_cost - they survive mi_ilqr_reset and apply to solve, mpc_run (every re-solve) and the stage
+ * entries.  Semantics (the convention u = u_bar - eps kappa - K (x - x_bar) kept):
+ *   rollout  every trial applies u_t = clip(u_bar_t - eps kappa_t - K_t (x_t - x_bar_t), u_min, u_max), the first solve's
+ *            included: an initial guess outside the box is projected, every returned u_bar lies inside it exactly;
+ *   backward per step the box QP  du* = argmin 1/2 du^T Quu du + Qu^T du,  u_min - u_bar_t <= du <= u_max - u_bar_t,
+ *            kappa_t = -du*; rows of K of the components du* put on a bound are 0, the free rows Quu_ff^-1 Qux_f; the value
+ *            update takes its general form; MI_F_DV holds kappa_t^T Qu (the reference's Qu^T Quu^-1 Qu when nothing is
+ *            clamped) and a trial's expected improvement is -(eps sum dV - eps^2/2 sum_t kappa_t^T Quu_t kappa_t);
+ *            a Quu that is not positive definite stops the problem with MI_STATUS_NOT_PD (counted in stats.n_not_pd).
+ * Limited handles take sequential rollouts and backward passes (the time-parallel forms carry no active set).  Wave- and
+ * lane-per-problem kernels (m <= 2); on a workgroup-per-problem handle MI_ILQR_E_UNSUPPORTED, the handle stays usable. */
+int mi_ilqr_set_control_limits(mi_ilqr_t* h, const double* u_min, const double* u_max, int32_t per_problem);
 
 /* Benchmark/MPC helper: make the resident u_guess (last mi_ilqr_set_initial or
  * mi_ilqr_mpc_shift) the initial guess of the next solve again, without host traffic. */
