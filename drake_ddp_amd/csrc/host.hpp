@@ -87,7 +87,8 @@ struct mi_ilqr {
   double *x_spec = nullptr, *u_spec = nullptr;   // mid-size kernels: trial trajectories of three more line-search candidates
   int32_t* bm_scratch = nullptr;   // lane-per-problem kernels with key-points: integer scratch (ilqr_batch.hpp)
   double *sink_x = nullptr, *sink_u = nullptr, *sink_cost = nullptr;   // result sink (device aliases of host arrays), optional
-  // control limits (mi_ilqr_set_control_limits; m <= 2 kernel families): `limited` selects the Limited<M> kernels
+  // control limits (mi_ilqr_set_control_limits; the m <= 2 kernel families and the mid-size workgroup family, n <= 32): `limited`
+  // selects the Limited<M> kernels
   bool limited = false;
   double* ulim = nullptr;          // (B, 2, m): u_min | u_max per problem (allocated on first use, kept when cleared)
   double* s2 = nullptr;            // (B,): S2 of each problem's last limited backward pass (KArgs::s2)
@@ -124,6 +125,9 @@ using namespace mi;
   } while (0)
 
 constexpr size_t kMaxLds = 160 * 1024;
+// A plugin's launch entry asked with this mode (and h->limited set) answers MI_ILQR_OK when it carries Limited<M> kernels, launching
+// nothing (mi_ilqr_set_control_limits; family-1 plugins carry them when built with them: plugin.py, control_limits=True).
+constexpr int kModeProbeLimits = 0x4c494d;
 constexpr int kMaxBatchPluginN = 6;      // family-0 plugin models up to this n also get the lane-per-problem kernels
 
 // The dynamic-LDS ceiling of a kernel is raised once per (kernel, device), to the hardware maximum - not
@@ -174,3 +178,5 @@ MI_INTERNAL int launch_acrobot_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
 MI_INTERNAL int launch_cartpole_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
 MI_INTERNAL int launch_cartpole_wall_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
 MI_INTERNAL int launch_batch_minor_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
+MI_INTERNAL int launch_arm27_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
+MI_INTERNAL int launch_arm27c_lim(mi_ilqr* h, int mode, const mi::KArgs& a);

@@ -33,6 +33,10 @@ namespace mi {
 
 constexpr int kLargeThreads = 256;
 constexpr int kPdFlag = 8;          // slot of the reduction scratch (LLay::oRed) where a backward pass leaves "a Quu was not positive definite"
+// Control limits (Limited<M> kernels of the mid-size family, mi_ilqr_set_control_limits): further slots of the reduction scratch
+// (block_sum uses 0..3) - S2 = sum_t kappa_t^T Quu_t kappa_t of the last backward pass, and the problem's bounds u_min | u_max,
+// read once per launch.  The LDS layout and large_lds_bytes stay what they are.
+constexpr int kS2Slot = 9, kLimSlot = 16;
 
 // The thread index of a STAGE (a backward pass, a rollout, a linearization): see stage_lane (ilqr_small.hpp).
 __device__ __forceinline__ int stage_tid() { return stage_lane(); }
@@ -301,6 +305,20 @@ template <class M>
 struct EarlyLeaderBlocks<M, decltype((void)M::kEarlyLeaderBlocks)> { static constexpr int value = M::kEarlyLeaderBlocks; };
 template <class M>
 constexpr bool kEarlyLin = M::m * 16 <= 192;                 // (the fourth wave holds no control-law lanes: no prefetch loads on it)
+// clip(v, u_min_k, u_max_k) by comparisons (a NaN stays NaN: its trial is rejected as without limits)
+template <class M>
+__device__ __forceinline__ double lim_clamp(const double* lds, int k, double v) {
+  using Ly = LLay<M::n, M::m>;
+  const double lo = lds[Ly::oRed + kLimSlot + k], hi = lds[Ly::oRed + kLimSlot + M::m + k];
+  v = v < lo ? lo : v;
+  return v > hi ? hi : v;
+}
+// Expected improvement of a trial with step eps (ilqr.py:326); Limited<M>: -(eps sum dV - eps^2 / 2 S2).
+template <class M>
+__device__ __forceinline__ double ls_expected(const double* lds, double eps, double dvs) {
+  if constexpr (UsesLimits<M>::value) return -(eps * dvs - 0.5 * eps * eps * lds[LLay<M::n, M::m>::oRed + kS2Slot]);
+  else return -eps * (1.0 - eps / 2.0) * dvs;
+}
 template <class M>
 __device__ inline double large_rollout(const LView<M::n, M::m>& v, double* lds, const KArgs& a,
                                        const double* x0g, double eps, double& expd_out,
@@ -401,7 +419,10 @@ __device__ inline double large_rollout(const LView<M::n, M::m>& v, double* lds, 
         if (j < n) p += f.kr[q] * (xc[j] - f.xbr[q]);
       }
       p = row16_sum(p);
-      if (ul == 0) us[uk] = (f.ubk - eps * f.kpk) - p;
+      if (ul == 0) {
+        if constexpr (UsesLimits<M>::value) us[uk] = lim_clamp<M>(lds, uk, (f.ubk - eps * f.kpk) - p);   // clip(u, u_min, u_max)
+        else us[uk] = (f.ubk - eps * f.kpk) - p;
+      }
     }
     if (drole) {
       const double xv_ = xc[tid - 192];
@@ -604,7 +625,7 @@ __device__ inline double large_rollout(const LView<M::n, M::m>& v, double* lds, 
   double* red = lds + Ly::oRed;
   double L = block_sum(acc, red);
   const double dvs = block_sum(dvp, red);
-  expd_out = -eps * (1.0 - eps / 2.0) * dvs;             // ilqr.py:326
+  expd_out = ls_expected<M>(lds, eps, dvs);              // ilqr.py:326
   if constexpr (CanFail<M>::value) {
     // a step was declared infeasible: the trial's cost is +inf (ilqr.py:317-323; the reference stops simulating
     // there - what this rollout computed past that step is never looked at: L = inf is never accepted, :330)
@@ -731,7 +752,10 @@ __device__ inline void mid_rollout4(const LView<M::n, M::m>& v, double* xsp, dou
       for (int c = 0; c < kSpec; ++c) p[c] = row16_sum(p[c]);
       if (ul == 0) {
 #pragma unroll
-        for (int c = 0; c < kSpec; ++c) us4[c * 16 + uk] = (f.ubk - eps4[c] * f.kpk) - p[c];
+        for (int c = 0; c < kSpec; ++c) {
+          if constexpr (UsesLimits<M>::value) us4[c * 16 + uk] = lim_clamp<M>(lds, uk, (f.ubk - eps4[c] * f.kpk) - p[c]);
+          else us4[c * 16 + uk] = (f.ubk - eps4[c] * f.kpk) - p[c];
+        }
       }
     }
     if (drole) {
@@ -858,7 +882,7 @@ __device__ inline bool mid_linesearch4(const LView<M::n, M::m>& v, double* xsp, 
     for (int c = 0; c < kSpec; ++c) {
       if (!(e4[c] >= 1e-8)) return false;                                     // the search has run out of step sizes (:300)
       trials += 1;
-      const double ex = -e4[c] * (1.0 - e4[c] / 2.0) * dvs;                   // :326
+      const double ex = ls_expected<M>(lds, e4[c], dvs);                      // :326
       if ((L_last - L4[c]) > a.gamma * ex) { L_out = L4[c]; eps_out = e4[c]; win = c; return true; }
     }
     double e = e4[kSpec - 1];
@@ -869,7 +893,7 @@ __device__ inline bool mid_linesearch4(const LView<M::n, M::m>& v, double* xsp, 
         if (!(e >= 1e-8)) return false;
         trials += 1;
         const double Lq = __longlong_as_double((long long)__hip_atomic_load(Lh + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        const double ex = -e * (1.0 - e / 2.0) * dvs;
+        const double ex = ls_expected<M>(lds, e, dvs);
         if ((L_last - Lq) > a.gamma * ex) { L_out = Lq; eps_out = e; win = kSpec + q; return true; }
       }
     }
@@ -2621,10 +2645,355 @@ __device__ inline void large_backward_asym(const LView<M::n, M::m>& v, double* l
   }
 }
 
+// ---- Box control limits, mid-size family (Limited<M> kernels: mi_ilqr_set_control_limits) ---------------------------------------
+// Per step t, given Qx, Qu, Qxx, Quu, Qux (ilqr.py:651-656):  du* = argmin 1/2 du^T Quu du + Qu^T du  on  lo <= du <= hi
+// (lo = u_min - u_bar_t, hi = u_max - u_bar_t), kappa_t = -du*; the rows of K of the components the QP puts on a bound are 0, the
+// free rows Quu_ff^-1 Qux_f; dV = kappa^T Qu; the value update takes its general form (the reference's, :666-667, when nothing is
+// clamped).  The QP is projected Newton (Bertsekas 1982; the "boxQP" of Tassa, Mansard & Todorov 2014) on ONE wave, lane i holding
+// row i of Quu (m <= 16), matrices in LDS:
+//   x = clip(0, lo, hi); repeat (at most kBoxIters times):
+//     g = Quu x + Qu; clamped c_i = lo_i == hi_i or (x_i <= lo_i and g_i > 0) or (x_i >= hi_i and g_i < 0);
+//     stop if everything is clamped, or if the last step was a full Newton step and the clamped set has not changed (KKT holds);
+//     Newton point on the free set: x_f = -Quu_ff^-1 (Qu_f + Quu_fc x_c) (Cholesky of the free block);
+//     inside the box: take it; otherwise Armijo backtracking (0.1, step x 0.6) along the projected path clip(x + s (x_N - x));
+//   then one exact solve on the final free set.  tests/limited_ilqr_mid_np.py is the same algorithm in NumPy.
+// The clamped rows / columns of the factored matrix are the identity's, so the triangular solves need no index compression.
+constexpr int kBoxIters = 32, kBoxLs = 40;
+
+// Cholesky factor (lower, row stride WS) of Quu restricted to the free components (`freem`: bit i = component i free; the clamped
+// rows / columns are the identity's) in S.  One wave; lanes < m own a row.  Returns false (wave-uniform) if a pivot is not positive.
+template <int m, int WS>
+__device__ __forceinline__ bool box_chol(const double* W, double* S, unsigned long long freem, int lane) {
+  auto wave_fence = [&]() __attribute__((always_inline)) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+  };
+  const bool on = lane < m;
+  const bool fi = on && ((freem >> lane) & 1ull);
+  if (on) {
+    for (int j = 0; j <= lane; ++j) {
+      const bool fj = (freem >> j) & 1ull;
+      S[lane * WS + j] = (fi && fj) ? W[lane * WS + j] : (j == lane ? 1.0 : 0.0);
+    }
+  }
+  bool ok = true;
+#pragma unroll 1
+  for (int k = 0; k < m; ++k) {
+    wave_fence();
+    const double d = S[k * WS + k];
+    ok = ok && d > 0.0 && __builtin_isfinite(d);
+    const double piv = __builtin_sqrt(d);
+    wave_fence();
+    double l = 0.0;
+    if (on && lane == k) S[k * WS + k] = piv;
+    if (on && lane > k) { l = S[lane * WS + k] / piv; S[lane * WS + k] = l; }
+    wave_fence();
+    if (on && lane > k) { for (int j = k + 1; j <= lane; ++j) S[lane * WS + j] = fma(-l, S[j * WS + k], S[lane * WS + j]); }
+  }
+  wave_fence();
+  return ok;
+}
+
+// (S S^T) y = r in place (one thread): forward, then backward substitution.
+template <int m, int WS>
+__device__ __forceinline__ void box_solve(const double* S, double* r, int stride = 1) {
+  for (int i = 0; i < m; ++i) {
+    double s = r[i * stride];
+    for (int j = 0; j < i; ++j) s = fma(-S[i * WS + j], r[j * stride], s);
+    r[i * stride] = s / S[i * WS + i];
+  }
+  for (int i = m - 1; i >= 0; --i) {
+    double s = r[i * stride];
+    for (int j = i + 1; j < m; ++j) s = fma(-S[j * WS + i], r[j * stride], s);
+    r[i * stride] = s / S[i * WS + i];
+  }
+}
+
+// The box QP on one wave (see above).  W: Quu [m][WS]; qu, lo, hi: [m]; out: du [m], cl [m] (1.0 = clamped), S: the Cholesky
+// factor of the FINAL free block; rv: [16] scratch.  Returns false (wave-uniform) when Quu is not positive definite (du = 0 then).
+template <int m, int WS>
+__device__ inline bool box_qp_wave(const double* W, const double* qu, const double* lo, const double* hi, double* du, double* cl,
+                                   double* S, double* rv, int lane) {
+  auto wave_fence = [&]() __attribute__((always_inline)) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+  };
+  auto wsum = [&](double v_) __attribute__((always_inline)) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v_ += __shfl_xor(v_, o);
+    return v_;
+  };
+  constexpr unsigned long long kAll = (m == 64) ? ~0ull : ((1ull << m) - 1ull);
+  const bool on = lane < m;
+  const double lo_ = on ? lo[lane] : 0.0, hi_ = on ? hi[lane] : 0.0, q_ = on ? qu[lane] : 0.0;
+  // positive definite?  (the full Cholesky factor)
+  if (!box_chol<m, WS>(W, S, kAll, lane)) {
+    if (on) { du[lane] = 0.0; cl[lane] = 0.0; }
+    wave_fence();
+    return false;
+  }
+  double x = 0.0;                                            // start: clip(0, lo, hi)
+  x = x < lo_ ? lo_ : x;
+  x = x > hi_ ? hi_ : x;
+  if (on) du[lane] = x;
+  wave_fence();
+  // g_i = (Quu x)_i + Qu_i for the x in du[]
+  auto grad = [&]() __attribute__((always_inline)) {
+    double s = q_;
+    if (on) { for (int j = 0; j < m; ++j) s = fma(W[lane * WS + j], du[j], s); }
+    return s;
+  };
+  auto clamped = [&](double xv, double g) __attribute__((always_inline)) {
+    return on && (lo_ == hi_ || (xv <= lo_ && g > 0.0) || (xv >= hi_ && g < 0.0));
+  };
+  // Newton point on the free set (factor of the free block in S): rv = x_N
+  auto newton = [&](unsigned long long freem) __attribute__((always_inline)) {
+    const bool fi = on && ((freem >> lane) & 1ull);
+    double r = 0.0;
+    if (fi) {
+      r = -q_;
+      for (int j = 0; j < m; ++j) if (!((freem >> j) & 1ull)) r = fma(-W[lane * WS + j], du[j], r);
+    }
+    if (on) rv[lane] = r;
+    wave_fence();
+    if (lane == 0) box_solve<m, WS>(S, rv);
+    wave_fence();
+    return fi ? rv[lane] : x;
+  };
+  unsigned long long prevC = ~0ull;
+  bool full = false;
+#pragma unroll 1
+  for (int it = 0; it < kBoxIters; ++it) {
+    const double g = grad();
+    const unsigned long long C = __ballot(clamped(x, g)) & kAll;
+    if ((full && C == prevC) || C == kAll) break;
+    const unsigned long long F = kAll & ~C;
+    box_chol<m, WS>(W, S, F, lane);                          // (a principal block of a positive definite matrix)
+    const double xn = newton(F);
+    const bool inside = !on || (!(xn < lo_) && !(xn > hi_));
+    prevC = C;
+    if (__ballot(!inside) == 0ull) {                         // a full Newton step
+      x = xn;
+      if (on) du[lane] = x;
+      wave_fence();
+      full = true;
+      continue;
+    }
+    full = false;
+    const double dir = xn - x;
+    const double f0 = wsum(on ? x * (0.5 * (g - q_) + q_) : 0.0);
+    const double gd = wsum(on ? g * dir : 0.0);
+    double step = 1.0, xt = x;
+    bool found = false;
+#pragma unroll 1
+    for (int ls = 0; ls < kBoxLs; ++ls) {
+      xt = fma(step, dir, x);
+      xt = xt < lo_ ? lo_ : xt;
+      xt = xt > hi_ ? hi_ : xt;
+      wave_fence();
+      if (on) du[lane] = xt;
+      wave_fence();
+      const double gt = grad();
+      const double ft = wsum(on ? xt * (0.5 * (gt - q_) + q_) : 0.0);
+      if (ft - f0 <= 0.1 * step * gd) { found = true; break; }
+      step *= 0.6;
+    }
+    wave_fence();
+    if (!found) { if (on) du[lane] = x; wave_fence(); break; }
+    x = xt;
+  }
+  // one exact solve on the final free set
+  const double g = grad();
+  const bool c = clamped(x, g);
+  const unsigned long long C = __ballot(c) & kAll;
+  box_chol<m, WS>(W, S, kAll & ~C, lane);
+  const double xf = newton(kAll & ~C);
+  if (on) { du[lane] = xf; cl[lane] = c ? 1.0 : 0.0; }
+  wave_fence();
+  return true;
+}
+
+// The limited backward pass of the mid-size family: the recursion in plain fp64 multiply-adds out of LDS (large_backward_asym's
+// form, cut to the mid-size layout's areas), the box QP on wave 0, K_f by triangular solves against the free block's factor, one
+// thread per column of Qux.  Seven barriers per step.  Leaves S2 in the reduction scratch (kS2Slot) and "a Quu was not positive
+// definite" in kPdFlag.
+template <class M>
+__device__ inline void mid_backward_limited(const LView<M::n, M::m>& v, double* lds) {
+  constexpr int n = M::n, m = M::m, nm = n + m;
+  using Ly = LLay<n, m>;
+  static_assert(Ly::kMid && m >= 1 && m <= 16, "mid-size family: n <= 32, m <= 16");
+  constexpr int WS = 17;
+  const int tid = stage_tid(), N = v.N, lane = tid & 63, wave = tid >> 6;
+  const double* Q = lds + Ly::oQ;
+  const double* R = lds + Ly::oR;
+  const double* Qf = lds + Ly::oQf;
+  const double* qn = lds + Ly::oQn;
+  const double* qfn = lds + Ly::oQfn;
+  const double* ulim = lds + Ly::oRed + kLimSlot;            // u_min [m] | u_max [m]
+  double* Vxx = lds + Ly::oVxx;      // [n][n] dense
+  double* Vx = lds + Ly::oVx;        // [n]
+  double* Fb = lds + Ly::oF;         // [n][nm] = [fx_t | fu_t]
+  double* A = lds + Ly::oT1;         // [nm][n] = F^T Vxx; after the products: K_t [m][n], Quu K_t [m][n]
+  double* Kt = A;
+  double* QK = A + m * n;
+  double* Hb = lds + Ly::oH;         // [nm][n]: rows < n  fx^T Vxx fx, rows >= n  Qux
+  double* Gr = Hb + nm * n;          // [nm] lx_t | lu_t
+  double* q1 = Gr + nm;              // [nm] Qx | Qu
+  double* du = q1 + nm;              // [16] du*
+  double* cl = du + 16;              // [16] 1.0: component clamped
+  double* Qk = cl + 16;              // [16] Quu kappa
+  double* lo = Qk + 16;              // [16] u_min - u_bar_t
+  double* hi = lo + 16;              // [16] u_max - u_bar_t
+  double* rv = hi + 16;              // [16] solve scratch
+  double* S = rv + 16;               // [16][WS] Cholesky factor of the free block
+  double* W = lds + Ly::oS;          // [m][WS] Quu
+  static_assert(n * n <= Ly::NP * Ly::VS && n * nm <= Ly::NK * Ly::NMP && nm * n <= Ly::NK * Ly::TS && 2 * m * n <= Ly::NK * Ly::TS,
+                "dense operands inside the matrix-core layout's areas");
+  static_assert(nm * n + 2 * nm + 6 * 16 + 16 * WS <= Ly::NMP * Ly::TS && m * WS <= 16 * 17 + 1, "scratch inside the H area, Quu in the tile scratch");
+  static_assert(kLimSlot + 2 * m <= kLargeThreads && kS2Slot < kLimSlot && kS2Slot != kPdFlag && kS2Slot > 3, "slots of the reduction scratch");
+  // terminal: Vx = 2 Qf x_T - 2 x_nom^T Qf ; Vxx = 2 Qf   (ilqr.py:203-204, :638)
+  __syncthreads();
+  if (tid == 0) lds[Ly::oRed + kPdFlag] = 0.0;
+  for (int e = tid; e < n * n; e += kLargeThreads) Vxx[e] = 2.0 * Qf[e];
+  if (tid < n) {
+    const double* xT = v.X + (size_t)(N - 1) * n;
+    double s_ = 0.0;
+    for (int j = 0; j < n; ++j) s_ += (2.0 * Qf[tid * n + j]) * xT[j];
+    Vx[tid] = s_ - qfn[tid];
+  }
+  double s2 = 0.0;                                           // (thread 0)
+  bool bad = false;                                          // (wave 0)
+  __syncthreads();
+#pragma unroll 1
+  for (int t = N - 2; t >= 0; --t) {
+    // ---- F_t, the cost gradients (:180-181), the box of du
+    {
+      const double* fxg = v.Fx + (size_t)t * n * n;
+      const double* fug = v.Fu + (size_t)t * n * m;
+      for (int e = tid; e < n * nm; e += kLargeThreads) {
+        const int i = e / nm, j = e - i * nm;
+        Fb[e] = j < n ? fxg[i * n + j] : fug[i * m + (j - n)];
+      }
+      if (tid < n) {
+        const double* xg = v.X + (size_t)t * n;
+        double s_ = -qn[tid];
+        for (int j = 0; j < n; ++j) s_ += (2.0 * Q[tid * n + j]) * xg[j];
+        Gr[tid] = s_;
+      } else if (tid < nm) {
+        const double* ug = v.U + (size_t)t * m;
+        double s_ = 0.0;
+        for (int j = 0; j < m; ++j) s_ += (2.0 * R[(tid - n) * m + j]) * ug[j];
+        Gr[tid] = s_;
+      } else if (tid >= 64 && tid < 64 + m) {
+        const int k = tid - 64;
+        const double ub = v.U[(size_t)t * m + k];
+        lo[k] = ulim[k] - ub;
+        hi[k] = ulim[m + k] - ub;
+      }
+    }
+    __syncthreads();
+    // ---- A = F^T Vxx ; Qx | Qu = l + F^T Vx (:651-652)
+    for (int e = tid; e < nm * n; e += kLargeThreads) {
+      const int r = e / n, j = e - r * n;
+      double s_ = 0.0;
+      for (int i = 0; i < n; ++i) s_ = fma(Fb[i * nm + r], Vxx[i * n + j], s_);
+      A[e] = s_;
+    }
+    if (tid >= 192 && tid - 192 < nm) {
+      const int r = tid - 192;
+      double s_ = Gr[r];
+      for (int i = 0; i < n; ++i) s_ = fma(Fb[i * nm + r], Vx[i], s_);
+      q1[r] = s_;
+    }
+    __syncthreads();
+    // ---- [Qxx - lxx ; Qux] = A fx ; Quu = luu + A_u fu (:653-656)
+    for (int e = tid; e < nm * n; e += kLargeThreads) {
+      const int r = e / n, j = e - r * n;
+      double s_ = 0.0;
+      for (int k = 0; k < n; ++k) s_ = fma(A[r * n + k], Fb[k * nm + j], s_);
+      Hb[e] = s_;
+    }
+    for (int e = tid; e < m * m; e += kLargeThreads) {
+      const int a_ = e / m, b_ = e - a_ * m;
+      double s_ = 0.0;
+      for (int k = 0; k < n; ++k) s_ = fma(A[(n + a_) * n + k], Fb[k * nm + n + b_], s_);
+      W[a_ * WS + b_] = 2.0 * R[a_ * m + b_] + s_;
+    }
+    __syncthreads();
+    // ---- the box QP (wave 0)
+    if (wave == 0) bad = !box_qp_wave<m, WS>(W, q1 + n, lo, hi, du, cl, S, rv, lane) || bad;
+    __syncthreads();
+    // ---- kappa = -du*, K: clamped rows 0, free rows Quu_ff^-1 Qux_f (thread j: column j); Quu kappa (wave 1)
+    if (tid < n) {
+      const int j = tid;
+      double* col = Kt + j;                                  // column j of K_t, stride n
+      for (int a_ = 0; a_ < m; ++a_) col[a_ * n] = cl[a_] != 0.0 ? 0.0 : Hb[(n + a_) * n + j];
+      box_solve<m, WS>(S, col, n);
+      double* Kg = v.K + (size_t)t * m * n;
+      for (int a_ = 0; a_ < m; ++a_) Kg[a_ * n + j] = col[a_ * n];
+    } else if (tid >= 64 && tid < 64 + m) {
+      const int a_ = tid - 64;
+      double s_ = 0.0;
+      for (int b_ = 0; b_ < m; ++b_) s_ = fma(W[a_ * WS + b_], -du[b_], s_);
+      Qk[a_] = s_;
+      v.kap[(size_t)t * m + a_] = -du[a_];
+    }
+    __syncthreads();
+    // ---- dV = kappa^T Qu, S2 += kappa^T Quu kappa; Vx' (:666, general form); Quu K
+    bool any = false;
+    for (int a_ = 0; a_ < m; ++a_) any = any || cl[a_] != 0.0;
+    if (tid == 0) {
+      double dv = 0.0, kq = 0.0;
+      for (int a_ = 0; a_ < m; ++a_) { dv = fma(-du[a_], q1[n + a_], dv); kq = fma(-du[a_], Qk[a_], kq); }
+      v.dV[t] = dv;
+      s2 += kq;
+    }
+    if (tid >= 64 && tid - 64 < n) {
+      const int j = tid - 64;
+      double s_ = q1[j];
+      if (!any) {
+        for (int a_ = 0; a_ < m; ++a_) s_ = fma(Hb[(n + a_) * n + j], du[a_], s_);                  // Qx - Qux^T kappa
+      } else {
+        for (int a_ = 0; a_ < m; ++a_)
+          s_ += (-Kt[a_ * n + j] * q1[n + a_] + Hb[(n + a_) * n + j] * du[a_]) + Kt[a_ * n + j] * Qk[a_];
+      }
+      Vx[j] = s_;
+    }
+    if (any) {
+      for (int e = tid; e < m * n; e += kLargeThreads) {
+        const int a_ = e / n, j = e - a_ * n;
+        double s_ = 0.0;
+        for (int b_ = 0; b_ < m; ++b_) s_ = fma(W[a_ * WS + b_], Kt[b_ * n + j], s_);
+        QK[e] = s_;
+      }
+    }
+    __syncthreads();
+    // ---- Vxx' = Qxx - Qux^T K (nothing clamped, :667), else Qxx - K^T Qux - Qux^T K + K^T Quu K
+    for (int e = tid; e < n * n; e += kLargeThreads) {
+      const int i = e / n, j = e - i * n;
+      double s_ = 0.0;
+      if (!any) {
+        for (int a_ = 0; a_ < m; ++a_) s_ = fma(Hb[(n + a_) * n + i], Kt[a_ * n + j], s_);
+      } else {
+        for (int a_ = 0; a_ < m; ++a_)
+          s_ += (Kt[a_ * n + i] * Hb[(n + a_) * n + j] + Hb[(n + a_) * n + i] * Kt[a_ * n + j]) - Kt[a_ * n + i] * QK[a_ * n + j];
+      }
+      Vxx[e] = (2.0 * Q[e] + Hb[e]) - s_;
+    }
+    __syncthreads();
+  }
+  if (wave == 0 && lane == 0 && bad) lds[Ly::oRed + kPdFlag] = 1.0;
+  if (tid == 0) lds[Ly::oRed + kS2Slot] = s2;
+  __syncthreads();
+}
+
 // The backward pass of a model's size class.
 template <class M, bool PIV>
 __device__ __forceinline__ void backward_pass(const LView<M::n, M::m>& v, double* lds, long long* bp_acc, bool lx_ready, bool xu_staged = false) {
-  if constexpr (LLay<M::n, M::m>::kMid) mid_backward<M, PIV>(v, lds, lx_ready, xu_staged);
+  if constexpr (UsesLimits<M>::value) mid_backward_limited<M>(v, lds);             // (control limits: the box-QP pass)
+  else if constexpr (LLay<M::n, M::m>::kMid) mid_backward<M, PIV>(v, lds, lx_ready, xu_staged);
   else {
     if constexpr (PIV) {
       if (v.asym) { large_backward_asym<M>(v, lds); return; }   // (cost matrices that are not symmetric: launched as the PIV form, launch_large.hpp)
@@ -2705,6 +3074,11 @@ __global__ void __launch_bounds__(kLargeThreads, kMinBlocks<M>) ilqr_large_kerne
       }
       lds[Ly::oQn + tid] = s; lds[Ly::oQfn + tid] = sf;
     }
+  }
+  if constexpr (UsesLimits<M>::value) {                     // this problem's bounds and the S2 of its last backward pass
+    static_assert(Ly::kMid, "control limits: the mid-size family only");
+    if (tid < 2 * m) lds[Ly::oRed + kLimSlot + tid] = a.ulim[(size_t)b * 2 * m + tid];
+    if (tid == 0) lds[Ly::oRed + kS2Slot] = a.cold ? 0.0 : a.s2[b];
   }
   // lazily-zero persistent state / pending initial guess (the cluster's leader only: helpers never write solver state)
   if (a.cold && role == 0) {
@@ -3044,7 +3418,8 @@ __global__ void __launch_bounds__(kLargeThreads, kMinBlocks<M>) ilqr_large_kerne
   if (MODE == MODE_BACKWARD) {
     backward_pass<M, PIV>(v, lds, nullptr, false);
     __syncthreads();
-    if (tid == 0) a.status[b] = lds[Ly::oRed + kPdFlag] == 0.0 ? MI_STATUS_CONVERGED : (a.pd_continue ? MI_STATUS_FLAG_INDEFINITE : MI_STATUS_NOT_PD);
+    if (tid == 0) a.status[b] = lds[Ly::oRed + kPdFlag] == 0.0 ? MI_STATUS_CONVERGED : ((a.pd_continue && !UsesLimits<M>::value) ? MI_STATUS_FLAG_INDEFINITE : MI_STATUS_NOT_PD);
+    if constexpr (UsesLimits<M>::value) { if (tid == 0) a.s2[b] = lds[Ly::oRed + kS2Slot]; }
     return;
   }
 
@@ -3192,7 +3567,7 @@ __global__ void __launch_bounds__(kLargeThreads, kMinBlocks<M>) ilqr_large_kerne
       L = L_new;
       it_this += 1;
       if (MODE == MODE_FORWARD) break;
-      if (not_pd && !a.pd_continue) { status = MI_STATUS_NOT_PD; break; }      // the gains of that pass are not to be used (unless asked to: on_indefinite)
+      if (not_pd && (!a.pd_continue || UsesLimits<M>::value)) { status = MI_STATUS_NOT_PD; break; }   // the gains of that pass are not to be used (unless asked to: on_indefinite; never with limits: no box-QP minimiser)
       met_indefinite = met_indefinite || not_pd;
     }
     iters += it_this;
@@ -3208,6 +3583,9 @@ __global__ void __launch_bounds__(kLargeThreads, kMinBlocks<M>) ilqr_large_kerne
   // helpers: go home (any non-zero value; the rest of the word is for MI_I64_CLUSTER_WORDS: rounds << 32 | same-L2 rounds << 8 | 1)
   if (G > 1 && tid == 0) __hip_atomic_store(csync + 3, ((unsigned long long)(unsigned)cst[0] << 32) | ((unsigned long long)((unsigned)cst[1] & 0xffffffu) << 8) | 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   for (int i = tid; i < nk; i += kLargeThreads) a.kp_list[(size_t)b * (N - 1) + i] = acc.kp[i];
+  if constexpr (UsesLimits<M>::value) {
+    if (MODE != MODE_FORWARD && tid == 0) a.s2[b] = lds[Ly::oRed + kS2Slot];
+  }
   if (tid == 0) {
     a.cost[b] = L; a.iters[b] = iters; a.status[b] = status | (met_indefinite ? MI_STATUS_FLAG_INDEFINITE : 0); a.ls_trials[b] = ls_total; a.kp_count[b] = nk;
 #ifndef MI_PROF_BACKWARD

@@ -1,0 +1,5 @@
+// Workgroup-per-problem kernels of the Arm27C model with control limits (Limited<Arm27C>: the mid-size family's box-QP backward pass and
+// clamped rollouts): every (Jacobian mode, kernel mode) instantiation.
+#include "launch_large.hpp"
+
+MI_INTERNAL int launch_arm27c_lim(mi_ilqr* h, int mode, const mi::KArgs& a) { return mi_host::launch_jac_large_limited<mi::Arm27C>(h, mode, a); }

@@ -70,4 +70,28 @@ int launch_jac_large(mi_ilqr* h, int mode, const KArgs& a) {
   return launch_mode_large<M, MI_JAC_FD_CENTRAL>(h, mode, a);
 }
 
+// Handles with control limits (mi_ilqr_set_control_limits; the mid-size family, n <= 32): the Limited<M> kernels - the clamped
+// rollouts and the box-QP backward pass (mid_backward_limited) - for every mode.  The backward pass has no pivoted-inverse path, so
+// there is one form (PIV = false).  Instantiated apart from launch_jac_large (k_<model>_lim.hip, the plugin units built with limits).
+template <class M, int JAC>
+int launch_mode_large_limited(mi_ilqr* h, int mode, const KArgs& a) {
+  static_assert(LLay<M::n, M::m>::kMid, "control limits: the mid-size family only");
+  switch (mode) {
+    case MODE_SOLVE: return launch_one_large<Limited<M>, JAC, MODE_SOLVE>(h, a);
+    case MODE_BACKWARD: return launch_one_large<Limited<M>, JAC, MODE_BACKWARD>(h, a);
+    case MODE_MPC: return launch_one_large<Limited<M>, JAC, MODE_MPC>(h, a);
+    case MODE_ROLLOUT: return launch_one_large<Limited<M>, JAC, MODE_ROLLOUT>(h, a);
+    case MODE_FORWARD: return launch_one_large<Limited<M>, JAC, MODE_FORWARD>(h, a);
+    case MODE_LINEARIZE: return launch_one_large<Limited<M>, JAC, MODE_LINEARIZE>(h, a);
+    default: break;
+  }
+  return MI_ILQR_E_BAD_ARG;
+}
+
+template <class M>
+int launch_jac_large_limited(mi_ilqr* h, int mode, const KArgs& a) {
+  if (h->d.jacobian_mode == MI_JAC_AUTODIFF) return launch_mode_large_limited<M, MI_JAC_AUTODIFF>(h, mode, a);
+  return launch_mode_large_limited<M, MI_JAC_FD_CENTRAL>(h, mode, a);
+}
+
 }  // namespace mi_host

@@ -157,7 +157,8 @@ KArgs make_args(const mi_ilqr* h) {
   a.spec_policy = (h->x_spec && spec >= 0 && spec <= 2) ? spec : 0;
   a.cluster = 1;
   a.cluster_sync = h->cluster_sync;
-  if (h->large && h->cluster_sync && h->d.keypoint_method == MI_KP_SET_INTERVAL && h->d.minN == 1) {
+  // (limited handles: one workgroup per problem - no clusters, hence no early linearization or candidate groups either)
+  if (h->large && h->cluster_sync && !h->limited && h->d.keypoint_method == MI_KP_SET_INTERVAL && h->d.minN == 1) {
     static const int forced = [] { const char* e = std::getenv("MI_ILQR_CLUSTER"); return e ? std::atoi(e) : 0; }();
     int g = forced > 0 ? forced : (h->n_cus > 0 ? h->n_cus / h->B : 1);
     // Which models: those whose linearization is worth a handshake (round 5: ~20 k cycles - six memory round trips - since the
@@ -230,6 +231,8 @@ int launch(mi_ilqr* h, int mode) {
       case MI_MODEL_ACROBOT: return launch_acrobot_lim(h, mode, a);
       case MI_MODEL_CARTPOLE: return launch_cartpole_lim(h, mode, a);
       case MI_MODEL_CARTPOLE_WALL: return launch_cartpole_wall_lim(h, mode, a);
+      case MI_MODEL_ARM27: return launch_arm27_lim(h, mode, a);
+      case MI_MODEL_ARM27C: return launch_arm27c_lim(h, mode, a);
       default: break;
     }
   }
@@ -1082,9 +1085,21 @@ int mi_ilqr_reset(mi_ilqr_t* h) {
   return MI_ILQR_OK;
 }
 
+// Whether a workgroup-per-problem handle has Limited<M> kernels: the mid-size layout (n <= 32), and for a plugin, kernels it was built
+// with (asked through its launch entry, which launches nothing for the probe).
+static bool large_accepts_limits(mi_ilqr* h) {
+  if (h->n > 32) return false;
+  if (h->d.model_id == MI_MODEL_ARM27 || h->d.model_id == MI_MODEL_ARM27C) return true;
+  const PluginSlot* ps = plugin_of(h->d.model_id);
+  if (!ps) return false;
+  const KArgs a = make_args(h);
+  return ps->p.launch(h, kModeProbeLimits, &a) == MI_ILQR_OK;
+}
+
 int mi_ilqr_set_control_limits(mi_ilqr_t* h, const double* u_min, const double* u_max, int32_t per_problem) {
   if (!h) return MI_ILQR_E_BAD_ARG;
-  if (h->large) return MI_ILQR_E_UNSUPPORTED;      // workgroup-per-problem kernels: no box-QP backward pass (yet)
+  // workgroup-per-problem kernels: the mid-size family (n <= 32) only - the built-in arms, family-1 plugins built with limits
+  if (h->large && !large_accepts_limits(h)) return MI_ILQR_E_UNSUPPORTED;
   if (!u_min && !u_max) { h->limited = false; return MI_ILQR_OK; }   // the regular kernels again, state untouched
   if (!u_min || !u_max) return MI_ILQR_E_BAD_ARG;
   const int m = h->m, B = h->B;

@@ -99,16 +99,17 @@ class BatchedIterativeLQR:
         _capi.check(self._lib.mi_ilqr_create(C.byref(d), C.byref(h)), "mi_ilqr_create")
         self._h = h
         # control_limits: "ignore" (default) keeps the reference's SetControlLimits, a no-op (ilqr.py:158-159); "enforce" makes it
-        # bound the controls (include/mi_ilqr.h: mi_ilqr_set_control_limits) - the m <= 2 kernel families only
+        # bound the controls (include/mi_ilqr.h: mi_ilqr_set_control_limits) - the m <= 2 kernel families and the mid-size family (n <= 32)
         if control_limits not in ("ignore", "enforce"):
             raise ValueError(f'control_limits must be "ignore" or "enforce", got {control_limits!r}')
         self.control_limits = control_limits
         if control_limits == "enforce":
             rc = self._lib.mi_ilqr_set_control_limits(h, None, None, 0)
             if rc == _capi.E_UNSUPPORTED:
-                raise ValueError("control_limits='enforce' is served by the m <= 2 kernel families only (wave-per-problem "
-                                 "LATENCY and lane-per-problem THROUGHPUT kernels: the built-in pendulum, acrobot, cart-pole "
-                                 "models and family-0 plugins); this model runs on the workgroup-per-problem kernels")
+                raise ValueError("control_limits='enforce' is served by the m <= 2 kernel families and the mid-size workgroup "
+                                 "family (n <= 32) only: the built-in pendulum, acrobot, cart-pole and arm models, family-0 "
+                                 "plugins and family-1 plugins with n <= 32 built with control_limits=True; this model runs on "
+                                 "other workgroup-per-problem kernels")
             _capi.check(rc, "mi_ilqr_set_control_limits")
         # pinned_results (the default): the arrays the state attributes / Solve() return are views of page-locked buffers
         # (direct DMA, no page faults of freshly allocated arrays; the wave-per-problem kernels write x_bar / u_bar / cost

@@ -283,7 +283,9 @@ int mi_ilqr_reset(mi_ilqr_t* h);
  *            clamped) and a trial's expected improvement is -(eps sum dV - eps^2/2 sum_t kappa_t^T Quu_t kappa_t);
  *            a Quu that is not positive definite stops the problem with MI_STATUS_NOT_PD (counted in stats.n_not_pd).
  * Limited handles take sequential rollouts and backward passes (the time-parallel forms carry no active set).  Wave- and
- * lane-per-problem kernels (m <= 2); on a workgroup-per-problem handle MI_ILQR_E_UNSUPPORTED, the handle stays usable. */
+ * lane-per-problem kernels (m <= 2) and the mid-size workgroup family (n <= 32, m <= 16: MI_MODEL_ARM27, MI_MODEL_ARM27C, family-1
+ * plugins built with limits; there the box QP is projected Newton and the free rows of K come from a Cholesky factor of Quu_ff);
+ * on any other workgroup-per-problem handle (n > 32, or a plugin built without them) MI_ILQR_E_UNSUPPORTED, the handle stays usable. */
 int mi_ilqr_set_control_limits(mi_ilqr_t* h, const double* u_min, const double* u_max, int32_t per_problem);
 
 /* Benchmark/MPC helper: make the resident u_guess (last mi_ilqr_set_initial or
