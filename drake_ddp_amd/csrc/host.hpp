@@ -92,6 +92,12 @@ struct mi_ilqr {
   bool limited = false;
   double* ulim = nullptr;          // (B, 2, m): u_min | u_max per problem (allocated on first use, kept when cleared)
   double* s2 = nullptr;            // (B,): S2 of each problem's last limited backward pass (KArgs::s2)
+  // per-problem targets (mi_ilqr_set MI_F_X_NOM / MI_F_TARGET_STEP): `per_problem_targets` hands the kernels x_nom_rows /
+  // target_steps; the host mirrors are what mi_ilqr_get returns (mi_ilqr_mpc_run advances both copies)
+  bool per_problem_targets = false;
+  bool target_steps_moving = false;   // a row of the steps is non-zero (cluster helpers' candidate groups need a still target)
+  double *x_nom_rows = nullptr, *target_steps = nullptr;   // (B, n) each, allocated on first use, kept when dropped
+  std::vector<double> h_x_nom_rows, h_target_steps;
 };
 
 // Small batches of the wave-per-problem kernels aggregate the batch statistics in the solve kernel

@@ -35,7 +35,7 @@ namespace mi {
 // batch-minor addressing helpers: element (t, r) of an array with `rows` rows per time step
 __device__ __forceinline__ size_t bm(int t, int r, int rows, int B) { return ((size_t)t * rows + r) * B; }
 
-template <class M, int JAC, bool KP = false>
+template <class M, int JAC, bool KP = false, bool PT = false>
 __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
   constexpr int n = M::n, m = M::m, nc = n + m;
   const int b = blockIdx.x * 64 + threadIdx.x;
@@ -56,7 +56,10 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
   double* sink = a.trial_cost + 2 * (size_t)bb;
 
   Consts<M> c;
-  c.load(a.costmat);
+  // PT: per-problem targets (KArgs::x_nom_rows) - x_nom, 2 x_nom^T Q and 2 x_nom^T Qf become per-lane values.  Its own
+  // instantiation: in the regular kernel they are batch-uniform (scalar registers) and stay so.
+  if constexpr (PT) c.load(a.costmat, a.x_nom_rows + (size_t)bb * n);
+  else c.load(a.costmat);
   double x0r[n];
 #pragma unroll
   for (int i = 0; i < n; ++i) x0r[i] = a.x0[(size_t)bb * n + i];

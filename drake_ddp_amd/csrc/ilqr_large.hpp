@@ -3064,7 +3064,7 @@ __global__ void __launch_bounds__(kLargeThreads, kMinBlocks<M>) ilqr_large_kerne
     const double* cm = a.costmat;
     for (int e = tid; e < n * n; e += kLargeThreads) { lds[Ly::oQ + e] = cm[e]; lds[Ly::oQf + e] = cm[n * n + m * m + e]; }
     for (int e = tid; e < m * m; e += kLargeThreads) lds[Ly::oR + e] = cm[n * n + e];
-    if (tid < n) lds[Ly::oXnom + tid] = cm[2 * n * n + m * m + tid];
+    if (tid < n) lds[Ly::oXnom + tid] = x_nom_of<n, m>(a, b)[tid];   // (a helper: the problem it serves)
     __syncthreads();
     if (tid < n) {
       double s = 0.0, sf = 0.0;
@@ -3462,7 +3462,7 @@ __global__ void __launch_bounds__(kLargeThreads, kMinBlocks<M>) ilqr_large_kerne
       if (tid < n) {
         x0w[tid] = x0n;
         // moving target (mini_cheetah.py:151-156) and the constants derived from it (ilqr.py:180,203)
-        lds[Ly::oXnom + tid] += a.mpc_target_step[tid];
+        lds[Ly::oXnom + tid] += target_step_of<n>(a, b, tid);
       }
       __syncthreads();
       if (tid < n) {

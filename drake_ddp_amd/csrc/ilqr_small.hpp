@@ -108,7 +108,23 @@ struct KArgs {
   // and S2 = sum_t kappa_t^T Quu_t kappa_t of each problem's last backward pass, (B,), the quadratic term of the expected improvement
   const double* ulim;
   double* s2;
+  // per-problem targets (mi_ilqr_set MI_F_X_NOM / MI_F_TARGET_STEP), (B, n) each: x_nom of problem b is row b of x_nom_rows instead
+  // of the costmat's shared one, and MODE_MPC adds row b of target_steps (instead of mpc_target_step) before every re-solve.
+  // Null: the shared target.
+  const double* x_nom_rows;
+  const double* target_steps;
 };
+
+// Where problem b's target lives: row b of the per-problem targets, else the shared one in the costmat (Q | R | Qf | x_nom).
+template <int n, int m>
+__device__ __forceinline__ const double* x_nom_of(const KArgs& a, size_t b) {
+  return a.x_nom_rows ? a.x_nom_rows + b * n : a.costmat + 2 * n * n + m * m;
+}
+// Problem b's per-re-solve step of the MPC target, component i.
+template <int n>
+__device__ __forceinline__ double target_step_of(const KArgs& a, size_t b, int i) {
+  return a.target_steps ? a.target_steps[b * n + i] : a.mpc_target_step[i];
+}
 
 // threadIdx.x behind an empty asm, for the STAGES of a solve kernel (a rollout, a linearization, a backward pass): what a stage
 // derives from its lane index is loop-invariant for the solve loop around the stages, the compiler hoists it out of that loop,
@@ -298,7 +314,9 @@ struct Consts : LimitRegs<M> {
   double Q[n][n], R[m][m], Qf[n][n], xnom[n];
   double qn[n];    // 2*x_nom^T Q    (ilqr.py:180)
   double qfn[n];   // 2*x_nom^T Qf   (ilqr.py:203)
-  __device__ inline void load(const double* cm) {
+  __device__ inline void load(const double* cm) { load(cm, cm + 2 * n * n + m * m); }
+  // xn: this problem's target (x_nom_of); qn / qfn come from the same loop whichever array it is
+  __device__ inline void load(const double* cm, const double* xn) {
 #pragma unroll
     for (int i = 0; i < n; ++i)
 #pragma unroll
@@ -308,7 +326,7 @@ struct Consts : LimitRegs<M> {
 #pragma unroll
       for (int j = 0; j < m; ++j) R[i][j] = cm[n * n + i * m + j];
 #pragma unroll
-    for (int i = 0; i < n; ++i) xnom[i] = cm[2 * n * n + m * m + i];
+    for (int i = 0; i < n; ++i) xnom[i] = xn[i];
 #pragma unroll
     for (int j = 0; j < n; ++j) {
       double s = 0.0, sf = 0.0;
@@ -2517,7 +2535,7 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
     // the control sequence - and consumed after the LDS arrays have been initialized: one memory
     // latency instead of one per array (a cold solve reads nothing else).  (n = 2 only: in the
     // larger kernels the extra live registers cost more in the line-search loops than this saves.)
-    c.load(a.costmat);
+    c.load(a.costmat, x_nom_of<n, m>(a, b));
 #pragma unroll
     for (int i = 0; i < n; ++i) x0r[i] = a.x0[(size_t)b * n + i];
     constexpr int UPQ = 4;
@@ -2566,7 +2584,7 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
     stage_in(w.G, Ly::GS, Ly::DV, a.dV + oT, 1, N - 1, cold);
     stage_in(w.J, Ly::JS, Ly::FX, a.fx + oFx, n * n, N - 1, cold);
     stage_in(w.J, Ly::JS, Ly::FU, a.fu + oFu, n * m, N - 1, cold);
-    c.load(a.costmat);
+    c.load(a.costmat, x_nom_of<n, m>(a, b));
 #pragma unroll
     for (int i = 0; i < n; ++i) x0r[i] = a.x0[(size_t)b * n + i];
     if constexpr (UsesScanBackward<M>::value) c.to_lds(w.cst);
@@ -2646,7 +2664,7 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
       }
       // moving target (mini_cheetah.py:151-156) and the constants derived from it (ilqr.py:180,203)
 #pragma unroll
-      for (int i = 0; i < n; ++i) c.xnom[i] += a.mpc_target_step[i];
+      for (int i = 0; i < n; ++i) c.xnom[i] += target_step_of<n>(a, b, i);
 #pragma unroll
       for (int j = 0; j < n; ++j) {
         double s_ = 0.0, sf_ = 0.0;

@@ -5,14 +5,21 @@
 #include "ilqr_batch.hpp"
 
 namespace mi_host {
-template <class M, int JAC>
-int launch_batch_one(mi_ilqr* h, const KArgs& a) {
+template <class M, int JAC, bool PT>
+int launch_batch_kp(mi_ilqr* h, const KArgs& a) {
   if (a.bm_scratch != nullptr) {                          // key-point configurations other than setInterval / 1
-    auto kern = ilqr_batch_kernel<M, JAC, true>;
+    auto kern = ilqr_batch_kernel<M, JAC, true, PT>;
     return launch_timed(h, kern, dim3((h->B + 63) / 64), dim3(64), 0, a);
   }
-  auto kern = ilqr_batch_kernel<M, JAC, false>;
+  auto kern = ilqr_batch_kernel<M, JAC, false, PT>;
   return launch_timed(h, kern, dim3((h->B + 63) / 64), dim3(64), 0, a);
+}
+
+// per-problem targets (KArgs::x_nom_rows) take instantiations of their own: the regular kernels' code does not change
+template <class M, int JAC>
+int launch_batch_one(mi_ilqr* h, const KArgs& a) {
+  if (a.x_nom_rows != nullptr) return launch_batch_kp<M, JAC, true>(h, a);
+  return launch_batch_kp<M, JAC, false>(h, a);
 }
 
 template <class M>

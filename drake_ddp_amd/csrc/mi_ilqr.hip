@@ -153,6 +153,8 @@ KArgs make_args(const mi_ilqr* h) {
   a.q_diag = h->q_diag ? 1 : 0;
   a.ulim = h->limited ? h->ulim : nullptr;
   a.s2 = h->s2;
+  a.x_nom_rows = h->per_problem_targets ? h->x_nom_rows : nullptr;
+  a.target_steps = h->per_problem_targets ? h->target_steps : nullptr;
   static const int spec = [] { const char* e = std::getenv("MI_ILQR_SPEC"); return e ? std::atoi(e) : 1; }();
   a.spec_policy = (h->x_spec && spec >= 0 && spec <= 2) ? spec : 0;
   a.cluster = 1;
@@ -203,6 +205,7 @@ KArgs make_args(const mi_ilqr* h) {
     static const int groups = [] { const char* e = std::getenv("MI_ILQR_LS_GROUPS"); return e ? std::atoi(e) : 1; }();
     bool still = true;
     for (int i = 0; i < h->n; ++i) still = still && h->mpc_target_step[i] == 0.0;
+    if (h->per_problem_targets && h->target_steps_moving) still = false;
     const bool lsg = groups && still && h->spec_slots >= 4 * g - 1 && g > 1;
     a.cluster = g | ((order & 3) << 8) | ((early ? 1 : 0) << 10) | ((lsg ? 1 : 0) << 11);
   }
@@ -827,7 +830,7 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
   void* ptrs[] = {h->x_bar, h->u_bar, h->K, h->kappa, h->dV, h->fx, h->fu, h->x0, h->u_guess, h->cost_ring, h->hist, h->iter_cyc,
                   h->x_trial, h->u_trial, h->trial_cost, h->stage_in, h->costmat, h->iters_ring, h->status_ring, h->ls_ring,
                   h->kp_count, h->kp_list, h->prof, h->done_counter, h->cluster_sync, h->bm_scratch, h->x_spec, h->u_spec, h->lxu,
-                  h->ulim, h->s2};
+                  h->ulim, h->s2, h->x_nom_rows, h->target_steps};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->mpc_log) (void)hipFree(h->mpc_log);
@@ -867,10 +870,79 @@ static bool is_sym_psd(const double* A, int k, bool strict) {
   return true;
 }
 
+// Per-problem targets (MI_F_X_NOM / MI_F_TARGET_STEP).  The host mirrors h_x_nom_rows / h_target_steps are the truth that
+// mi_ilqr_get returns; the device copies follow them on the handle's stream.
+static void drop_per_problem_targets(mi_ilqr* h) {
+  h->per_problem_targets = false;
+  h->target_steps_moving = false;
+  h->h_x_nom_rows.clear();
+  h->h_target_steps.clear();
+}
+
+static const double* shared_x_nom(const mi_ilqr* h) { return h->h_costmat.data() + 2 * (size_t)h->n * h->n + (size_t)h->m * h->m; }
+
+// Switch to per-problem targets: rows = the shared x_nom broadcast, steps = zeros (both then overwritten by the caller's field).
+static int enter_per_problem_targets(mi_ilqr* h) {
+  if (h->per_problem_targets) return MI_ILQR_OK;
+  const size_t B = h->B, n = h->n;
+  if (!h->x_nom_rows) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->x_nom_rows), B * n * 8));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->target_steps), B * n * 8));
+  }
+  h->h_x_nom_rows.resize(B * n);
+  for (size_t b = 0; b < B; ++b) std::memcpy(h->h_x_nom_rows.data() + b * n, shared_x_nom(h), n * 8);
+  h->h_target_steps.assign(B * n, 0.0);
+  int rc = stage_h2d(h, h->x_nom_rows, h->h_x_nom_rows.data(), B * n * 8);
+  if (rc == MI_ILQR_OK) rc = stage_h2d(h, h->target_steps, h->h_target_steps.data(), B * n * 8);
+  if (rc != MI_ILQR_OK) { drop_per_problem_targets(h); return rc; }
+  h->per_problem_targets = true;
+  h->target_steps_moving = false;
+  return MI_ILQR_OK;
+}
+
+static int set_target_field(mi_ilqr* h, int which, const double* src, size_t bytes) {
+  const size_t cnt = (size_t)h->B * h->n;
+  if (bytes != cnt * 8) return MI_ILQR_E_BAD_SHAPE;
+  for (size_t i = 0; i < cnt; ++i) if (src[i] != src[i]) return MI_ILQR_E_BAD_ARG;
+  HIPCHK(hipSetDevice(h->d.device_id));
+  int rc = enter_per_problem_targets(h);
+  if (rc != MI_ILQR_OK) return rc;
+  std::vector<double>& mirror = which == MI_F_X_NOM ? h->h_x_nom_rows : h->h_target_steps;
+  std::memcpy(mirror.data(), src, bytes);
+  if ((rc = stage_h2d(h, which == MI_F_X_NOM ? h->x_nom_rows : h->target_steps, mirror.data(), bytes)) != MI_ILQR_OK) return rc;
+  if (which == MI_F_TARGET_STEP) {
+    h->target_steps_moving = false;
+    for (size_t i = 0; i < cnt; ++i) if (src[i] != 0.0) h->target_steps_moving = true;
+  }
+  return MI_ILQR_OK;
+}
+
+static int get_target_field(mi_ilqr* h, int which, double* dst, size_t bytes) {
+  const size_t B = h->B, n = h->n;
+  if (bytes != B * n * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (h->per_problem_targets) {
+    std::memcpy(dst, (which == MI_F_X_NOM ? h->h_x_nom_rows : h->h_target_steps).data(), bytes);
+  } else if (which == MI_F_X_NOM) {
+    for (size_t b = 0; b < B; ++b) std::memcpy(dst + b * n, shared_x_nom(h), n * 8);
+  } else {
+    std::memset(dst, 0, bytes);
+  }
+  return MI_ILQR_OK;
+}
+
+// mpc_run with per-problem targets: every row moves by its own step, once per re-solve - fp64 repeated addition, what the kernels do
+static int advance_per_problem_targets(mi_ilqr* h, int32_t times) {
+  const size_t cnt = (size_t)h->B * h->n;
+  for (int32_t r = 0; r < times; ++r)
+    for (size_t i = 0; i < cnt; ++i) h->h_x_nom_rows[i] += h->h_target_steps[i];
+  return stage_h2d(h, h->x_nom_rows, h->h_x_nom_rows.data(), cnt * 8);
+}
+
 int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const double* Qf, const double* x_nom) {
   if (!h) return MI_ILQR_E_BAD_ARG;
   HIPCHK(hipSetDevice(h->d.device_id));
   const size_t n = h->n, m = h->m;
+  if (x_nom) drop_per_problem_targets(h);   // one target for the batch again: the per-problem targets and steps are dropped
   {
     // The time-parallel / matrix-core backward passes use Vxx = Vxx^T and (scan) PSD second-order terms; the
     // reference accepts ANY Q, R, Qf and never symmetrizes (ilqr.py:182,653-667).  Matrices outside that
@@ -1284,6 +1356,7 @@ __global__ void __launch_bounds__(256) mpc_log_fill_kernel(const double* __restr
 int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, const double* target_step, mi_ilqr_stats* stats) {
   if (!h) return MI_ILQR_E_BAD_ARG;
   if (num_resolves < 1 || replan_steps < 1 || replan_steps >= h->N - 1) return MI_ILQR_E_BAD_ARG;
+  if (h->per_problem_targets && target_step) return MI_ILQR_E_BAD_ARG;   // the steps are the field MI_F_TARGET_STEP then
   HIPCHK(hipSetDevice(h->d.device_id));
   int rc;
   if (h->mpc_log_resolves < num_resolves) {
@@ -1311,6 +1384,7 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
         for (int i = 0; i < h->n; ++i) xn[i] += target_step[i];
         if ((rc = mi_ilqr_set_cost(h, nullptr, nullptr, nullptr, xn.data())) != MI_ILQR_OK) return rc;
       }
+      if (h->per_problem_targets && (rc = advance_per_problem_targets(h, 1)) != MI_ILQR_OK) return rc;   // one (B, n) upload
       mi_ilqr_stats st;
       if ((rc = mi_ilqr_solve(h, &st)) != MI_ILQR_OK) return rc;
       hipLaunchKernelGGL(mpc_log_fill_kernel, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, h->x0, h->cost, h->iters, h->status, h->mpc_log,
@@ -1337,6 +1411,10 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
                        h->B, h->d_ring, h->cur_slot, (int)mi_ilqr::kStatsRing);
     HIPCHK(hipGetLastError());
   }
+  if (h->per_problem_targets) {   // the rows the kernel moved, every problem's num_resolves times (a failed problem's included)
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = advance_per_problem_targets(h, num_resolves)) != MI_ILQR_OK) return rc;
+  }
   if (target_step) {          // keep the handle's x_nom in step with what the kernel accumulated
     std::vector<double> xn(h->n);
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1360,6 +1438,7 @@ int mi_ilqr_get_mpc_log(mi_ilqr_t* h, double* dst, size_t bytes) {
 
 int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
+  if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return get_target_field(h, which, dst, bytes);
   Field f = field_of(h, which);
   if (!f.ptr || f.is_int) return MI_ILQR_E_BAD_ARG;
   if (bytes != f.bytes && !prefix_ok(which, bytes, f.bytes)) return MI_ILQR_E_BAD_SHAPE;
@@ -1384,6 +1463,11 @@ int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
 
 int mi_ilqr_get_async(mi_ilqr_t* h, int which, void* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
+  if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) {      // (host mirrors: the copy is done when the call returns)
+    HIPCHK(hipSetDevice(h->d.device_id));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return get_target_field(h, which, static_cast<double*>(dst), bytes);
+  }
   Field f = field_of(h, which);
   if (!f.ptr) return MI_ILQR_E_BAD_ARG;
   if (bytes != f.bytes && !prefix_ok(which, bytes, f.bytes)) return MI_ILQR_E_BAD_SHAPE;
@@ -1423,6 +1507,7 @@ int mi_ilqr_get_int(mi_ilqr_t* h, int which, int32_t* dst, size_t bytes) {
 
 int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
   if (!h || !src) return MI_ILQR_E_BAD_ARG;
+  if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return set_target_field(h, which, src, bytes);
   Field f = field_of(h, which);
   if (!f.ptr || f.is_int) return MI_ILQR_E_BAD_ARG;
   if (bytes != f.bytes) return MI_ILQR_E_BAD_SHAPE;
@@ -1446,6 +1531,12 @@ int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
 
 int mi_ilqr_device_ptr(mi_ilqr_t* h, int which, void** ptr, size_t* bytes) {
   if (!h || !ptr) return MI_ILQR_E_BAD_ARG;
+  if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) {      // per-problem mode only: the (B, n) device copies
+    if (!h->per_problem_targets) return MI_ILQR_E_BAD_ARG;
+    *ptr = which == MI_F_X_NOM ? h->x_nom_rows : h->target_steps;
+    if (bytes) *bytes = (size_t)h->B * h->n * 8;
+    return MI_ILQR_OK;
+  }
   Field f = field_of(h, which);
   if (!f.ptr) return MI_ILQR_E_BAD_ARG;
   *ptr = f.ptr;

@@ -139,7 +139,20 @@ class BatchedIterativeLQR:
         self.x0 = x0
 
     def SetTargetState(self, x_nom):
-        self.x_nom = np.asarray(x_nom).reshape((self.n,))
+        """(n,) or (1, n): one target for the batch (the reference's argument).  (B, n): every problem its own target - the
+        reference's SetTargetState called on each problem's own object (include/mi_ilqr.h: "Per-problem targets")."""
+        x_nom = np.asarray(x_nom)
+        if x_nom.size != self.n and x_nom.shape == (self.B, self.n):
+            self.x_nom = x_nom
+        else:
+            self.x_nom = x_nom.reshape((self.n,))
+
+    def _per_problem_targets(self):
+        return np.ndim(self.x_nom) == 2
+
+    def _set_field(self, which, a):
+        a = _capi.as_f64(a, (self.B, self.n))
+        _capi.check(self._lib.mi_ilqr_set(self._h, which, _capi.ptr(a), a.nbytes), "mi_ilqr_set")
 
     def SetRunningCost(self, Q, R):
         assert Q.shape == (self.n, self.n)
@@ -187,9 +200,12 @@ class BatchedIterativeLQR:
     def _push_problem(self):
         x_nom = self.x_nom             # AttributeError if SetTargetState was never called, as in the reference
         Q, R, Qf = (_capi.as_f64(a) for a in (self.Q, self._pad_u(self.R, (0, 1), diag=1.0), self.Qf))
-        xn = _capi.as_f64(x_nom, (self.n,))
+        per_problem = np.ndim(x_nom) == 2
+        xn = None if per_problem else _capi.as_f64(x_nom, (self.n,))
         _capi.check(self._lib.mi_ilqr_set_cost(self._h, _capi.ptr(Q), _capi.ptr(R), _capi.ptr(Qf), _capi.ptr(xn)),
                     "mi_ilqr_set_cost")
+        if per_problem:                # (B, n): the handle's per-problem targets (a shared x_nom above switches them off again)
+            self._set_field(_capi.F_X_NOM, x_nom)
         x0 = np.asarray(self.x0, dtype=np.float64).reshape(-1, self.n)
         x0 = np.ascontiguousarray(x0 if len(x0) == self.B else np.broadcast_to(x0, (self.B, self.n)))
         ug = None
@@ -462,12 +478,22 @@ class BatchedIterativeLQR:
         wave-per-problem and workgroup-per-problem models (the lane-per-problem "throughput" kernels loop on
         the host).  Returns the aggregate stats; `mpc_log` has the per-re-solve record."""
         ts = None
-        if target_step is not None:
-            ts = _capi.as_f64(target_step, (self.n,))
+        steps = None if target_step is None else np.asarray(target_step, dtype=np.float64)
+        per_problem = self._per_problem_targets() or (steps is not None and steps.shape == (self.B, self.n) and steps.size != self.n)
+        if per_problem:
+            # (B, n) steps, or targets that are per-problem already: every problem's target moves by its own row
+            self._set_field(_capi.F_TARGET_STEP, np.zeros((self.B, self.n)) if steps is None
+                            else np.broadcast_to(steps.reshape((self.n,)) if steps.size == self.n else steps, (self.B, self.n)))
+        elif steps is not None:
+            ts = _capi.as_f64(steps, (self.n,))
             self.x_nom = np.asarray(self.x_nom, dtype=np.float64) + num_resolves * ts
         stats = _capi.Stats()
         _capi.check(self._lib.mi_ilqr_mpc_run(self._h, int(num_resolves), int(replan_steps), _capi.ptr(ts), C.byref(stats)),
                     "mi_ilqr_mpc_run")
+        if per_problem:                # the targets as the loop left them (x_nom_b + step_b added num_resolves times)
+            out = np.empty((self.B, self.n))
+            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_X_NOM, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+            self.x_nom = out
         self.stats = stats
         self._mpc_resolves = int(num_resolves)
         self._check_internal(stats)
@@ -483,6 +509,9 @@ class BatchedIterativeLQR:
     def SetTargetStateResident(self, x_nom):
         """Moving target between resident re-solves (mini_cheetah.py:151-156)."""
         self.SetTargetState(x_nom)
+        if self._per_problem_targets():
+            self._set_field(_capi.F_X_NOM, self.x_nom)
+            return
         xn = _capi.as_f64(self.x_nom, (self.n,))
         _capi.check(self._lib.mi_ilqr_set_cost(self._h, None, None, None, _capi.ptr(xn)), "mi_ilqr_set_cost")
 

@@ -120,6 +120,8 @@ enum {
                            linearization (0 when the rollout linearized on its way), backward pass, whole iteration - the
                            reference's time_fp / time_getDerivs / time_backwardsPass / iter time (ilqr.py:364-372,696-702);
                            wave- and workgroup-per-problem kernels */
+  MI_F_X_NOM = 14,      /* (B,n) per-problem targets x_nom_b (mi_ilqr_set_cost, "Per-problem targets" below)              */
+  MI_F_TARGET_STEP = 15,/* (B,n) per-problem target_step_b of mi_ilqr_mpc_run                                             */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
@@ -245,6 +247,20 @@ void mi_ilqr_destroy(mi_ilqr_t* h);
  * definite. */
 int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const double* Qf, const double* x_nom);
 
+/* Per-problem targets (the reference's SetTargetState, ilqr.py:111-118, called on each problem's own object; mini_cheetah.py:151-156
+ * moves it every re-solve).  Q, R, Qf stay shared by the batch.
+ *   mi_ilqr_set(MI_F_X_NOM, (B,n))       gives every problem its own x_nom and switches the handle to PER-PROBLEM TARGETS;
+ *   mi_ilqr_set(MI_F_TARGET_STEP, (B,n)) gives every problem its own target_step of mi_ilqr_mpc_run; set in shared mode it also
+ *                                        switches: the targets start as the shared x_nom broadcast, the steps as zeros until set.
+ *   mi_ilqr_get returns the targets (B,n) in both modes (shared mode: the shared x_nom broadcast) and the steps (zeros in shared mode);
+ *   mi_ilqr_device_ptr returns the (B,n) device copies in per-problem mode (MI_ILQR_E_BAD_ARG in shared mode).
+ *   Per-problem mode: mi_ilqr_mpc_run's target_step must be NULL (else MI_ILQR_E_BAD_ARG); before each re-solve every problem's target
+ *   moves by its own row; after the call MI_F_X_NOM holds, for EVERY problem (failed ones included), x_nom_b with step_b added
+ *   num_resolves times - fp64 repeated addition, the kernels' arithmetic - so the single-launch and host-loop forms agree bitwise.
+ *   mi_ilqr_set_cost with a non-NULL x_nom returns the handle to shared mode and drops both fields: it is then bitwise a
+ *   never-per-problem one.  Targets are problem data: they survive mi_ilqr_reset.  Wrong `bytes` is MI_ILQR_E_BAD_SHAPE, a NaN
+ *   MI_ILQR_E_BAD_ARG (the handle keeps what it had).  Every kernel family, solve, mpc_run and the stage entries. */
+
 /* SetInitialState / SetInitialGuess (ilqr.py:102-109,148-156): x0 (B,n), u_guess (B,m,N-1).
  * u_guess becomes u_bar (the reference aliases it, ilqr.py:156).  NULL = keep.
  * Ordering against mi_ilqr_solve_async: the new inputs are those of the NEXT solve.  Handles of more than four problems copy them
@@ -336,7 +352,10 @@ int mi_ilqr_mpc_shift(mi_ilqr_t* h, int32_t replan_steps);
  * A problem whose re-solve r FAILS (line search, MI_STATUS_NOT_PD, internal) gets row r of the log and none after it:
  * the log is zero-filled at every call and both forms stop logging the problem there (rows r+1.. read as zeros).  The
  * single-launch forms also stop RE-SOLVING it (its status is that of re-solve r); the host-loop form's batched launches
- * cannot leave a problem out - it is shifted and solved on, and its final status is the last re-solve's. */
+ * cannot leave a problem out - it is shifted and solved on, and its final status is the last re-solve's.
+ * Per-problem targets (MI_F_X_NOM / MI_F_TARGET_STEP, after mi_ilqr_set_cost): target_step must be NULL (else MI_ILQR_E_BAD_ARG),
+ * each problem's target moves by its own (B,n) row before each re-solve, and MI_F_X_NOM holds x_nom_b + step_b added num_resolves
+ * times afterwards, in both forms. */
 int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, const double* target_step, mi_ilqr_stats* stats);
 int mi_ilqr_get_mpc_log(mi_ilqr_t* h, double* dst, size_t bytes);
 
