@@ -336,8 +336,9 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
             if (act) {
 #pragma unroll
               for (int r = 0; r < cnt; ++r) fS[r] = fE[r];
-              s_ = t; ptr += 1;
-              next = ptr < nk_ ? kpl[(size_t)ptr * Bz] : -1;
+              s_ = t;
+              // past every entry <= t: an adaptiveJerk list can hold t = 0 twice (ilqr.py:452-463, minN = 1 or maxN = 1)
+              do { ptr += 1; next = ptr < nk_ ? kpl[(size_t)ptr * Bz] : -1; } while (next >= 0 && next <= t);
             }
           }
         };

@@ -633,6 +633,9 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   if (desc->N < 2 || desc->B < 1) return MI_ILQR_E_BAD_SHAPE;
   if (desc->keypoint_method < MI_KP_SET_INTERVAL || desc->keypoint_method > MI_KP_ITERATIVE_ERROR) return MI_ILQR_E_BAD_METHOD;
   if (desc->minN < 1) return MI_ILQR_E_BAD_ARG;
+  // adaptiveJerk with maxN < 1 can append two key-points per step (ilqr.py:452-463): its list would outgrow the N - 1 slots
+  // of every key-point buffer.  The other methods never read maxN (callers pass 0 with setInterval).
+  if (desc->keypoint_method == MI_KP_ADAPTIVE_JERK && desc->maxN < 1) return MI_ILQR_E_BAD_ARG;
   if (desc->jacobian_mode != MI_JAC_FD_CENTRAL && desc->jacobian_mode != MI_JAC_AUTODIFF) return MI_ILQR_E_BAD_ARG;
   if (desc->jacobian_mode == MI_JAC_FD_CENTRAL && !(desc->fd_step > 0.0)) return MI_ILQR_E_BAD_ARG;
 
@@ -782,6 +785,13 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   }
   if (batch_minor && !(desc->keypoint_method == MI_KP_SET_INTERVAL && desc->minN == 1)) ALLOC(h->bm_scratch, B * 6 * (N - 1), int32_t);
 #undef ALLOC
+  if (batch_minor && desc->keypoint_method == MI_KP_SET_INTERVAL && desc->minN == 1) {
+    // the KP = false lane-per-problem kernels never write the key-point list: every step is a key-point (ilqr.py:417-432), the
+    // same list for every problem and every linearization - stored once here
+    std::vector<int32_t> kl(B * (N - 1));
+    for (size_t i = 0; i < kl.size(); ++i) kl[i] = (int32_t)(i % (N - 1));
+    if (hipMemcpy(h->kp_list, kl.data(), kl.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { mi_ilqr_destroy(h); return MI_ILQR_E_HIP; }
+  }
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, desc->device_id) == hipSuccess) h->n_cus = cus;

@@ -153,7 +153,10 @@ typedef struct {
   double model_params[MI_ILQR_MAX_PARAMS];
   double dt;
   double delta, beta, gamma;                 /* ilqr.py:52-54 */
-  int32_t keypoint_method, minN, maxN;       /* derivs_interpolation fields */
+  int32_t keypoint_method, minN, maxN;       /* derivs_interpolation fields; minN >= 1, and maxN >= 1 with MI_KP_ADAPTIVE_JERK
+                                                (else MI_ILQR_E_BAD_ARG).  The reference accepts adaptiveJerk with maxN < 1, and its
+                                                list can then take two entries per step and grow past N - 1 (ilqr.py:452-463);
+                                                no key-point buffer here holds more than N - 1. */
   double jerk_threshold, iterative_error_threshold;
   int32_t jacobian_mode;
   double fd_step;                            /* absolute central-difference step */

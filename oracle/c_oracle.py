@@ -52,7 +52,8 @@ def solve_batch(model, prob, x0, u_guess=None, minN=1, fd_h=1e-5, nthreads=0, wa
     """Cold-start batched solve on the host.  model: oracle.models_np.Model.  keypoint: (method, minN, maxN,
     jerk_threshold, iterative_error_threshold) like utils_derivs_interpolation.derivs_interpolation; hist_cap > 0
     also returns hist (B, hist_cap, 4) = cost | eps | trials | key-point count per iteration, and the key-points of
-    the last linearization (kp_count (B,), kp_list (B, N-1))."""
+    the last linearization (kp_count (B,), kp_list (B, N-1)).  ValueError for minN < 1, or adaptiveJerk with maxN < 1 (its
+    list could outgrow N - 1: mi_ilqr_create refuses it too)."""
     lib = load(native)
     n, m, N = model.n, model.m, prob["N"]
     x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, n)
@@ -78,6 +79,10 @@ def solve_batch(model, prob, x0, u_guess=None, minN=1, fd_h=1e-5, nthreads=0, wa
                                      p(out.get("x_bar")), p(out.get("u_bar")), p(out.get("K")), p(out.get("kappa")),
                                      p(out["cost"]), p(out["iters"]), p(out["ls"]), p(out["status"]), int(nthreads),
                                      p(out.get("hist")), int(hist_cap), p(out.get("kp_count")), p(out.get("kp_list")))
+    if used == -2:
+        raise ValueError("key-point configuration refused: minN < 1, or adaptiveJerk with maxN < 1 (its list could outgrow N - 1)")
+    if used < 0:
+        raise ValueError(f"oracle_solve_batch_ex refused the problem ({used})")
     out["threads"] = used
     return out
 

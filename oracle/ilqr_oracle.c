@@ -751,13 +751,16 @@ int oracle_solve_batch(const oracle_cfg* c, int B, const double* Q, const double
 }
 
 /* ... with the per-iteration history (B, hist_cap, 4) and the key-points of the LAST linearization (counts (B,), lists
- * (B, N-1)); any of them may be NULL. */
+ * (B, N-1)); any of them may be NULL.  Returns -1 for n or m above MAXN / MAXM, -2 for minN < 1 or adaptiveJerk with
+ * maxN < 1 (like mi_ilqr_create: that list can outgrow N - 1). */
 int oracle_solve_batch_ex(const oracle_cfg* c, int B, const double* Q, const double* R, const double* Qf, const double* xnom,
                           const double* x0, const double* u_guess, double* x_bar, double* u_bar, double* K, double* kappa,
                           double* cost, int* iters, int* ls_trials, int* status, int nthreads,
                           double* hist, int hist_cap, int* kp_count, int* kp_list) {
   const int n = c->n, m = c->m, N = c->N;
   if (n > MAXN || m > MAXM) return -1;
+  /* adaptiveJerk with maxN < 1 can append two key-points per step (ilqr.py:452-463): refused, like mi_ilqr_create does */
+  if (c->minN < 1 || (c->kp_method == 1 && c->maxN < 1)) return -2;
   int used = 1;
 #ifdef _OPENMP
   if (nthreads > 0) omp_set_num_threads(nthreads);

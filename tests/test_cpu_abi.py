@@ -76,6 +76,29 @@ def test_create_validates_and_fails_loudly_without_gpu(lib):
         assert not h.value
 
 
+def test_create_refuses_adaptive_jerk_with_maxN_below_one(lib):
+    """adaptiveJerk with maxN < 1 can append two key-points per step (ilqr.py:452-463), past the N - 1 slots of every
+    key-point buffer: refused before any device is touched.  setInterval and iterativeError never read maxN, and callers
+    pass 0 there: still accepted."""
+    import torch
+    from drake_ddp_amd import _capi
+    d = _capi.Desc()
+    d.n, d.m, d.N, d.B, d.model_id, d.minN, d.fd_step = 2, 1, 40, 4, 0, 1, 1e-5
+    h = C.c_void_p()
+    for maxN in (0, -1):
+        bad = _capi.Desc.from_buffer_copy(d); bad.keypoint_method, bad.maxN = _capi.KP_ADAPTIVE_JERK, maxN
+        assert lib.mi_ilqr_create(C.byref(bad), C.byref(h)) == _capi.E_BAD_ARG, maxN
+        assert not h.value
+    for method, maxN in ((_capi.KP_SET_INTERVAL, 0), (_capi.KP_ITERATIVE_ERROR, -1), (_capi.KP_ADAPTIVE_JERK, 1)):
+        ok = _capi.Desc.from_buffer_copy(d); ok.keypoint_method, ok.maxN = method, maxN
+        rc = lib.mi_ilqr_create(C.byref(ok), C.byref(h))
+        if torch.cuda.is_available():
+            assert rc == _capi.OK, (method, maxN)
+            lib.mi_ilqr_destroy(h)
+        else:
+            assert rc == _capi.E_NO_DEVICE, (method, maxN)
+
+
 def test_product_never_imports_oracle():
     pkg = os.path.join(ROOT, "drake_ddp_amd")
     for dirpath, _, files in os.walk(pkg):

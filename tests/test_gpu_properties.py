@@ -627,10 +627,7 @@ def test_longest_horizons_of_the_workgroup_kernels_vs_c_oracle():
             ug = ugf(N)
             s = make_solver(p, B=B, jac="fd", hist_cap=256)
             s.SetInitialState(x0); s.SetInitialGuess(ug)
-            try:
-                s.Solve()
-            except RuntimeError:
-                pass
+            s.Solve()
             model = M.Model(p["model_id"], p["dt"])
             r = c_oracle.solve_batch(model, p, x0, ug)
             rel = np.abs(s.cost - r["cost"]) / np.abs(r["cost"])
@@ -676,10 +673,7 @@ def test_randomized_configs_of_the_workgroup_kernels_vs_c_oracle(seed):
     x0, ug = x0f(B), ugf(N)
     s = make_solver(prob, B=B, jac="fd", hist_cap=8)
     s.SetInitialState(x0); s.SetInitialGuess(ug)
-    try:
-        s.Solve()
-    except RuntimeError:
-        pass
+    s.Solve()
     model = M.Model(prob["model_id"], prob["dt"])
     r = c_oracle.solve_batch(model, prob, x0, ug)
     same = (s.status == r["status"]) & (s.iterations == r["iters"]) & (s.ls_trials == r["ls"])
@@ -752,10 +746,7 @@ def test_mpc_loop_replan_extremes_vs_c_oracle(replan):
         s.SetInitialState(x0); s.SetInitialGuess(ug)
         s.Solve()
         first_it = s.iterations.copy()
-        try:
-            s.MPCRun(3, r_)
-        except RuntimeError:
-            pass
+        s.MPCRun(3, r_)
         log = s.mpc_log
         r = c_oracle.mpc_batch(M.Model(prob["model_id"], prob["dt"]), prob, x0, ug, 3, r_)
         assert np.array_equal(first_it, r["first"][:, 1].astype(int)), name
@@ -798,10 +789,7 @@ def test_randomized_keypoint_configs_vs_c_oracle(seed):
     x0, ug = x0f(B), ugf(N)
     s = make_solver(p, B=B, keypoint=kp, jac="fd", hist_cap=64, **kw)
     s.SetInitialState(x0); s.SetInitialGuess(ug)
-    try:
-        s.Solve()
-    except RuntimeError:
-        pass
+    s.Solve()
     r = c_oracle.solve_batch(M.Model(p["model_id"], p["dt"]), p, x0, ug, keypoint=kp, hist_cap=64)
     h, nk, kl = s.history, s.keypoint_count, s.keypoint_list
     exact = np.zeros(B, bool)
@@ -866,10 +854,7 @@ def test_other_model_parameters_vs_c_oracle():
         p = dict(prob, params=params)
         s = make_solver(p, B=len(x0), jac="fd", **kw)
         s.SetInitialState(x0); s.SetInitialGuess(ug)
-        try:
-            s.Solve()
-        except RuntimeError:
-            pass
+        s.Solve()
         r = c_oracle.solve_batch(M.Model(prob["model_id"], prob["dt"], params), p, x0, ug)
         same = (s.status == r["status"]) & (s.iterations == r["iters"]) & (s.ls_trials == r["ls"])
         fin = same & np.isfinite(r["cost"])
