@@ -1,6 +1,6 @@
 // Host-side pieces shared by the translation units of libmi_ilqr.so: the handle, the error macro and the
 // kernel-launch templates.  mi_ilqr.hip holds the C ABI; every model's kernels are instantiated in their own
-// k_<model>.hip (built in parallel, drake_ddp_amd/build.py) behind one `launch_<model>(handle, mode, args)` each.
+// k_<model>.hip (built in parallel, drake_ddp_amd/build.py), reached through the model's launch entry (launch_entry below).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -8,11 +8,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mi_ilqr.h"
 #include "ilqr_small.hpp"
 
+// library-internal: hidden from the dynamic symbol table (the C ABI is mi_ilqr.h)
+#define MI_INTERNAL __attribute__((visibility("hidden")))
 
 struct mi_ilqr {
   mi_ilqr_desc d;
@@ -100,15 +103,39 @@ struct mi_ilqr {
   std::vector<double> h_x_nom_rows, h_target_steps;
 };
 
+// Run-time switches for A/B runs (README): the environment is read once per process.
+struct Switches {
+  bool no_helper;        // MI_ILQR_NO_HELPER=1: no helper wavefronts (make_args)
+  bool seq_backward;     // MI_ILQR_SEQ_BACKWARD=1: sequential instead of time-parallel backward sweep
+  bool seq_rollout;      // MI_ILQR_SEQ_ROLLOUT=1: sequential instead of time-parallel rollout
+  int stats_kernel;      // MI_ILQR_STATS_KERNEL: -1 unset, 1 the separate kernel, 0 the in-kernel epilogue (stats_in_kernel)
+  int spec;              // MI_ILQR_SPEC: line-search candidate policy of the mid-size kernels (default 1; outside 0..2: 0)
+  int cluster;           // MI_ILQR_CLUSTER: workgroups per problem, forced when > 0 (cluster_size)
+  int cluster_order;     // MI_ILQR_CLUSTER_ORDER: placement of a cluster's workgroups (default 2)
+  int early;             // MI_ILQR_EARLY: early linearization by the helpers (default 1)
+  int ls_groups;         // MI_ILQR_LS_GROUPS: candidate groups (default 1)
+};
+MI_INTERNAL inline const Switches& switches() {
+  static const Switches s = [] {
+    auto on = [](const char* name) { const char* e = std::getenv(name); return e && e[0] == '1'; };
+    auto num = [](const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; };
+    const char* stats = std::getenv("MI_ILQR_STATS_KERNEL");
+    const int spec = num("MI_ILQR_SPEC", 1);
+    return Switches{on("MI_ILQR_NO_HELPER"), on("MI_ILQR_SEQ_BACKWARD"), on("MI_ILQR_SEQ_ROLLOUT"),
+                    !stats ? -1 : (stats[0] == '1' ? 1 : 0), (spec >= 0 && spec <= 2) ? spec : 0, num("MI_ILQR_CLUSTER", 0),
+                    num("MI_ILQR_CLUSTER_ORDER", 2), num("MI_ILQR_EARLY", 1), num("MI_ILQR_LS_GROUPS", 1)};
+  }();
+  return s;
+}
+
 // Small batches of the wave-per-problem kernels aggregate the batch statistics in the solve kernel
 // itself (last workgroup to finish): a blocking single-problem solve saves a kernel launch, 5 us of
 // 98.  Large batches keep the separate stats_kernel: with pipelined solves the two cost the same per
 // step (measured at B = 1024: 0.166 ms either way), and the solve kernel stays 3.6 us shorter.
 // MI_ILQR_STATS_KERNEL=1 / =0 forces the separate kernel / the in-kernel epilogue (A/B runs).
 static inline bool stats_in_kernel(const mi_ilqr* h) {
-  static const int forced = [] { const char* e = std::getenv("MI_ILQR_STATS_KERNEL"); return !e ? -1 : (e[0] == '1' ? 1 : 0); }();
   if (h->large || h->batch_minor) return false;
-  if (forced >= 0) return forced == 0;
+  if (switches().stats_kernel >= 0) return switches().stats_kernel == 0;
   return h->B <= 64;
 }
 static inline void select_stats_slot(mi_ilqr* h, int slot) {
@@ -131,10 +158,10 @@ using namespace mi;
   } while (0)
 
 constexpr size_t kMaxLds = 160 * 1024;
-// A plugin's launch entry asked with this mode (and h->limited set) answers MI_ILQR_OK when it carries Limited<M> kernels, launching
-// nothing (mi_ilqr_set_control_limits; family-1 plugins carry them when built with them: plugin.py, control_limits=True).
+// A model's launch entry asked with this mode answers MI_ILQR_OK when it carries Limited<M> kernels, launching nothing
+// (mi_ilqr_set_control_limits; family-1 plugins carry them when built with them: plugin.py, control_limits=True).
 constexpr int kModeProbeLimits = 0x4c494d;
-constexpr int kMaxBatchPluginN = 6;      // family-0 plugin models up to this n also get the lane-per-problem kernels
+constexpr int kMaxBatchPluginN = 6;      // family-0 models up to this n also get the lane-per-problem kernels
 
 // The dynamic-LDS ceiling of a kernel is raised once per (kernel, device), to the hardware maximum - not
 // on every launch.
@@ -164,25 +191,51 @@ int launch_timed(mi_ilqr* h, Kern kern, dim3 grid, dim3 block, size_t lds, const
   return MI_ILQR_OK;
 }
 
+// Run-time choices turned into template arguments: with_jac calls f(std::integral_constant<int, JAC>{}) for the handle's Jacobian
+// mode, with_mode f(std::integral_constant<int, MODE>{}) for `mode` when it is one of MODES (else MI_ILQR_E_BAD_ARG), with_any_mode
+// the same over the six kernel modes.  Only what f is called with gets instantiated.
+template <class F>
+int with_jac(const mi_ilqr* h, F&& f) {
+  if (h->d.jacobian_mode == MI_JAC_AUTODIFF) return f(std::integral_constant<int, MI_JAC_AUTODIFF>{});
+  return f(std::integral_constant<int, MI_JAC_FD_CENTRAL>{});
+}
+template <int MODE, int... MODES, class F>
+int with_mode(int mode, F&& f) {
+  if (mode == MODE) return f(std::integral_constant<int, MODE>{});
+  if constexpr (sizeof...(MODES) > 0) return with_mode<MODES...>(mode, f);
+  return MI_ILQR_E_BAD_ARG;
+}
+template <class F>
+int with_any_mode(int mode, F&& f) {
+  return with_mode<MODE_SOLVE, MODE_ROLLOUT, MODE_FORWARD, MODE_LINEARIZE, MODE_BACKWARD, MODE_MPC>(mode, f);
+}
+
 }  // namespace mi_host
 
-// one per kernel translation unit (library-internal: hidden from the dynamic symbol table, the C ABI is mi_ilqr.h)
-#define MI_INTERNAL __attribute__((visibility("hidden")))
-MI_INTERNAL int launch_pendulum(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_acrobot(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_cartpole(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_cartpole_wall(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_synth36(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_planar_quad(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_quad3d(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_arm27(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_arm27c(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_batch_minor(mi_ilqr* h, int mode, const mi::KArgs& a);
-// the same with control limits (Limited<M> kernels: k_<model>_lim.hip, k_batch_lim.hip)
-MI_INTERNAL int launch_pendulum_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_acrobot_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_cartpole_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_cartpole_wall_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_batch_minor_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_arm27_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
-MI_INTERNAL int launch_arm27c_lim(mi_ilqr* h, int mode, const mi::KArgs& a);
+// The kernel sets of a model: one launcher per set, (handle, mode, args) -> status.  Instantiated for the built-in models in their
+// own translation units (k_<model>.hip, k_<model>_lim.hip, k_batch.hip, k_batch_lim.hip: explicit instantiations), for a plugin model
+// in its unit (drake_ddp_amd/plugin.py).
+namespace mi_host {
+using Launcher = int (*)(mi_ilqr* h, int mode, const KArgs& a);
+template <class M> MI_INTERNAL int launch_jac(mi_ilqr* h, int mode, const KArgs& a);                 // launch_small.hpp
+template <class M> MI_INTERNAL int launch_limited(mi_ilqr* h, int mode, const KArgs& a);
+template <class M> MI_INTERNAL int launch_jac_large(mi_ilqr* h, int mode, const KArgs& a);           // launch_large.hpp
+template <class M> MI_INTERNAL int launch_jac_large_limited(mi_ilqr* h, int mode, const KArgs& a);
+template <class M> MI_INTERNAL int launch_batch(mi_ilqr* h, int mode, const KArgs& a);               // launch_batch.hpp
+template <class M> MI_INTERNAL int launch_batch_limited(mi_ilqr* h, int mode, const KArgs& a);
+
+// The launch entry of a model's record (mi_ilqr_model_plugin::launch), built-in or plugin: the handle picks the kernel set - the
+// lane-per-problem kernels (h->batch_minor), the Limited<M> ones (h->limited), else the regular ones.  A set the model lacks is
+// nullptr; the probe (kModeProbeLimits) answers whether it has Limited<M> kernels, launching nothing.
+template <Launcher REGULAR, Launcher LIMITED = nullptr, Launcher BATCH = nullptr, Launcher BATCH_LIMITED = nullptr>
+int launch_entry(mi_ilqr* h, int mode, const void* kargs) {
+  if (mode == kModeProbeLimits) return LIMITED ? MI_ILQR_OK : MI_ILQR_E_UNSUPPORTED;
+  const KArgs& a = *static_cast<const KArgs*>(kargs);
+  if (h->batch_minor) {
+    if constexpr (BATCH != nullptr && BATCH_LIMITED != nullptr) return h->limited ? BATCH_LIMITED(h, mode, a) : BATCH(h, mode, a);
+    return MI_ILQR_E_UNSUPPORTED;
+  }
+  if constexpr (LIMITED != nullptr) if (h->limited) return LIMITED(h, mode, a);
+  return REGULAR(h, mode, a);
+}
+}  // namespace mi_host

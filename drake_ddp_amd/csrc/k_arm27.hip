@@ -1,4 +1,4 @@
 // Workgroup-per-problem kernels of the Arm27 model (n = 27, m = 7: the mid-size family of ilqr_large.hpp): every (Jacobian mode, kernel mode) instantiation.
 #include "launch_large.hpp"
 
-MI_INTERNAL int launch_arm27(mi_ilqr* h, int mode, const mi::KArgs& a) { return mi_host::launch_jac_large<mi::Arm27>(h, mode, a); }
+template int mi_host::launch_jac_large<mi::Arm27>(mi_ilqr*, int, const mi::KArgs&);

@@ -2,4 +2,4 @@
 // family of ilqr_large.hpp): every (Jacobian mode, kernel mode) instantiation.
 #include "launch_large.hpp"
 
-MI_INTERNAL int launch_arm27c(mi_ilqr* h, int mode, const mi::KArgs& a) { return mi_host::launch_jac_large<mi::Arm27C>(h, mode, a); }
+template int mi_host::launch_jac_large<mi::Arm27C>(mi_ilqr*, int, const mi::KArgs&);

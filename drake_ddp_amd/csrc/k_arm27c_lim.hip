@@ -2,4 +2,4 @@
 // clamped rollouts): every (Jacobian mode, kernel mode) instantiation.
 #include "launch_large.hpp"
 
-MI_INTERNAL int launch_arm27c_lim(mi_ilqr* h, int mode, const mi::KArgs& a) { return mi_host::launch_jac_large_limited<mi::Arm27C>(h, mode, a); }
+template int mi_host::launch_jac_large_limited<mi::Arm27C>(mi_ilqr*, int, const mi::KArgs&);

@@ -37,61 +37,33 @@ struct HasPivSplit<M, decltype((void)M::kPivSplit)> { static constexpr bool valu
 template <class M>
 constexpr bool kPivSplit = HasPivSplit<M>::value;
 
-template <class M, int JAC>
-int launch_mode_large(mi_ilqr* h, int mode, const KArgs& a) {
-  if (a.pd_continue || a.cost_asym || !kPivSplit<M>) {
-    switch (mode) {
-      case MODE_SOLVE: return launch_one_large<M, JAC, MODE_SOLVE, true>(h, a);
-      case MODE_BACKWARD: return launch_one_large<M, JAC, MODE_BACKWARD, true>(h, a);
-      case MODE_MPC: return launch_one_large<M, JAC, MODE_MPC, true>(h, a);
-      default: break;
-    }
-  }
-  if constexpr (kPivSplit<M>) {
-    switch (mode) {
-      case MODE_SOLVE: return launch_one_large<M, JAC, MODE_SOLVE>(h, a);
-      case MODE_BACKWARD: return launch_one_large<M, JAC, MODE_BACKWARD>(h, a);
-      case MODE_MPC: return launch_one_large<M, JAC, MODE_MPC>(h, a);
-      default: break;
-    }
-  }
-  switch (mode) {
-    case MODE_ROLLOUT: return launch_one_large<M, JAC, MODE_ROLLOUT>(h, a);
-    case MODE_FORWARD: return launch_one_large<M, JAC, MODE_FORWARD>(h, a);
-    case MODE_LINEARIZE: return launch_one_large<M, JAC, MODE_LINEARIZE>(h, a);
-    default: break;
-  }
-  return MI_ILQR_E_BAD_ARG;
+template <class M, int JAC, bool PIV, int... MODES>
+int launch_large_modes(mi_ilqr* h, int mode, const KArgs& a) {
+  return with_mode<MODES...>(mode, [&](auto md) { return launch_one_large<M, JAC, decltype(md)::value, PIV>(h, a); });
 }
 
 template <class M>
 int launch_jac_large(mi_ilqr* h, int mode, const KArgs& a) {
-  if (h->d.jacobian_mode == MI_JAC_AUTODIFF) return launch_mode_large<M, MI_JAC_AUTODIFF>(h, mode, a);
-  return launch_mode_large<M, MI_JAC_FD_CENTRAL>(h, mode, a);
+  const bool backward = mode == MODE_SOLVE || mode == MODE_BACKWARD || mode == MODE_MPC;
+  const bool piv = a.pd_continue || a.cost_asym || !kPivSplit<M>;
+  return with_jac(h, [&](auto jac) {
+    constexpr int JAC = decltype(jac)::value;
+    if (backward && piv) return launch_large_modes<M, JAC, true, MODE_SOLVE, MODE_BACKWARD, MODE_MPC>(h, mode, a);
+    if constexpr (kPivSplit<M>) if (backward) return launch_large_modes<M, JAC, false, MODE_SOLVE, MODE_BACKWARD, MODE_MPC>(h, mode, a);
+    return launch_large_modes<M, JAC, false, MODE_ROLLOUT, MODE_FORWARD, MODE_LINEARIZE>(h, mode, a);
+  });
 }
 
 // Handles with control limits (mi_ilqr_set_control_limits; the mid-size family, n <= 32): the Limited<M> kernels - the clamped
 // rollouts and the box-QP backward pass (mid_backward_limited) - for every mode.  The backward pass has no pivoted-inverse path, so
 // there is one form (PIV = false).  Instantiated apart from launch_jac_large (k_<model>_lim.hip, the plugin units built with limits).
-template <class M, int JAC>
-int launch_mode_large_limited(mi_ilqr* h, int mode, const KArgs& a) {
-  static_assert(LLay<M::n, M::m>::kMid, "control limits: the mid-size family only");
-  switch (mode) {
-    case MODE_SOLVE: return launch_one_large<Limited<M>, JAC, MODE_SOLVE>(h, a);
-    case MODE_BACKWARD: return launch_one_large<Limited<M>, JAC, MODE_BACKWARD>(h, a);
-    case MODE_MPC: return launch_one_large<Limited<M>, JAC, MODE_MPC>(h, a);
-    case MODE_ROLLOUT: return launch_one_large<Limited<M>, JAC, MODE_ROLLOUT>(h, a);
-    case MODE_FORWARD: return launch_one_large<Limited<M>, JAC, MODE_FORWARD>(h, a);
-    case MODE_LINEARIZE: return launch_one_large<Limited<M>, JAC, MODE_LINEARIZE>(h, a);
-    default: break;
-  }
-  return MI_ILQR_E_BAD_ARG;
-}
-
 template <class M>
 int launch_jac_large_limited(mi_ilqr* h, int mode, const KArgs& a) {
-  if (h->d.jacobian_mode == MI_JAC_AUTODIFF) return launch_mode_large_limited<M, MI_JAC_AUTODIFF>(h, mode, a);
-  return launch_mode_large_limited<M, MI_JAC_FD_CENTRAL>(h, mode, a);
+  static_assert(LLay<M::n, M::m>::kMid, "control limits: the mid-size family only");
+  return with_jac(h, [&](auto jac) {
+    return launch_large_modes<Limited<M>, decltype(jac)::value, false, MODE_SOLVE, MODE_BACKWARD, MODE_MPC, MODE_ROLLOUT, MODE_FORWARD,
+                              MODE_LINEARIZE>(h, mode, a);
+  });
 }
 
 }  // namespace mi_host

@@ -13,55 +13,42 @@ int launch_one(mi_ilqr* h, const KArgs& a) {
   return launch_timed(h, kern, dim3(h->B), dim3(64 * waves), h->lds, a);
 }
 
-template <class M, int JAC>
-int launch_mode(mi_ilqr* h, int mode, const KArgs& a) {
-  switch (mode) {
-    case MODE_SOLVE: return launch_one<M, JAC, MODE_SOLVE>(h, a);
-    case MODE_ROLLOUT: return launch_one<M, JAC, MODE_ROLLOUT>(h, a);
-    case MODE_FORWARD: return launch_one<M, JAC, MODE_FORWARD>(h, a);
-    case MODE_LINEARIZE: return launch_one<M, JAC, MODE_LINEARIZE>(h, a);
-    case MODE_BACKWARD: return launch_one<M, JAC, MODE_BACKWARD>(h, a);
-    case MODE_MPC: return launch_one<M, JAC, MODE_MPC>(h, a);
-  }
-  return MI_ILQR_E_BAD_ARG;
+// every kernel mode, in the handle's Jacobian mode
+template <class M>
+int launch_modes(mi_ilqr* h, int mode, const KArgs& a) {
+  return with_jac(h, [&](auto jac) {
+    return with_any_mode(mode, [&](auto md) { return launch_one<M, decltype(jac)::value, decltype(md)::value>(h, a); });
+  });
+}
+
+// the modes that run a backward pass, for the model forms that only change that pass (ExactCost, LongHorizon): MODE_BACKWARD in its
+// central-difference form only
+template <class M>
+int launch_backward_forms(mi_ilqr* h, int mode, const KArgs& a) {
+  return with_mode<MODE_SOLVE, MODE_MPC, MODE_BACKWARD>(mode, [&](auto md) {
+    constexpr int MODE = decltype(md)::value;
+    if constexpr (MODE == MODE_BACKWARD) return launch_one<M, MI_JAC_FD_CENTRAL, MODE>(h, a);
+    else return with_jac(h, [&](auto jac) { return launch_one<M, decltype(jac)::value, MODE>(h, a); });
+  });
 }
 
 template <class M>
 int launch_jac(mi_ilqr* h, int mode, const KArgs& a) {
   if constexpr (M::n >= 3 && M::n <= 4 && M::m == 1) {
-    // cost matrices outside the symmetric-PSD class: the kernels whose backward pass is the reference's recursion
-    if (h->exact_backward && (mode == MODE_SOLVE || mode == MODE_MPC || mode == MODE_BACKWARD)) {
-      using E = ExactCost<M>;
-      const bool ad = h->d.jacobian_mode == MI_JAC_AUTODIFF;
-      switch (mode) {
-        case MODE_SOLVE: return ad ? launch_one<E, MI_JAC_AUTODIFF, MODE_SOLVE>(h, a) : launch_one<E, MI_JAC_FD_CENTRAL, MODE_SOLVE>(h, a);
-        case MODE_MPC: return ad ? launch_one<E, MI_JAC_AUTODIFF, MODE_MPC>(h, a) : launch_one<E, MI_JAC_FD_CENTRAL, MODE_MPC>(h, a);
-        default: return launch_one<E, MI_JAC_FD_CENTRAL, MODE_BACKWARD>(h, a);
-      }
-    }
-    // two or more steps per lane: the kernels whose backward pass is the time-parallel scan (ilqr_small.hpp:
-    // LongHorizon) - only the modes that run a backward pass have such an instantiation
-    if (h->N > 128 && (mode == MODE_SOLVE || mode == MODE_MPC || mode == MODE_BACKWARD)) {
-      using L = LongHorizon<M>;
-      const bool ad = h->d.jacobian_mode == MI_JAC_AUTODIFF;
-      switch (mode) {
-        case MODE_SOLVE: return ad ? launch_one<L, MI_JAC_AUTODIFF, MODE_SOLVE>(h, a) : launch_one<L, MI_JAC_FD_CENTRAL, MODE_SOLVE>(h, a);
-        case MODE_MPC: return ad ? launch_one<L, MI_JAC_AUTODIFF, MODE_MPC>(h, a) : launch_one<L, MI_JAC_FD_CENTRAL, MODE_MPC>(h, a);
-        default: return launch_one<L, MI_JAC_FD_CENTRAL, MODE_BACKWARD>(h, a);
-      }
+    if (mode == MODE_SOLVE || mode == MODE_MPC || mode == MODE_BACKWARD) {
+      // cost matrices outside the symmetric-PSD class: the kernels whose backward pass is the reference's recursion
+      if (h->exact_backward) return launch_backward_forms<ExactCost<M>>(h, mode, a);
+      // two or more steps per lane: the kernels whose backward pass is the time-parallel scan (ilqr_small.hpp: LongHorizon)
+      if (h->N > 128) return launch_backward_forms<LongHorizon<M>>(h, mode, a);
     }
   }
-  if (h->d.jacobian_mode == MI_JAC_AUTODIFF) return launch_mode<M, MI_JAC_AUTODIFF>(h, mode, a);
-  return launch_mode<M, MI_JAC_FD_CENTRAL>(h, mode, a);
+  return launch_modes<M>(h, mode, a);
 }
 
 // Handles with control limits (mi_ilqr_set_control_limits): the Limited<M> kernels - sequential rollout with the clamp, the
 // box-QP backward pass - for every mode.  Instantiated apart from launch_jac (k_<model>_lim.hip, the plugin units) so that
 // the parallel build keeps its shape.
 template <class M>
-int launch_limited(mi_ilqr* h, int mode, const KArgs& a) {
-  if (h->d.jacobian_mode == MI_JAC_AUTODIFF) return launch_mode<Limited<M>, MI_JAC_AUTODIFF>(h, mode, a);
-  return launch_mode<Limited<M>, MI_JAC_FD_CENTRAL>(h, mode, a);
-}
+int launch_limited(mi_ilqr* h, int mode, const KArgs& a) { return launch_modes<Limited<M>>(h, mode, a); }
 
 }  // namespace mi_host

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -36,69 +37,101 @@ using namespace mi_host;
 namespace {
 
 
-struct ModelInfo { int n, m, n_params; double defaults[MI_ILQR_MAX_PARAMS]; };
+// One record per model id: the plugin record (n, m, parameters and their defaults, family, LDS bytes, launch entry) - filled in
+// below for the built-in models, by mi_ilqr_register_model for those registered at run time - and the clustering policy.
+struct Model {
+  mi_ilqr_model_plugin p;
+  // Workgroup-per-problem launches of batches up to this size share their linearizations in clusters (cluster_size): the models
+  // whose linearization is worth a handshake (round 5: ~20 k cycles - six memory round trips - since the cache-wide write-backs are
+  // gone; with the helpers linearizing the line search's first trial WHILE it is rolled out - early linearization, ilqr_large.hpp -
+  // the stage shrinks to the wait for the last block: 36-state chain 74 k -> 12 k cycles at B = 64, 3-D quadruped 92 k -> 30 k,
+  // planar quadruped 164 k -> 132 k (its helpers cannot keep up with the rollout)).  The arm + ball's dense linearization (100 k
+  // single) up to B = 64; plugin models: the library cannot know what their step costs - a cheap one loses to the handshake, so
+  // they are not clustered unless forced (0).
+  int cluster_max_B;
+};
+constexpr int kAnyB = 1 << 30;
+
+template <int n, int m>
+size_t wave_lds(int32_t N, int32_t n_store) { return ws_bytes<n, m>(N, n_store); }
+template <int n, int m>   // (n_store < 0: the cost gradients in HBM, long horizons)
+size_t workgroup_lds(int32_t N, int32_t n_store) { return n_store < 0 ? large_lds_bytes_hbm<n, m>(N) : large_lds_bytes<n, m>(N); }
+
+template <class M>
+Model builtin(int family, size_t (*lds)(int32_t, int32_t), int (*launch)(mi_ilqr*, int, const void*), int cluster_max_B,
+              std::initializer_list<double> defaults) {
+  Model r{};
+  r.p.n = M::n; r.p.m = M::m; r.p.n_params = M::n_params; r.p.family = family;
+  std::copy(defaults.begin(), defaults.end(), r.p.default_params);
+  r.p.lds_bytes = lds; r.p.launch = launch;
+  r.cluster_max_B = cluster_max_B;
+  return r;
+}
+// wave-per-problem kernels (k_<model>.hip, k_<model>_lim.hip) and the lane-per-problem ones (k_batch.hip, k_batch_lim.hip)
+template <class M>
+Model wave_model(std::initializer_list<double> defaults) {
+  return builtin<M>(0, wave_lds<M::n, M::m>,
+                    launch_entry<launch_jac<M>, launch_limited<M>, launch_batch<M>, launch_batch_limited<M>>, 0, defaults);
+}
+// workgroup-per-problem kernels (k_<model>.hip; with control limits, k_<model>_lim.hip)
+template <class M, Launcher LIMITED = nullptr>
+Model workgroup_model(int cluster_max_B, std::initializer_list<double> defaults) {
+  return builtin<M>(1, workgroup_lds<M::n, M::m>, launch_entry<launch_jac_large<M>, LIMITED>, cluster_max_B, defaults);
+}
+
+const Model kBuiltins[] = {
+    wave_model<Pendulum>({0.25, 0.1, 4.905}),                                                        // MI_MODEL_PENDULUM
+    wave_model<Acrobot>({1.0, 1.0, 1.0, 0.5, 1.0, 0.083, 0.33, 0.1, 0.1, 9.81}),                     // MI_MODEL_ACROBOT
+    wave_model<CartPole>({10.0, 1.0, 0.5, 9.81}),                                                    // MI_MODEL_CARTPOLE
+    wave_model<CartPoleWall>({10.0, 1.0, 0.5, 9.81, -0.45, 0.05, 2000.0, 0.01}),                     // MI_MODEL_CARTPOLE_WALL
+    workgroup_model<Synth36>(64, {4.0, 0.5, 6.0, 0.1}),                                              // MI_MODEL_SYNTH36
+    workgroup_model<PlanarQuad>(kAnyB, {9.81, 4000.0, 0.004, 0.3, 0.15, 0.05, 0.02, 2.0, 60.0}),     // MI_MODEL_PLANAR_QUAD
+    workgroup_model<Quad3D>(kAnyB, {9.81, 4000.0, 0.004, 0.3, 0.15, 0.3, 60.0, 9.0, 0.07, 0.26, 0.28, 0.06, 0.06, 0.04}),  // MI_MODEL_QUAD3D
+    workgroup_model<Arm27, launch_jac_large_limited<Arm27>>(
+        64, {9.81, 1500.0, 0.005, 0.5, 1.0, 0.5, 0.2, 0.1, 0.05, 1.0, 0.8, 0.6, 0.3, 0.1, 0.04}),    // MI_MODEL_ARM27
+    workgroup_model<Arm27C, launch_jac_large_limited<Arm27C>>(
+        64, {9.81, 1500.0, 0.005, 0.5, 1.0, 0.5, 0.2, 0.1, 0.05, 1.0, 0.8, 0.3, 0.15, 0.05, 0.04, 0.6}),  // MI_MODEL_ARM27C
+};
+constexpr int kNumBuiltins = sizeof(kBuiltins) / sizeof(kBuiltins[0]);
+static_assert(kNumBuiltins == MI_MODEL_ARM27C + 1, "one row per built-in model id, in id order");
 
 // models registered at run time (mi_ilqr_register_model): id = MI_MODEL_PLUGIN_BASE + slot
 // Registrations take the mutex; a slot is filled once and read lock-free afterwards: `used` is published LAST with release
 // ordering and read with acquire ordering, so a thread that sees it set also sees the slot's contents (a create or a launch on
 // one thread may race a registration on another).
-struct PluginSlot { ModelInfo info; mi_ilqr_model_plugin p; std::atomic<bool> used{false}; };
+struct PluginSlot { Model model; std::atomic<bool> used{false}; };
 PluginSlot g_plugins[MI_ILQR_MAX_PLUGINS];
 std::mutex g_plugins_mutex;
-const PluginSlot* plugin_of(int id) {
+
+const Model* model_of(int id) {
+  if (id >= 0 && id < kNumBuiltins) return &kBuiltins[id];
   const int s_ = id - MI_MODEL_PLUGIN_BASE;
-  return (s_ >= 0 && s_ < MI_ILQR_MAX_PLUGINS && g_plugins[s_].used.load(std::memory_order_acquire)) ? &g_plugins[s_] : nullptr;
+  return (s_ >= 0 && s_ < MI_ILQR_MAX_PLUGINS && g_plugins[s_].used.load(std::memory_order_acquire)) ? &g_plugins[s_].model : nullptr;
 }
 
-const ModelInfo* model_info(int id) {
-  if (const PluginSlot* ps = plugin_of(id)) return &ps->info;
-  static const ModelInfo table[] = {
-      {2, 1, 3, {0.25, 0.1, 4.905}},
-      {4, 1, 10, {1.0, 1.0, 1.0, 0.5, 1.0, 0.083, 0.33, 0.1, 0.1, 9.81}},
-      {4, 1, 4, {10.0, 1.0, 0.5, 9.81}},
-      {4, 1, 8, {10.0, 1.0, 0.5, 9.81, -0.45, 0.05, 2000.0, 0.01}},
-      {36, 12, 4, {4.0, 0.5, 6.0, 0.1}},
-      {36, 12, 9, {9.81, 4000.0, 0.004, 0.3, 0.15, 0.05, 0.02, 2.0, 60.0}},
-      {37, 12, 14, {9.81, 4000.0, 0.004, 0.3, 0.15, 0.3, 60.0, 9.0, 0.07, 0.26, 0.28, 0.06, 0.06, 0.04}},
-      {27, 7, 15, {9.81, 1500.0, 0.005, 0.5, 1.0, 0.5, 0.2, 0.1, 0.05, 1.0, 0.8, 0.6, 0.3, 0.1, 0.04}},
-      {27, 7, 16, {9.81, 1500.0, 0.005, 0.5, 1.0, 0.5, 0.2, 0.1, 0.05, 1.0, 0.8, 0.3, 0.15, 0.05, 0.04, 0.6}},
-  };
-  if (id < 0 || id > 8) return nullptr;
-  return &table[id];
-}
+// every step is a key-point (ilqr.py:417-432): the linearization covers the whole horizon
+bool every_step_keypoint(const mi_ilqr_desc& d) { return d.keypoint_method == MI_KP_SET_INTERVAL && d.minN == 1; }
 
-size_t small_lds_bytes(int model_id, int N, int n_store = 1) {
-  if (const PluginSlot* ps = plugin_of(model_id)) return ps->p.family == 0 ? ps->p.lds_bytes(N, n_store) : 0;
-  switch (model_id) {
-    case MI_MODEL_PENDULUM: return ws_bytes<2, 1>(N, n_store);
-    case MI_MODEL_ACROBOT:
-    case MI_MODEL_CARTPOLE:
-    case MI_MODEL_CARTPOLE_WALL: return ws_bytes<4, 1>(N, n_store);
-    default: return 0;
-  }
-}
-
-size_t large_lds(int model_id, int N) {
-  if (const PluginSlot* ps = plugin_of(model_id)) return ps->p.family == 1 ? ps->p.lds_bytes(N, 1) : 0;
-  switch (model_id) {
-    case MI_MODEL_SYNTH36: return large_lds_bytes<Synth36::n, Synth36::m>(N);
-    case MI_MODEL_PLANAR_QUAD: return large_lds_bytes<PlanarQuad::n, PlanarQuad::m>(N);
-    case MI_MODEL_QUAD3D: return large_lds_bytes<Quad3D::n, Quad3D::m>(N);
-    case MI_MODEL_ARM27: case MI_MODEL_ARM27C: return large_lds_bytes<Arm27::n, Arm27::m>(N);
-    default: return 0;
-  }
-}
-
-// LDS of the workgroup-per-problem kernels with the cost gradients in HBM (long horizons)
-size_t large_lds_hbm(int model_id, int N) {
-  if (const PluginSlot* ps = plugin_of(model_id)) return ps->p.family == 1 ? ps->p.lds_bytes(N, -1) : 0;
-  switch (model_id) {
-    case MI_MODEL_SYNTH36: return large_lds_bytes_hbm<Synth36::n, Synth36::m>(N);
-    case MI_MODEL_PLANAR_QUAD: return large_lds_bytes_hbm<PlanarQuad::n, PlanarQuad::m>(N);
-    case MI_MODEL_QUAD3D: return large_lds_bytes_hbm<Quad3D::n, Quad3D::m>(N);
-    case MI_MODEL_ARM27: case MI_MODEL_ARM27C: return large_lds_bytes_hbm<Arm27::n, Arm27::m>(N);
-    default: return 0;
-  }
+// Workgroups per problem of a workgroup-per-problem launch: with few problems per GPU most CUs idle - up to 8 workgroups per
+// problem share the linearization (ilqr_large.hpp: cluster handshake), as many as keep every workgroup of the launch on its own
+// CU.  MI_ILQR_CLUSTER=k forces k (1 = off) for A/B runs.  make_args launches with it; mi_ilqr_create sizes the trial buffers
+// (spec_slots) for it.
+int cluster_size(const mi_ilqr* h) {
+  if (!every_step_keypoint(h->d)) return 1;
+  const int forced = switches().cluster;
+  if (forced > 0) return std::min(forced, 8);
+  if (h->B > model_of(h->d.model_id)->cluster_max_B) return 1;
+  // Forward-mode duals (a parity / testing mode - the benchmarked path is central differences) are not clustered unless forced.
+  // Round 5: the helper path of ilqr_large_kernel<PlanarQuad, JAC = 1, MODE_SOLVE> faulted (HSA memory aperture violation in a
+  // flat load of the item loop of large_jac_at_tree) after two unrelated edits inside large_backward, each alone enough, and
+  // stopped faulting with a bounds check added next to it.  Under rocgdb the faulting helper wavefront sits at the top of the item
+  // loop with an EXEC mask that is no prefix of the lanes (0x316eaa6bf7995fc5) and garbage in the lanes' time index - a state no
+  // path of the source produces (the loop's lanes leave in order); the spilled scalars it restores there (361 - 932 SGPRs of these
+  // kernels live in VGPR lanes) were written correctly at kernel start.  Root cause not established beyond that - it points at
+  // the compiler's handling of this kernel's spills, not at the handshake - so the instantiation is kept off the default path
+  // and the full GPU suite stays the safety net for the clustered central-difference kernels, which every bench config runs.
+  if (h->d.jacobian_mode == MI_JAC_AUTODIFF) return 1;
+  return std::clamp(h->n_cus > 0 ? h->n_cus / h->B : 1, 1, 8);
 }
 
 KArgs make_args(const mi_ilqr* h) {
@@ -125,25 +158,20 @@ KArgs make_args(const mi_ilqr* h) {
   // wave of the kernel carries the main wave's register allocation (> 256 VGPRs with the time-parallel
   // rollout and sweep), so a second resident wave per SIMD does not fit and extra waves would queue.
   // MI_ILQR_NO_HELPER=1 turns them off (A/B measurements).
-  static const bool no_helper = [] { const char* e = std::getenv("MI_ILQR_NO_HELPER"); return e && e[0] == '1'; }();
-  static const bool seq_bp = [] { const char* e = std::getenv("MI_ILQR_SEQ_BACKWARD"); return e && e[0] == '1'; }();
-  a.seq_backward = h->exact_backward ? 2 : (seq_bp ? 1 : 0);
-  static const bool seq_ro = [] { const char* e = std::getenv("MI_ILQR_SEQ_ROLLOUT"); return e && e[0] == '1'; }();
-  a.newton_rollout = seq_ro ? 0 : 1;
+  const Switches& sw = switches();
+  a.seq_backward = h->exact_backward ? 2 : (sw.seq_backward ? 1 : 0);
+  a.newton_rollout = sw.seq_rollout ? 0 : 1;
   // (not for n = 2 with the time-parallel rollout: its final pass differentiates the steps it holds in registers,
   //  which beats sharing them - C2's batch at B = 512: 0.141 ms without helpers, 0.149 ms with one; tools/helper_ab.py)
   const bool fused_linearization = h->n == 2 && h->m == 1 && h->N - 1 <= 256 && a.newton_rollout != 0;
   a.helpers = 0;
-  if (!no_helper && !h->large && !h->batch_minor && h->d.keypoint_method == MI_KP_SET_INTERVAL && h->d.minN == 1 &&
+  if (!sw.no_helper && !h->large && !h->batch_minor && every_step_keypoint(h->d) &&
       (h->N - 1) * (h->n + h->m) > 128 && !fused_linearization)
     a.helpers = h->B <= 256 ? 3 : (h->B <= 512 ? 1 : 0);
   // wave-per-problem kernels aggregate the batch statistics themselves (MODE_SOLVE / MODE_MPC)
   const bool own_stats = stats_in_kernel(h);
   a.stats_out = own_stats ? h->d_stats : nullptr;
   a.done_counter = own_stats ? h->done_counter : nullptr;
-  // workgroup-per-problem kernels: with few problems per GPU most CUs idle - up to 8 workgroups per problem share the
-  // linearization (ilqr_large.hpp: cluster handshake), as many as keep every workgroup of the launch on its own CU.
-  // MI_ILQR_CLUSTER=k forces k (1 = off) for A/B runs.
   a.sink_x = h->sink_x; a.sink_u = h->sink_u; a.sink_cost = h->sink_cost;
   a.bm_scratch = h->bm_scratch;
   a.x_spec = h->x_spec; a.u_spec = h->u_spec;
@@ -155,59 +183,29 @@ KArgs make_args(const mi_ilqr* h) {
   a.s2 = h->s2;
   a.x_nom_rows = h->per_problem_targets ? h->x_nom_rows : nullptr;
   a.target_steps = h->per_problem_targets ? h->target_steps : nullptr;
-  static const int spec = [] { const char* e = std::getenv("MI_ILQR_SPEC"); return e ? std::atoi(e) : 1; }();
-  a.spec_policy = (h->x_spec && spec >= 0 && spec <= 2) ? spec : 0;
+  a.spec_policy = h->x_spec ? sw.spec : 0;
   a.cluster = 1;
   a.cluster_sync = h->cluster_sync;
+  // workgroup-per-problem kernels: clusters (cluster_size)
   // (limited handles: one workgroup per problem - no clusters, hence no early linearization or candidate groups either)
-  if (h->large && h->cluster_sync && !h->limited && h->d.keypoint_method == MI_KP_SET_INTERVAL && h->d.minN == 1) {
-    static const int forced = [] { const char* e = std::getenv("MI_ILQR_CLUSTER"); return e ? std::atoi(e) : 0; }();
-    int g = forced > 0 ? forced : (h->n_cus > 0 ? h->n_cus / h->B : 1);
-    // Which models: those whose linearization is worth a handshake (round 5: ~20 k cycles - six memory round trips - since the
-    // cache-wide write-backs are gone; with the helpers linearizing the line search's first trial WHILE it is rolled out - early
-    // linearization, ilqr_large.hpp - the stage shrinks to the wait for the last block: 36-state chain 74 k -> 12 k cycles at
-    // B = 64, 3-D quadruped 92 k -> 30 k, planar quadruped 164 k -> 132 k (its helpers cannot keep up with the rollout)).  The arm
-    // + ball's dense linearization (100 k single) up to B = 64; plugin models: the library cannot know what their step costs - a
-    // cheap one loses to the handshake, so they are not clustered unless forced.
-    if (forced <= 0) {
-      const int id = h->d.model_id;
-      if (id == MI_MODEL_PLANAR_QUAD || id == MI_MODEL_QUAD3D) {}
-      else if (id == MI_MODEL_ARM27 || id == MI_MODEL_ARM27C || id == MI_MODEL_SYNTH36) { if (h->B > 64) g = 1; }
-      else if (plugin_of(id)) g = 1;
-      else if (h->B > 16) g = 1;
-    }
-    // Forward-mode duals (a parity / testing mode - the benchmarked path is central differences) are not clustered unless forced.
-    // Round 5: the helper path of ilqr_large_kernel<PlanarQuad, JAC = 1, MODE_SOLVE> faulted (HSA memory aperture violation in a
-    // flat load of the item loop of large_jac_at_tree) after two unrelated edits inside large_backward, each alone enough, and
-    // stopped faulting with a bounds check added next to it.  Under rocgdb the faulting helper wavefront sits at the top of the item
-    // loop with an EXEC mask that is no prefix of the lanes (0x316eaa6bf7995fc5) and garbage in the lanes' time index - a state no
-    // path of the source produces (the loop's lanes leave in order); the spilled scalars it restores there (361 - 932 SGPRs of these
-    // kernels live in VGPR lanes) were written correctly at kernel start.  Root cause not established beyond that - it points at
-    // the compiler's handling of this kernel's spills, not at the handshake - so the instantiation is kept off the default path
-    // and the full GPU suite stays the safety net for the clustered central-difference kernels, which every bench config runs.
-    if (forced <= 0 && h->d.jacobian_mode == MI_JAC_AUTODIFF) g = 1;
-    if (g > 8) g = 8;
-    if (g < 1) g = 1;
+  if (h->large && h->cluster_sync && !h->limited && every_step_keypoint(h->d)) {
+    const int g = cluster_size(h);
     // placement (MI_ILQR_CLUSTER_ORDER, A/B runs): 2 = a cluster on ONE XCD, the XCD's leaders in its first slots (default: measured
     // best or level for every model once early linearization is on); 1 = one XCD, members in consecutive slots (the quadrupeds'
     // helpers run 40 - 70 % slower next to leaders: neighbouring CUs share an instruction cache, and their linearization loops are
     // 50 - 90 KB of code); 0 = consecutive blocks, a cluster spans XCDs (what rounds 2 - 4 did; no early linearization there)
-    static const int order = [] { const char* e = std::getenv("MI_ILQR_CLUSTER_ORDER"); return e ? std::atoi(e) : 2; }();
     // Early linearization (MI_ILQR_EARLY=0|1): every model, built-in or plugin (round 6).  Round 5 opened it for the built-in models
     // only: forced onto plugin chains with steps of a few hundred cycles the helpers linearized rows of the previous trial.  The cause
     // was not the progress word's lag but the helpers' side of the hand-shake - `buffer_inv sc0` does not drop another CU's lines
     // from the vector L1 (tools/ubench/l1_probe.hip), and a small trajectory survives there from one iteration to the next; the
     // helpers now read the trial with agent-scope loads and the progress word follows a full drain (ilqr_large.hpp).
-    static const int early_env = [] { const char* e = std::getenv("MI_ILQR_EARLY"); return e ? std::atoi(e) : 1; }();
-    const int early = early_env;
     // candidate groups (MI_ILQR_LS_GROUPS=0|1): the helpers need trial buffers of their own, and - they keep their own LDS copy of
     // the cost constants - a target that does not move inside the launch
-    static const int groups = [] { const char* e = std::getenv("MI_ILQR_LS_GROUPS"); return e ? std::atoi(e) : 1; }();
     bool still = true;
     for (int i = 0; i < h->n; ++i) still = still && h->mpc_target_step[i] == 0.0;
     if (h->per_problem_targets && h->target_steps_moving) still = false;
-    const bool lsg = groups && still && h->spec_slots >= 4 * g - 1 && g > 1;
-    a.cluster = g | ((order & 3) << 8) | ((early ? 1 : 0) << 10) | ((lsg ? 1 : 0) << 11);
+    const bool lsg = sw.ls_groups && still && h->spec_slots >= 4 * g - 1 && g > 1;
+    a.cluster = g | ((sw.cluster_order & 3) << 8) | ((sw.early ? 1 : 0) << 10) | ((lsg ? 1 : 0) << 11);
   }
   return a;
 }
@@ -223,37 +221,7 @@ int launch(mi_ilqr* h, int mode) {
   if (h->u_zero && !h->u_pending) HIPCHK(hipMemsetAsync(h->u_bar, 0, (size_t)h->B * h->m * (h->N - 1) * 8, h->stream));
   h->u_zero = false;
   const KArgs a = make_args(h);
-  int rc;
-  if (h->batch_minor) {
-    if (const PluginSlot* ps = plugin_of(h->d.model_id)) return ps->p.launch(h, mode, &a);   // (family-0 plugins carry the lane-per-problem kernels too)
-    return h->limited ? launch_batch_minor_lim(h, mode, a) : launch_batch_minor(h, mode, a);
-  }
-  if (h->limited) {                                // (plugins pick their Limited<M> kernels in their own launch entry)
-    switch (h->d.model_id) {
-      case MI_MODEL_PENDULUM: return launch_pendulum_lim(h, mode, a);
-      case MI_MODEL_ACROBOT: return launch_acrobot_lim(h, mode, a);
-      case MI_MODEL_CARTPOLE: return launch_cartpole_lim(h, mode, a);
-      case MI_MODEL_CARTPOLE_WALL: return launch_cartpole_wall_lim(h, mode, a);
-      case MI_MODEL_ARM27: return launch_arm27_lim(h, mode, a);
-      case MI_MODEL_ARM27C: return launch_arm27c_lim(h, mode, a);
-      default: break;
-    }
-  }
-  switch (h->d.model_id) {
-    case MI_MODEL_PENDULUM: rc = launch_pendulum(h, mode, a); break;
-    case MI_MODEL_ACROBOT: rc = launch_acrobot(h, mode, a); break;
-    case MI_MODEL_CARTPOLE: rc = launch_cartpole(h, mode, a); break;
-    case MI_MODEL_CARTPOLE_WALL: rc = launch_cartpole_wall(h, mode, a); break;
-    case MI_MODEL_SYNTH36: rc = launch_synth36(h, mode, a); break;
-    case MI_MODEL_PLANAR_QUAD: rc = launch_planar_quad(h, mode, a); break;
-    case MI_MODEL_QUAD3D: rc = launch_quad3d(h, mode, a); break;
-    case MI_MODEL_ARM27: rc = launch_arm27(h, mode, a); break;
-    case MI_MODEL_ARM27C: rc = launch_arm27c(h, mode, a); break;
-    default:
-      if (const PluginSlot* ps = plugin_of(h->d.model_id)) { rc = ps->p.launch(h, mode, &a); break; }
-      return MI_ILQR_E_UNSUPPORTED;
-  }
-  return rc;
+  return model_of(h->d.model_id)->p.launch(h, mode, &a);
 }
 
 // When the state is lazily-zero (cold) but a kernel is about to write only part
@@ -592,13 +560,11 @@ int mi_ilqr_register_model(const mi_ilqr_model_plugin* p, int32_t* model_id_out)
   // (mid_backward), 32 < n <= 40 with m % 4 == 0 and 2 m <= n (large_backward's wave roles)
   if (p->family == 0 ? p->m > 2
                      : (p->family != 1 || p->m > 16 || (p->n > 32 && (2 * p->m > p->n || p->m % 4 != 0)))) return MI_ILQR_E_UNSUPPORTED;
-  std::lock_guard<std::mutex> lock(g_plugins_mutex);                     // (readers: plugin_of, lock-free)
+  std::lock_guard<std::mutex> lock(g_plugins_mutex);                     // (readers: model_of, lock-free)
   for (int s_ = 0; s_ < MI_ILQR_MAX_PLUGINS; ++s_) {
     if (g_plugins[s_].used.load(std::memory_order_relaxed)) continue;
     PluginSlot& ps = g_plugins[s_];
-    ps.p = *p;
-    ps.info.n = p->n; ps.info.m = p->m; ps.info.n_params = p->n_params;
-    for (int i = 0; i < MI_ILQR_MAX_PARAMS; ++i) ps.info.defaults[i] = p->default_params[i];
+    ps.model = Model{*p, 0};
     ps.used.store(true, std::memory_order_release);
     *model_id_out = MI_MODEL_PLUGIN_BASE + s_;
     return MI_ILQR_OK;
@@ -607,29 +573,30 @@ int mi_ilqr_register_model(const mi_ilqr_model_plugin* p, int32_t* model_id_out)
 }
 
 int mi_ilqr_model_info(int model_id, int32_t* n, int32_t* m, int32_t* n_params, double* default_params) {
-  const ModelInfo* mi_ = model_info(model_id);
-  if (!mi_) return MI_ILQR_E_BAD_ARG;
-  if (n) *n = mi_->n;
-  if (m) *m = mi_->m;
-  if (n_params) *n_params = mi_->n_params;
-  if (default_params) for (int i = 0; i < MI_ILQR_MAX_PARAMS; ++i) default_params[i] = i < mi_->n_params ? mi_->defaults[i] : 0.0;
+  const Model* mod = model_of(model_id);
+  if (!mod) return MI_ILQR_E_BAD_ARG;
+  const mi_ilqr_model_plugin& p = mod->p;
+  if (n) *n = p.n;
+  if (m) *m = p.m;
+  if (n_params) *n_params = p.n_params;
+  if (default_params) for (int i = 0; i < MI_ILQR_MAX_PARAMS; ++i) default_params[i] = i < p.n_params ? p.default_params[i] : 0.0;
   return MI_ILQR_OK;
 }
 
 double mi_ilqr_bytes_per_iteration(int32_t n, int32_t m, int32_t N, int32_t ls) { return bytes_per_iteration(n, m, N, ls); }
 
 size_t mi_ilqr_lds_bytes(const mi_ilqr_desc* d) {
-  if (!d) return 0;
-  const size_t s_ = small_lds_bytes(d->model_id, d->N);
-  return s_ ? s_ : large_lds(d->model_id, d->N);
+  const Model* mod = d ? model_of(d->model_id) : nullptr;
+  return mod ? mod->p.lds_bytes(d->N, 1) : 0;
 }
 
 int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   if (!desc || !out) return MI_ILQR_E_BAD_ARG;
   *out = nullptr;
-  const ModelInfo* info = model_info(desc->model_id);
-  if (!info) return MI_ILQR_E_BAD_ARG;
-  if (desc->n != info->n || desc->m != info->m) return MI_ILQR_E_BAD_SHAPE;
+  const Model* mod = model_of(desc->model_id);
+  if (!mod) return MI_ILQR_E_BAD_ARG;
+  const mi_ilqr_model_plugin& model = mod->p;
+  if (desc->n != model.n || desc->m != model.m) return MI_ILQR_E_BAD_SHAPE;
   if (desc->N < 2 || desc->B < 1) return MI_ILQR_E_BAD_SHAPE;
   if (desc->keypoint_method < MI_KP_SET_INTERVAL || desc->keypoint_method > MI_KP_ITERATIVE_ERROR) return MI_ILQR_E_BAD_METHOD;
   if (desc->minN < 1) return MI_ILQR_E_BAD_ARG;
@@ -644,24 +611,22 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   if (desc->device_id < 0 || desc->device_id >= ndev) return MI_ILQR_E_NO_DEVICE;
   HIPCHK(hipSetDevice(desc->device_id));
 
-  size_t lds = small_lds_bytes(desc->model_id, desc->N);
-  bool large = false;
+  const bool large = model.family == 1;
+  size_t lds = model.lds_bytes(desc->N, 1);
   int n_store = 1;
-  if (lds == 0) { lds = large_lds(desc->model_id, desc->N); large = true; }
   if (lds == 0) return MI_ILQR_E_UNSUPPORTED;
   bool batch_minor = false;
   if (desc->kernel_mode < MI_KERNEL_AUTO || desc->kernel_mode > MI_KERNEL_THROUGHPUT) return MI_ILQR_E_BAD_ARG;
   if (desc->on_indefinite != 0 && desc->on_indefinite != 1) return MI_ILQR_E_BAD_ARG;
   {
     // (every key-point configuration since round 4: the KP instantiation of the lane-per-problem kernels)
-    // plugin models: family 0 with n <= 6 (their units instantiate the lane-per-problem kernels as well - per-lane register
-    // arrays of n x n doubles set the limit)
-    const PluginSlot* const plug = plugin_of(desc->model_id);
-    const bool can = !large && (!plug || (plug->p.family == 0 && plug->p.n <= kMaxBatchPluginN));
+    // family 0 with n <= 6: the models whose units instantiate the lane-per-problem kernels as well (every built-in one; per-lane
+    // register arrays of n x n doubles set the limit)
+    const bool can = model.family == 0 && model.n <= kMaxBatchPluginN;
     if (desc->kernel_mode == MI_KERNEL_THROUGHPUT && !can) return MI_ILQR_E_UNSUPPORTED;
     // n = 2 within the time-parallel passes' horizon: the wave-per-problem kernel is the faster one at
     // every batch size (B = 65536: 68 M vs 42 M it/s, profiles/r01n_c2_modes_batch_sweep.txt)
-    const bool time_parallel = info->n == 2 && info->m == 1 && desc->N - 1 <= 256;
+    const bool time_parallel = model.n == 2 && model.m == 1 && desc->N - 1 <= 256;
     batch_minor = can && (desc->kernel_mode == MI_KERNEL_THROUGHPUT ||
                           (desc->kernel_mode == MI_KERNEL_AUTO && desc->B >= 8192 && !time_parallel));
     // horizons whose per-problem state exceeds the 160 KB of LDS (e.g. acrobot.py's literal N = 750) are
@@ -671,7 +636,7 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   bool lxu_hbm = false;
   if (!batch_minor && lds > kMaxLds && large) {
     // the horizon's cost gradients do not fit beside the fixed block: keep them in HBM (ilqr_large.hpp: large_lds_bytes_hbm)
-    const size_t l = large_lds_hbm(desc->model_id, desc->N);
+    const size_t l = model.lds_bytes(desc->N, -1);
     if (l != 0 && l <= kMaxLds) { lds = l; lxu_hbm = true; }
   }
   if (!batch_minor && lds > kMaxLds) return MI_ILQR_E_UNSUPPORTED;
@@ -682,7 +647,7 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
     // batch needs (256 CUs) — it removes the second rollout of a backtracking iteration.
     const size_t per_cu_needed = ((size_t)desc->B + 255) / 256;
     for (int ns = 6; ns > 1; --ns) {
-      const size_t l = small_lds_bytes(desc->model_id, desc->N, ns);
+      const size_t l = model.lds_bytes(desc->N, ns);
       if (l <= kMaxLds && kMaxLds / l >= per_cu_needed) { n_store = ns; lds = l; break; }
     }
   }
@@ -697,6 +662,10 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   h->large = large;
   h->n_store = n_store;
   h->batch_minor = batch_minor;
+  {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, desc->device_id) == hipSuccess) h->n_cus = cus;
+  }
   const size_t n = h->n, m = h->m, N = h->N, B = h->B;
 
 #define ALLOC(p, count, T)                                             \
@@ -760,19 +729,11 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
     // trial buffers simply searches one candidate at a time (make_args: spec_policy = 0 without them)
     // (batches small enough for clusters: 31 slots - the candidates 1 .. 31 of a first pass that the leader and up to seven helper
     //  workgroups roll out together, ilqr_large.hpp: candidate groups)
-    // ... as many as the cluster size make_args will pick asks for: 4 g - 1 (15 at B = 64 on 256 CUs), 3 when the launch will not be
-    // clustered - plugin models unless MI_ILQR_CLUSTER forces it, batches beyond 64, fewer than two CUs per problem.  (Round 5
-    // allocated 31 for every batch up to 64: 1 GB of HBM for nothing on an n = 32, N = 2000 plugin.)
-    {
-      int cus = 0;
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, desc->device_id);
-      const char* fe = std::getenv("MI_ILQR_CLUSTER");
-      const int forced = fe ? std::atoi(fe) : 0;
-      int g = forced > 0 ? forced : (cus > 0 ? cus / B : 1);
-      if (forced <= 0 && (plugin_of(desc->model_id) || B > 64)) g = 1;
-      if (g > 8) g = 8;
-      h->spec_slots = g > 1 ? 4 * g - 1 : 3;
-    }
+    // ... as many as the cluster size make_args will pick asks for (cluster_size): 4 g - 1 (15 at B = 64 on 256 CUs), 3 when the
+    // launch will not be clustered - plugin models unless MI_ILQR_CLUSTER forces it, batches beyond 64, fewer than two CUs per
+    // problem.  (Round 5 allocated 31 for every batch up to 64: 1 GB of HBM for nothing on an n = 32, N = 2000 plugin.)
+    const int g = cluster_size(h);
+    h->spec_slots = g > 1 ? 4 * g - 1 : 3;
     for (;;) {
       const size_t xb = (size_t)h->spec_slots * B * n * N * sizeof(double), ub = (size_t)h->spec_slots * B * m * (N - 1) * sizeof(double);
       if (hipMalloc(reinterpret_cast<void**>(&h->x_spec), xb) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&h->u_spec), ub) == hipSuccess) break;
@@ -791,10 +752,6 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
     std::vector<int32_t> kl(B * (N - 1));
     for (size_t i = 0; i < kl.size(); ++i) kl[i] = (int32_t)(i % (N - 1));
     if (hipMemcpy(h->kp_list, kl.data(), kl.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { mi_ilqr_destroy(h); return MI_ILQR_E_HIP; }
-  }
-  {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, desc->device_id) == hipSuccess) h->n_cus = cus;
   }
   // defaults Q=I, R=I, Qf=I, x_nom=0 (ilqr.py:61-67)
   {
@@ -1167,15 +1124,12 @@ int mi_ilqr_reset(mi_ilqr_t* h) {
   return MI_ILQR_OK;
 }
 
-// Whether a workgroup-per-problem handle has Limited<M> kernels: the mid-size layout (n <= 32), and for a plugin, kernels it was built
+// Whether a workgroup-per-problem handle has Limited<M> kernels: the mid-size layout (n <= 32), and kernels the model was built
 // with (asked through its launch entry, which launches nothing for the probe).
 static bool large_accepts_limits(mi_ilqr* h) {
   if (h->n > 32) return false;
-  if (h->d.model_id == MI_MODEL_ARM27 || h->d.model_id == MI_MODEL_ARM27C) return true;
-  const PluginSlot* ps = plugin_of(h->d.model_id);
-  if (!ps) return false;
   const KArgs a = make_args(h);
-  return ps->p.launch(h, kModeProbeLimits, &a) == MI_ILQR_OK;
+  return model_of(h->d.model_id)->p.launch(h, kModeProbeLimits, &a) == MI_ILQR_OK;
 }
 
 int mi_ilqr_set_control_limits(mi_ilqr_t* h, const double* u_min, const double* u_max, int32_t per_problem) {

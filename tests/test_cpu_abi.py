@@ -51,6 +51,22 @@ def test_model_registry_matches_python_side(lib):
     assert lib.mi_ilqr_model_info(99, None, None, None, None) != 0
 
 
+def test_lds_bytes_of_the_builtin_models(lib):
+    """mi_ilqr_lds_bytes of every built-in model id (the model table's LDS sizes, one LDS-resident problem) at four horizons."""
+    from drake_ddp_amd import _capi
+    expected = {0: [1776, 10416, 37416, 181416], 1: [2840, 18776, 68576, 334176], 2: [2840, 18776, 68576, 334176],
+                3: [2840, 18776, 68576, 334176], 4: [103704, 123312, 185112, 514712], 5: [103704, 123312, 185112, 514712],
+                6: [124424, 144416, 207416, 543416], 7: [68800, 83032, 128032, 368032], 8: [68800, 83032, 128032, 368032]}
+    for mid, sizes in expected.items():
+        for N, size in zip((2, 50, 200, 1000), sizes):
+            d = _capi.Desc()
+            d.model_id, d.N = mid, N
+            assert lib.mi_ilqr_lds_bytes(C.byref(d)) == size, (mid, N)
+    d = _capi.Desc()
+    d.model_id, d.N = 99, 50
+    assert lib.mi_ilqr_lds_bytes(C.byref(d)) == 0
+
+
 def test_bytes_per_iteration_formula(lib):
     # SURVEY.md §8d per-unit figures
     assert lib.mi_ilqr_bytes_per_iteration(2, 1, 200, 1) == 49424
