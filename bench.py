@@ -2,8 +2,12 @@
 """bench.py — iLQR iterations/s of the batched HIP solver on BASELINE.json's config C2
 (pendulum swing-up n=2 m=1 N=200, B=1024 seeded initial states per GPU, fp64).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: set-up, the clock ramp (K + 96 untimed steps) and the W warm-up
+steps, the K timed steps, the line.  --full adds every other measurement of this file around the same timed steps (below); --no-cpu-baseline
+and --no-configs narrow a --full run.
 
 --dump-outputs DIR: after the K timed steps, rank 0 writes what the last of them computed for its batch - the arrays a
 caller of the solver reads after a Solve() - as DIR/<name>.npy (float64, see dump_outputs).  The inputs are seeded, so two
@@ -17,10 +21,13 @@ u_guess re-armed) of this rank's shard; inputs are resident in HBM before the ti
 region.  Steps are enqueued back to back on the solver's stream (one solve runs at a time;
 each keeps its own kernel events and statistics record) and collected per group of 32.
 value = (sum over ranks and steps of iLQR iterations) / (max-over-ranks wall).
-After the headline the same line carries `configs` (BASELINE.json's other configs C1, C3, C4, C5 at
-their full sizes, sharded over the ranks: iterations/s, ms per solve, kernel ms, algorithmic GB/s and
-roofline fraction, fp64 FLOP/s for C5) and `boundary_inclusive` (C2 through the class surface:
-Solve() with the host copy-in and the x_bar/u_bar/cost copy-out).  Prints exactly one JSON line on rank 0.
+With --full the same line also carries `cpu_baseline` (the oracle on the host cores), `configs` (BASELINE.json's other
+configs C1, C3, C4, C5 at their full sizes, sharded over the ranks: iterations/s, ms per solve, kernel ms, algorithmic
+GB/s and roofline fraction, fp64 FLOP/s for C5), `boundary_inclusive` (C2 through the class surface: Solve() with the
+host copy-in and the x_bar/u_bar/cost copy-out), `concurrent_batches`, `value_cold_clock` (the K steps from an idle
+clock), the solve kernel's live hardware counters in `roofline` / `roofline_compute` (nested rocprofv3 passes; a plain
+run takes the committed passes under profiles/) and, with N > 1 ranks, `strong_scaling`; a plain run prints null for
+them.  Prints exactly one JSON line on rank 0.
 """
 import argparse
 import json
@@ -75,13 +82,12 @@ def pmc_live(batch, groups=("fetch", "write", "fp64", "waves")):
     if not os.path.exists(exe):
         return {}
     vals = {}
-    env = dict(os.environ, TMPDIR="/tmp", MI_BENCH_NESTED="1")
+    env = dict(os.environ, TMPDIR="/tmp")
     for grp in groups:
         out = tempfile.mkdtemp(prefix="mi_pmc_", dir="/tmp")
         try:
             cmd = [exe, "--pmc"] + PMC_GROUPS[grp] + ["--kernel-trace", "--output-format", "csv", "-d", out, "--",
-                   sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1",
-                   "--batch", str(batch), "--no-cpu-baseline", "--no-configs"]
+                   sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--batch", str(batch)]
             subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
                            timeout=180, check=True)
             rows = {}
@@ -112,8 +118,6 @@ def pmc_traffic_live(batch, vals=None):
 
 
 def pmc_traffic(batch, vals=None):
-    if os.environ.get("MI_BENCH_NESTED"):
-        return None, None
     live = pmc_traffic_live(batch, vals)
     if live is not None:
         return live, "live rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes), FETCH x2 gfx950 correction"
@@ -585,8 +589,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024, help="problems per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="headline only (skip C1/C3/C4/C5 and the boundary-inclusive run)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baseline, every other config, the boundary-inclusive and concurrent-batch runs, "
+                         "the idle-clock steps, live hardware counters and (N > 1) the strong-scaling figure")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="with --full: skip C1/C3/C4/C5, the boundary-inclusive and the concurrent-batch runs")
     ap.add_argument("--cpu-sample", type=int, default=24)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's results (rank 0's batch) to DIR/<name>.npy")
@@ -630,13 +638,13 @@ def main():
     x0_all = W.pendulum_batch_x0(B * world, seed=0)       # global batch; rank r owns a contiguous block
     x0 = x0_all[rank * B:(rank + 1) * B]
 
-    # Order of the run: the CPU baseline (host cores only), then every other config and the boundary-inclusive
-    # figure, then the headline.
+    # Order of a --full run: the CPU baseline (host cores only), then every other config and the boundary-inclusive
+    # figure, then the headline.  A plain run goes straight to the headline.
     cpu_base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_base = cpu_baseline(prob, x0_all, min(args.cpu_sample, B))
     configs = boundary = concurrent = None
-    if not args.no_configs and not os.environ.get("MI_BENCH_NESTED"):
+    if args.full and not args.no_configs:
         configs = all_configs(rk, dev_index)
         if rank == 0:
             boundary = boundary_inclusive(prob, x0, dev_index)
@@ -742,17 +750,23 @@ def main():
     # 20-step group after an idle spell runs 4-5 % slower than the fourth); W warm-up steps of 0.16 ms do not get
     # there, so CLOCK_RAMP_STEPS more untimed steps precede them.  Reported in the line as `clock_ramp_steps`.
     CLOCK_RAMP_STEPS = 96
-    # The same K steps from an IDLE clock first (no ramp, no warm-up beyond the module load above): `value_cold_clock`,
-    # what a caller who solves one batch now and then sees.  The device idles for half a second before it.
-    rk.fence()
-    time.sleep(0.5)
-    rk.fence()
+    # The same K steps from an IDLE clock first (no ramp, no warm-up beyond the module load above).  --full times them:
+    # `value_cold_clock`, what a caller who solves one batch now and then sees; the device idles for half a second before
+    # them.  A plain run issues them untimed, as the first part of its ramp: the device work ahead of the timed region is then
+    # the same in both forms, and so is the headline (with CLOCK_RAMP_STEPS alone ahead of W = 5, K = 20 timed steps came out
+    # 0.9 % slower than with these steps first, five alternated pairs on one MI355X; 0.2 % at K = 200).
+    if args.full:
+        rk.fence()
+        time.sleep(0.5)
+        rk.fence()
     tc0 = time.perf_counter()
     cold_steps = run_steps(args.steps)
     drain()
     rk.fence()
-    cold_elapsed = rk.reduce([time.perf_counter() - tc0], "max")[0]
-    cold_iters = rk.reduce([sum(st.total_iters for st in cold_steps)], "sum")[0]
+    cold_iters = cold_elapsed = None
+    if args.full:
+        cold_elapsed = rk.reduce([time.perf_counter() - tc0], "max")[0]
+        cold_iters = rk.reduce([sum(st.total_iters for st in cold_steps)], "sum")[0]
     run_steps(CLOCK_RAMP_STEPS)
     run_steps(args.warmup)
     drain()
@@ -778,12 +792,12 @@ def main():
         dump_outputs(s, args.dump_outputs)                 # (after the timed region: the reads cost it nothing)
     del s, s_weak
 
-    # N > 1: the STRONG-scaling figure beside the weak one - north_star's "a batch of 1024 ... at 1/2/4/8 GPUs": the single-GPU run's
+    # --full, N > 1: the STRONG-scaling figure beside the weak one - north_star's "a batch of 1024 ... at 1/2/4/8 GPUs": the single-GPU run's
     # own 1024 problems (the same draw), a contiguous shard per rank, the same K steps between the same fences.  A launch lasts
     # as long as its slowest problem at any batch size, so this is expected to stay near the single-GPU value: it is reported
     # so that a scaling record shows it, not because the path has anything to gain from it.
     strong = None
-    if world > 1:
+    if args.full and world > 1:
         from drake_ddp_amd.dist import shard_range
         lo, hi = shard_range(B, rank, world)
         ss = make_solver(prob, hi - lo, dev_index)
@@ -812,10 +826,10 @@ def main():
         k_ms = kernel_ms / n_timed                          # avg launch duration of the dominant kernel (HIP events)
         bytes_per_launch = alg_bytes / args.steps
         achieved = bytes_per_launch / (k_ms * 1e-3) / 1e9
-        ctr = pmc_live(B) if (world == 1 and not os.environ.get("MI_BENCH_NESTED")) else {}
-        traffic, traffic_src = pmc_traffic(B, ctr) if world == 1 else pmc_traffic_committed(B)
+        ctr = pmc_live(B) if (args.full and world == 1) else {}
+        traffic, traffic_src = pmc_traffic(B, ctr) if (args.full and world == 1) else pmc_traffic_committed(B)
         # the BINDING roofline: fp64 arithmetic issued (SQ instruction counters of this kernel, live when one GPU runs
-        # the bench, else the committed pass) against the fp64 vector peak
+        # the bench with --full, else the committed pass) against the fp64 vector peak
         cc, cc_src = committed_issue_counters()
         if all(k in ctr for k in PMC_GROUPS["fp64"]):
             flops = 64.0 * (2 * ctr["SQ_INSTS_VALU_FMA_F64"] + ctr["SQ_INSTS_VALU_ADD_F64"] + ctr["SQ_INSTS_VALU_MUL_F64"] + ctr["SQ_INSTS_VALU_TRANS_F64"])
@@ -866,8 +880,9 @@ def main():
                        "collective": None if world == 1 else ("librccl all-reduce(min) via mi_ilqr_allreduce_min_start (the library's own communicator; ncclCommCount = %d)" % comm_ranks
                                                               if native is not None else f"torch.distributed all_reduce(MIN), backend {backend}"),
                        "collective_fallback_reason": native_why},
-            "value_cold_clock": cold_iters / cold_elapsed,
-            "ms_per_step_cold_clock": 1e3 * cold_elapsed / args.steps,
+            "full": args.full,
+            "value_cold_clock": cold_iters / cold_elapsed if args.full else None,
+            "ms_per_step_cold_clock": 1e3 * cold_elapsed / args.steps if args.full else None,
             "iterations_per_step_rank0": iters / args.steps,
             "max_iterations_per_problem": int(last.max_iters_seen),
             "converged_rank0": int(last.n_converged),
@@ -884,8 +899,9 @@ def main():
         }
         out["roofline_compute"] = compute
         out["cpu_baseline"] = cpu_base
-        out["order"] = ("cpu_baseline, configs, boundary_inclusive, then the headline: 0.5 s idle, K steps from the idle clock "
-                        "(value_cold_clock), clock_ramp_steps untimed steps (the shader clock reaches its sustained level), the W "
+        out["order"] = (("cpu_baseline, configs, boundary_inclusive, then the headline: 0.5 s idle, K steps from the idle clock "
+                         "(value_cold_clock), " if args.full else "the headline alone: K untimed steps, ") +
+                        "clock_ramp_steps untimed steps (the shader clock reaches its sustained level), the W "
                         "warm-up steps, the K timed steps (value)")
         out["configs"] = configs
         out["boundary_inclusive"] = boundary

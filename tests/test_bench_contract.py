@@ -1,10 +1,12 @@
 """bench.py's launch contract: `--gpus N` starts N ranks by itself when no launcher did, the N > 1
-path runs (gloo stand-in for RCCL on a single-GPU box: all ranks share device 0), and the one JSON
-line carries the headline, `roofline`, `cpu_baseline`, `configs` and `boundary_inclusive`."""
+path runs (gloo stand-in for RCCL on a single-GPU box: all ranks share device 0), a plain run times the
+headline alone, and with `--full` the one JSON line carries the headline, `roofline`, `cpu_baseline`, `configs`
+and `boundary_inclusive`."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -31,7 +33,7 @@ def test_bench_fails_loudly_without_a_gpu_or_with_too_few():
         r = _run(["--gpus", str(torch.cuda.device_count() + 1), "--steps", "1", "--warmup", "0"])
         assert r.returncode != 0 and "GPU(s) visible" in (r.stderr + r.stdout)
     else:
-        for a in (["--steps", "1"], ["--gpus", "2", "--steps", "1"]):
+        for a in (["--steps", "1"], ["--gpus", "2", "--steps", "1"], ["--full", "--steps", "1"]):
             r = _run(a)
             assert r.returncode != 0 and "needs an MI355X" in (r.stderr + r.stdout)
 
@@ -54,9 +56,10 @@ def test_bench_gpus_2_launches_its_own_ranks():
 
 @pytest.mark.gpu
 def test_bench_line_carries_every_config_and_the_boundary():
-    r = _run(["--steps", "5", "--warmup", "2", "--cpu-sample", "4"])
+    r = _run(["--full", "--steps", "5", "--warmup", "2", "--cpu-sample", "4"])
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
+    assert d["full"] is True and d["value_cold_clock"] > 0 and d["ms_per_step_cold_clock"] > 0
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "configs", "boundary_inclusive"):
         assert k in d, k
@@ -76,6 +79,37 @@ def test_bench_line_carries_every_config_and_the_boundary():
     assert d["clock_ramp_steps"] >= 0 and "order" in d and "kernel_ms_source" in rf
     cb = d["concurrent_batches"]["runs"]
     assert [r_["handles"] for r_ in cb] == [2, 4] and all(r_["iterations_per_s"] > 0.8 * d["value"] for r_ in cb)
+
+
+PLAIN_OVERHEAD_S = 30.0     # what a plain run may spend outside its warm-up and timed steps
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: set-up, warm-up, the K timed steps and the line - the headline's
+    keys as ever, null for everything that has runs of its own (they are --full's), the counters from the committed passes, and
+    at most PLAIN_OVERHEAD_S of the whole process (start to exit) outside its K + W steps."""
+    steps, warmup = 20, 3
+    t0 = time.perf_counter()
+    r = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)])
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    assert d["metric"] == "iLQR iterations/sec (batch, whole node)" and d["unit"] == "iterations/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warmup
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["converged_rank0"] == 1024
+    assert abs(d["value"] - d["iterations_per_step_rank0"] / (d["ms_per_step"] * 1e-3)) < 1e-9 * d["value"]
+    assert d["full"] is False
+    for k in ("cpu_baseline", "configs", "boundary_inclusive", "concurrent_batches", "value_cold_clock", "ms_per_step_cold_clock",
+              "strong_scaling", "value_strong"):
+        assert d[k] is None, k
+    rf = d["roofline"]
+    assert rf["kernel_ms"] > 0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-12
+    assert rf["traffic_source"] is None or rf["traffic_source"].startswith("committed ")
+    assert d["roofline_compute"] is None or d["roofline_compute"]["source"].startswith("committed ")
+    outside = wall - (steps + warmup) * d["ms_per_step"] * 1e-3
+    print(f"plain run: {wall:.2f} s start to exit, {outside:.2f} s outside its {steps} + {warmup} steps")
+    assert outside <= PLAIN_OVERHEAD_S, (wall, outside)
 
 
 def test_dump_outputs_samples_a_fixed_subset_above_the_cap(tmp_path, monkeypatch):
@@ -136,7 +170,7 @@ _ONE_RANK = {}
 def _one_rank_configs():
     """The single-rank run with every config (cached for the sharded runs to be compared with)."""
     if "d" not in _ONE_RANK:
-        r = _run(["--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+        r = _run(["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
         assert r.returncode == 0, r.stderr[-3000:]
         _ONE_RANK["d"] = _json_line(r.stdout)
     return _ONE_RANK["d"]
@@ -147,13 +181,13 @@ def _one_rank_configs():
 #  node allows no more than 6; 3 ranks also give uneven shards: C3's 512 -> 171/171/170, C5's 64 -> 22/21/21)
 @pytest.mark.parametrize("world", [2, 3])
 def test_bench_sharded_configs_do_exactly_the_whole_batchs_work(world):
-    """`bench.py --gpus N` WITH every config (C1, C3 ... C6b through run_config's shard path: C3 at 512 / N problems per rank, C5 at
+    """`bench.py --full --gpus N` WITH every config (C1, C3 ... C6b through run_config's shard path: C3 at 512 / N problems per rank, C5 at
     64 / N, C1's single problem on rank 0 alone), N ranks over gloo sharing this box's GPU - the form of the run a multi-GPU
     node executes over RCCL.  Problems are independent and every kernel's result is independent of its batch,
     so the ranks together must do EXACTLY the single-rank run's work: the same iterations per config (rank-summed), every problem
     converged, batch_per_gpu = ceil(B / N); the line says how many ranks and which collective."""
     one = _one_rank_configs()
-    r = _run(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env={"MI_BENCH_BACKEND": "gloo"}, timeout=1500)
+    r = _run(["--full", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env={"MI_BENCH_BACKEND": "gloo"}, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["n_gpus"] == world and d["scaling"] == "weak" and d["config"]["global_batch"] == 1024 * world

@@ -8,10 +8,10 @@ OUT=$PWD/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 REPO=$PWD
-python bench.py > $OUT/${TAG}_bench_c2.json 2> $OUT/${TAG}_bench_c2.err
-( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -- python $REPO/bench.py --no-cpu-baseline --no-configs > $OUT/${TAG}_prof.log 2>&1 )
+python bench.py --full > $OUT/${TAG}_bench_c2.json 2> $OUT/${TAG}_bench_c2.err
+( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -- python $REPO/bench.py > $OUT/${TAG}_prof.log 2>&1 )
 for C in FETCH_SIZE WRITE_SIZE; do
-  ( cd /tmp && MI_BENCH_NESTED=1 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_$C -- python $REPO/bench.py --no-cpu-baseline --steps 5 --warmup 1 > $OUT/${TAG}_pmc_$C.log 2>&1 )
+  ( cd /tmp && rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_$C -- python $REPO/bench.py --steps 5 --warmup 1 > $OUT/${TAG}_pmc_$C.log 2>&1 )
 done
 python - > $OUT/${TAG}_all_configs.jsonl <<PY
 import json
