@@ -70,6 +70,16 @@ __host__ __device__ inline Dual2 operator-(Dual2 a, double b) { return {a.v - b,
 __host__ __device__ inline Dual2 operator-(double a, Dual2 b) { return {a - b.v, -b.d0, -b.d1}; }
 __host__ __device__ inline Dual2 operator*(Dual2 a, double b) { return {a.v * b, a.d0 * b, a.d1 * b}; }
 __host__ __device__ inline Dual2 operator*(double a, Dual2 b) { return {a * b.v, a * b.d0, a * b.d1}; }
+// (the quotient rules of Dual1, per direction)
+__host__ __device__ inline Dual2 operator/(Dual2 a, Dual2 b) {
+  const double q = a.v / b.v;
+  return {q, (a.d0 - q * b.d0) / b.v, (a.d1 - q * b.d1) / b.v};
+}
+__host__ __device__ inline Dual2 operator/(Dual2 a, double b) { return {a.v / b, a.d0 / b, a.d1 / b}; }
+__host__ __device__ inline Dual2 operator/(double a, Dual2 b) {
+  const double q = a / b.v;
+  return {q, (-q * b.d0) / b.v, (-q * b.d1) / b.v};
+}
 __host__ __device__ inline double value_of(Dual2 a) { return a.v; }
 // The time-parallel rollout's Newton sweeps need cos only as the SLOPE of sin: fast_sin_slope (fastmath.hpp) - the value bit for
 // bit fast_sin, the slope to 1e-10 from the same reduction.  Same-box A/B, round 6 (tools/diag/build_variant.py cc1
@@ -85,6 +95,11 @@ __device__ inline Dual2 mi_sin(Dual2 a) { const double c_ = fast_cos(a.v); retur
 #endif
 __device__ inline Dual2 mi_cos(Dual2 a) { const double s_ = -fast_sin(a.v); return {fast_cos(a.v), s_ * a.d0, s_ * a.d1}; }
 __device__ inline Dual2 mi_rcp(Dual2 a) { const double r = fast_rcp(a.v), q = -(r * r); return {r, q * a.d0, q * a.d1}; }
+// The rest of the primitive set, so that one step() body serves double, Dual1 and Dual2 alike (plugin.py): the values and
+// the derivative rules are those of the Dual1 overloads, per direction.
+__device__ inline Dual2 mi_sqrt(Dual2 a) { const double r = sqrt(a.v), h = fast_rcp(2.0 * r); return {r, a.d0 * h, a.d1 * h}; }
+__device__ inline Dual2 mi_exp(Dual2 a) { const double e = exp(a.v); return {e, e * a.d0, e * a.d1}; }
+__device__ inline Dual2 mi_log1p(Dual2 a) { const double g = 1.0 + a.v; return {log1p(a.v), a.d0 / g, a.d1 / g}; }
 
 // log(1+exp(z)) = max(z,0) + log1p(exp(-|z|)), overflow-safe and branch-free; same value as the
 // two-branch form of oracle/dual.py:softplus.  d/dz = logistic(z).
@@ -112,6 +127,13 @@ __device__ inline Dual1 mi_softplus(Dual1 z) {
   const double r = fast_rcp(1.0 + t);
   const double sig = z.v > 0.0 ? r : t * r;
   return {fmax(z.v, 0.0) + fast_log1p01(t), sig * z.d};
+}
+// (value: bit for bit mi_softplus(double), as mi_sin(Dual2)'s is fast_sin's)
+__device__ inline Dual2 mi_softplus(Dual2 z) {
+  const double t = fast_exp_nonpos(-fabs(z.v));
+  const double r = fast_rcp(1.0 + t);
+  const double sig = z.v > 0.0 ? r : t * r;
+  return {fmax(z.v, 0.0) + fast_log1p01(t), sig * z.d0, sig * z.d1};
 }
 
 }  // namespace mi

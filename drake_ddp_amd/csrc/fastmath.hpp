@@ -169,7 +169,9 @@ __device__ __forceinline__ double fast_sin_or_cos(double x, bool is_cos) {
   return flip_sign_if_odd(sin_reduced(r), kn.lo);
 }
 
-// 1/x: hardware seed + two Newton steps (~1 ulp); no denormal/overflow rescaling.
+// 1/x: hardware seed + two Newton steps (~1 ulp; measured against mpmath on an MI355X: 0.50 ulp over 2^-500 .. 2^500, powers of
+// two exact - tests/test_gpu_primitives.py); no denormal/overflow rescaling.  NOT IEEE at the ends: x = +-0 and x = +-inf give NaN
+// (the Newton residual is 0 x inf there), as NaN does.
 __device__ __forceinline__ double fast_rcp(double x) {
   double r = __builtin_amdgcn_rcp(x);
   double e = fma(-x, r, 1.0);

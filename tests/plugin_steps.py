@@ -72,3 +72,15 @@ def kink2_step(x, u, p, dt):
         a = a - k * q
     vn = v + dt * a
     return [q + dt * vn, vn]
+
+
+def endstop2_step(x, u, p, dt):
+    """tests/test_gpu_dual2_overloads.py: a pendulum with a soft end-stop at q = qmax, a drag v / (2 + q^2) and small terms through
+    every other primitive - params [g_l, c, k, sig, qmax]."""
+    g_l, c, k, sig, qmax = p[0], p[1], p[2], p[3], p[4]
+    q, v = x[0], x[1]
+    w = q * q
+    a = u[0] - g_l * D.sin(q) - c * (v / (2.0 + w)) - (k * sig) * D.softplus((q - qmax) / sig)
+    a = a - 0.05 * (v / D.sqrt(1.0 + v * v)) + 0.1 * D.exp(-w) - 0.05 * D.log1p(w) + 0.02 * (1.0 / (3.0 + w)) * D.cos(q)
+    vn = v + dt * a
+    return [q + dt * vn, vn]
