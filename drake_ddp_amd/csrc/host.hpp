@@ -101,6 +101,12 @@ struct mi_ilqr {
   bool target_steps_moving = false;   // a row of the steps is non-zero (cluster helpers' candidate groups need a still target)
   double *x_nom_rows = nullptr, *target_steps = nullptr;   // (B, n) each, allocated on first use, kept when dropped
   std::vector<double> h_x_nom_rows, h_target_steps;
+  // per-problem model parameters (mi_ilqr_set MI_F_MODEL_PARAMS): `per_problem_params` hands the kernels param_rows, (B, n_params)
+  // dense, and - the lane-per-problem kernels - param_cols, the same values batch-minor, (n_params, B); the host mirror is what
+  // mi_ilqr_get returns.  Problem data: mi_ilqr_reset keeps them.
+  bool per_problem_params = false;
+  double *param_rows = nullptr, *param_cols = nullptr;   // allocated on first use, kept when dropped
+  std::vector<double> h_param_rows;
 };
 
 // Run-time switches for A/B runs (README): the environment is read once per process.

@@ -35,7 +35,7 @@ namespace mi {
 // batch-minor addressing helpers: element (t, r) of an array with `rows` rows per time step
 __device__ __forceinline__ size_t bm(int t, int r, int rows, int B) { return ((size_t)t * rows + r) * B; }
 
-template <class M, int JAC, bool KP = false, bool PT = false>
+template <class M, int JAC, bool KP = false, bool PT = false, bool PP = false>
 __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
   constexpr int n = M::n, m = M::m, nc = n + m;
   const int b = blockIdx.x * 64 + threadIdx.x;
@@ -63,6 +63,17 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
   double x0r[n];
 #pragma unroll
   for (int i = 0; i < n; ++i) x0r[i] = a.x0[(size_t)bb * n + i];
+  // PP: per-problem model parameters - the lane's own plant in registers, read once from the batch-minor copy of the rows
+  // (KArgs::param_cols, (n_params, B): one coalesced load per parameter).  Its own instantiation as well: the regular kernel's
+  // parameters are batch-uniform kernel arguments (scalar registers) and stay so.
+  [[maybe_unused]] double par[M::n_params > 0 ? M::n_params : 1];
+  if constexpr (PP) {
+#pragma unroll
+    for (int i = 0; i < M::n_params; ++i) par[i] = a.param_cols[(size_t)i * B + bb];
+  }
+  const double* prm;
+  if constexpr (PP) prm = par;
+  else prm = a.params;
   // Limited<M>: the lane's bounds in registers, and S2 of its last backward pass (box_qp_step)
   [[maybe_unused]] double s2 = 0.0;
   if constexpr (UsesLimits<M>::value) {
@@ -154,7 +165,7 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
           if constexpr (UsesLimits<M>::value) u[k] = c.clamp(k, u[k]);  // clip(u, u_min, u_max)
         }
         double xn[n];
-        M::template step<double>(x, u, xn, a.params, a.dt);             // :316
+        M::template step<double>(x, u, xn, prm, a.dt);             // :316
         Lc += stage_cost<M>(c, x, u);                                   // :325
         if constexpr (UsesLimits<M>::value) ex += r.dv;                 // sum dV (limited_expected)
         else ex += ce * r.dv;                                           // :326
@@ -227,12 +238,12 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
             for (int i = 0; i < n; ++i) xp[i] = (col == i) ? xv[i] + h : xv[i];
 #pragma unroll
             for (int k = 0; k < m; ++k) up[k] = (col == n + k) ? uv[k] + h : uv[k];
-            M::template step<double>(xp, up, fp, a.params, a.dt);
+            M::template step<double>(xp, up, fp, prm, a.dt);
 #pragma unroll
             for (int i = 0; i < n; ++i) xp[i] = (col == i) ? xv[i] - h : xv[i];
 #pragma unroll
             for (int k = 0; k < m; ++k) up[k] = (col == n + k) ? uv[k] - h : uv[k];
-            M::template step<double>(xp, up, fmv, a.params, a.dt);
+            M::template step<double>(xp, up, fmv, prm, a.dt);
 #pragma unroll
             for (int i = 0; i < n; ++i) d[i] = (fp[i] - fmv[i]) * inv2h;
           } else {
@@ -241,7 +252,7 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
             for (int i = 0; i < n; ++i) xd[i] = Dual1(xv[i], (col == i) ? 1.0 : 0.0);
 #pragma unroll
             for (int k = 0; k < m; ++k) ud[k] = Dual1(uv[k], (col == n + k) ? 1.0 : 0.0);
-            M::template step<Dual1>(xd, ud, fd, a.params, a.dt);
+            M::template step<Dual1>(xd, ud, fd, prm, a.dt);
 #pragma unroll
             for (int i = 0; i < n; ++i) d[i] = fd[i].d;
           }

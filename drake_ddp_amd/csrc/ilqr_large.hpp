@@ -102,6 +102,7 @@ struct LView {
   int N;
   int pd_continue;  // a Quu that is not positive definite: 1 = invert it with partial pivoting and carry on like np.linalg.inv (ilqr.py:655)
   int asym;         // Q, R or Qf is not symmetric (mid-size kernels only): the reference's recursion without any use of symmetry
+  const double* prow;   // this problem's row of the per-problem model parameters (KArgs::param_rows), or nullptr: the shared ones
 };
 
 // lx_t | lu_t: LDS (the address space stays known to the compiler) or HBM, chosen per launch
@@ -256,9 +257,11 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 template <class M>
 struct ModelScalars {
   double p[M::n_params], dt, fd_h;
-  __device__ __forceinline__ explicit ModelScalars(const KArgs& a) {
+  // row: the problem's row of the per-problem parameters (LView::prow; a cluster helper: the problem it serves), or nullptr
+  __device__ __forceinline__ ModelScalars(const KArgs& a, const double* row) {
+    const ModelParams<M> par(a, row);
 #pragma unroll
-    for (int i = 0; i < M::n_params; ++i) { p[i] = a.params[i]; if constexpr (M::n_params > 4) asm volatile("" : "+s"(p[i])); }
+    for (int i = 0; i < M::n_params; ++i) { p[i] = par.v[i]; if constexpr (M::n_params > 4) asm volatile("" : "+s"(p[i])); }
     dt = a.dt; if constexpr (M::n_params > 4) asm volatile("" : "+s"(dt));
     fd_h = a.fd_h; if constexpr (M::n_params > 4) asm volatile("" : "+s"(fd_h));
   }
@@ -371,7 +374,7 @@ __device__ inline double large_rollout(const LView<M::n, M::m>& v, double* lds, 
   double* r2buf = lds + Ly::oT1 + 64;                                  // [2][64]
   static_assert(Ly::NK * Ly::TS >= 192, "dx + two half-row scratch vectors inside T1");
   double r1_prev = 0.0;
-  const ModelScalars<M> ms(a);
+  const ModelScalars<M> ms(a, v.prow);
   const double* prm = ms.p;
   const double dt_ = ms.dt;
   // Models whose whole state is advanced by ONE lane (whole-step plugins) or redundantly by every lane of a row (trig models):
@@ -706,7 +709,7 @@ __device__ inline void mid_rollout4(const LView<M::n, M::m>& v, double* xsp, dou
   }
   const bool drole = tid >= 192 && tid < 192 + n;
   const double xnr = drole ? xnom[tid - 192] : 0.0;
-  const ModelScalars<M> ms(a);
+  const ModelScalars<M> ms(a, v.prow);
   const double* prm = ms.p;
   const double dt_ = ms.dt;
   auto Xo = [&](int c) __attribute__((always_inline)) { return c == 0 ? v.Xn : xsp + (size_t)(c - 1) * sx; };
@@ -926,7 +929,7 @@ template <class M, int JAC, bool COH = false>
 __device__ __forceinline__ void large_jac_at_sparse(const LView<M::n, M::m>& v, const KArgs& a, const int* list, int count,
                                                     const double* Xsrc, const double* Usrc, int first = 0, int stride = 1) {
   constexpr int n = M::n, m = M::m, nc = n + m, nq = M::nq;
-  const ModelScalars<M> ms(a);
+  const ModelScalars<M> ms(a, v.prow);
   const double h = ms.fd_h, inv2h = 1.0 / (2.0 * h);
   for (int it = first * kLargeThreads + stage_tid(); it < count * nc; it += stride * kLargeThreads) {
     const int ki = it / nc, col = it - ki * nc;
@@ -982,7 +985,7 @@ __device__ __forceinline__ void large_jac_at_tree(const LView<M::n, M::m>& v, co
                                                   const double* Xsrc, const double* Usrc, int xstride, int ustride, double* cache,
                                                   int first = 0, int stride = 1) {
   constexpr int n = M::n, m = M::m, nc = n + m, nq = M::nq, NCH = M::kChains;
-  const ModelScalars<M> ms(a);
+  const ModelScalars<M> ms(a, v.prow);
   const double h = ms.fd_h, inv2h = 1.0 / (2.0 * h), dt = ms.dt;
   using AggD = typename M::template Agg<double>;
   if (JAC == MI_JAC_FD_CENTRAL) {
@@ -1112,7 +1115,7 @@ __device__ __forceinline__ void large_jac_at_legs(const LView<M::n, M::m>& v, co
                                                   const double* Xsrc, const double* Usrc, int xstride, int ustride,
                                                   int first = 0, int cstride = 1) {
   constexpr int n = M::n, m = M::m, nc = n + m;
-  const ModelScalars<M> ms(a);
+  const ModelScalars<M> ms(a, v.prow);
   const double h = ms.fd_h, inv2h = 1.0 / (2.0 * h), dt = ms.dt;
   for (int it = first * kLargeThreads + stage_tid(); it < count * nc; it += cstride * kLargeThreads) {
     const int rank = it / count, ki = it - rank * count;
@@ -1212,7 +1215,7 @@ __device__ __forceinline__ void large_jac_at(const LView<M::n, M::m>& v, const K
                                              const double* Xsrc, const double* Usrc, int xstride, int ustride,
                                              int first = 0, int cstride = 1) {
   constexpr int n = M::n, m = M::m, nc = n + m;
-  const ModelScalars<M> ms(a);
+  const ModelScalars<M> ms(a, v.prow);
   const double h = ms.fd_h, inv2h = 1.0 / (2.0 * h);
   for (int it = first * kLargeThreads + stage_tid(); it < count * nc; it += cstride * kLargeThreads) {
     const int ki = it / nc, col = it - ki * nc;
@@ -3054,6 +3057,7 @@ __global__ void __launch_bounds__(kLargeThreads, kMinBlocks<M>) ilqr_large_kerne
   v.LxG = a.lxu ? a.lxu + (size_t)b * (N - 1) * (n + m) : nullptr;
   v.pd_continue = a.pd_continue;
   v.asym = a.cost_asym;                     // (n >= 33: large_backward_asym, the PIV form of the kernel)
+  v.prow = param_row_of<M>(a, b);
   LargeAcc<n, m> acc;
   acc.X = v.X; acc.Fx = v.Fx; acc.Fu = v.Fu; acc.N = N;
   { const int Nr = int_row(N); acc.kp = ilds; acc.aux = ilds + Nr; acc.need = ilds + 2 * Nr; acc.binA = ilds + 3 * Nr; acc.binB = ilds + 5 * Nr; }

@@ -113,6 +113,12 @@ struct KArgs {
   // Null: the shared target.
   const double* x_nom_rows;
   const double* target_steps;
+  // per-problem model parameters (mi_ilqr_set MI_F_MODEL_PARAMS): the plant of problem b is row b of param_rows instead of `params`.
+  // Rows are DENSE: (B, n_params), the row stride is the model's n_params doubles - what mi_ilqr_device_ptr hands out.  The
+  // lane-per-problem kernels read param_cols, the same values batch-minor, (n_params, B): a wave's load of parameter k is one
+  // coalesced transaction.  Null (both): the shared `params`.  Neither array is written while a kernel runs.
+  const double* param_rows;
+  const double* param_cols;
 };
 
 // Where problem b's target lives: row b of the per-problem targets, else the shared one in the costmat (Q | R | Qf | x_nom).
@@ -124,6 +130,32 @@ __device__ __forceinline__ const double* x_nom_of(const KArgs& a, size_t b) {
 template <int n>
 __device__ __forceinline__ double target_step_of(const KArgs& a, size_t b, int i) {
   return a.target_steps ? a.target_steps[b * n + i] : a.mpc_target_step[i];
+}
+
+// The model parameters of problem b as VALUES: row b of the per-problem rows, else the shared copy in the kernel arguments.  b is
+// uniform for the wave (a wave or a workgroup serves one problem): the row is read through the constant address space - scalar
+// loads into scalar registers, where the shared copy lives too - once, by whoever constructs this, and handed on as values.  No
+// pointer ever selects between the two sources (that would be a generic-address-space or a scratch access).
+typedef const double __attribute__((address_space(4))) * const_row_t;
+template <class M>
+struct ModelParams {
+  double v[M::n_params > 0 ? M::n_params : 1];
+  // row: this problem's row of KArgs::param_rows, or nullptr
+  __device__ __forceinline__ ModelParams(const KArgs& a, const double* row) {
+    if (row != nullptr) {
+      const const_row_t r = (const_row_t)row;
+#pragma unroll
+      for (int i = 0; i < M::n_params; ++i) v[i] = r[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < M::n_params; ++i) v[i] = a.params[i];
+    }
+    if constexpr (M::n_params == 0) v[0] = 0.0;
+  }
+};
+template <class M>
+__device__ __forceinline__ const double* param_row_of(const KArgs& a, size_t b) {
+  return a.param_rows ? a.param_rows + b * M::n_params : nullptr;
 }
 
 // threadIdx.x behind an empty asm, for the STAGES of a solve kernel (a rollout, a linearization, a backward pass): what a stage
@@ -459,7 +491,7 @@ template <class M>
 struct PoolOf<M, true> { using type = typename M::StepPool; __device__ __forceinline__ static type make() { return M::StepPool::in_vgprs(); } };
 
 template <class M, bool COST>
-__device__ __forceinline__ void rollout_step(const GRegs<M>& r, const Consts<M>& c, const KArgs& a, double eps,
+__device__ __forceinline__ void rollout_step(const GRegs<M>& r, const Consts<M>& c, const KArgs& a, const ModelParams<M>& par, double eps,
                                              double ce, double (&x)[M::n], double& L, double& expd, double* tw,
                                              const typename PoolOf<M>::type& pool) {
   constexpr int n = M::n, m = M::m;
@@ -475,8 +507,8 @@ __device__ __forceinline__ void rollout_step(const GRegs<M>& r, const Consts<M>&
     if constexpr (UsesLimits<M>::value) u[k] = c.clamp(k, u[k]);   // clip(u, u_min, u_max)
   }
   double xnext[n];
-  if constexpr (HasStepPool<M>::value) M::step_pooled(x, u, xnext, a.params, a.dt, pool);   // ilqr.py:316
-  else M::template step<double>(x, u, xnext, a.params, a.dt);
+  if constexpr (HasStepPool<M>::value) M::step_pooled(x, u, xnext, par.v, a.dt, pool);   // ilqr.py:316
+  else M::template step<double>(x, u, xnext, par.v, a.dt);
   if (COST) {
     // stage cost (no 1/2 factor, ilqr.py:325) and expected improvement (:326)
     L += stage_cost<M>(c, x, u, a.q_diag != 0);
@@ -503,7 +535,7 @@ __device__ __forceinline__ double limited_expected(const WS& w, double eps, doub
 
 // `slot` >= 0: this lane stores its trajectory into T buffer `slot`; < 0: stores are parked.
 template <class M, bool COST = true>
-__device__ inline void rollout(const WS& w, const Consts<M>& c, const KArgs& a, const double* x0r,
+__device__ inline void rollout(const WS& w, const Consts<M>& c, const KArgs& a, const ModelParams<M>& par, const double* x0r,
                                double eps, int slot, double& L_out, double& exp_out) {
   constexpr int n = M::n, m = M::m;
   using Ly = Lay<n, m>;
@@ -531,15 +563,15 @@ __device__ inline void rollout(const WS& w, const Consts<M>& c, const KArgs& a, 
   for (; t + 1 < N - 1; t += 2) {
     B.load(g + Ly::GS);
     __builtin_amdgcn_sched_barrier(0);      // keep the prefetch a full step ahead of its first use
-    rollout_step<M, COST>(A, c, a, eps, ce, x, L, expd, tw, pool);
+    rollout_step<M, COST>(A, c, a, par, eps, ce, x, L, expd, tw, pool);
     tw += tstep;
     A.load(g + 2 * Ly::GS);                 // t+2 <= N-1: a real record (or the pad at N)
     __builtin_amdgcn_sched_barrier(0);
-    rollout_step<M, COST>(B, c, a, eps, ce, x, L, expd, tw, pool);
+    rollout_step<M, COST>(B, c, a, par, eps, ce, x, L, expd, tw, pool);
     tw += tstep;
     g += 2 * Ly::GS;
   }
-  if (t < N - 1) rollout_step<M, COST>(A, c, a, eps, ce, x, L, expd, tw, pool);
+  if (t < N - 1) rollout_step<M, COST>(A, c, a, par, eps, ce, x, L, expd, tw, pool);
   if (COST) L += terminal_cost<M>(c, x);            // ilqr.py:327
   L_out = L;
   if constexpr (UsesLimits<M>::value) exp_out = limited_expected<n, m>(w, eps, expd);
@@ -621,7 +653,7 @@ __device__ __forceinline__ double lane_read_f64(double v, int src);
 // One column of [fx | fu] at (x, u): central differences (the build's stand-in for AutoDiff,
 // ilqr.py:233-272) or one forward-mode dual evaluation.
 template <class M, int JAC>
-__device__ __forceinline__ void jac_column(const double (&x)[M::n], const double (&u)[M::m], int col, const KArgs& a,
+__device__ __forceinline__ void jac_column(const double (&x)[M::n], const double (&u)[M::m], int col, const KArgs& a, const ModelParams<M>& par,
                                            double (&d)[M::n]) {
   constexpr int n = M::n, m = M::m;
   if (JAC == MI_JAC_FD_CENTRAL) {
@@ -631,8 +663,8 @@ __device__ __forceinline__ void jac_column(const double (&x)[M::n], const double
     for (int i = 0; i < n; ++i) { xp[i] = (col == i) ? x[i] + h : x[i]; xm[i] = (col == i) ? x[i] - h : x[i]; }
 #pragma unroll
     for (int k = 0; k < m; ++k) { up[k] = (col == n + k) ? u[k] + h : u[k]; um[k] = (col == n + k) ? u[k] - h : u[k]; }
-    M::template step<double>(xp, up, fp, a.params, a.dt);
-    M::template step<double>(xm, um, fm_, a.params, a.dt);
+    M::template step<double>(xp, up, fp, par.v, a.dt);
+    M::template step<double>(xm, um, fm_, par.v, a.dt);
 #pragma unroll
     for (int i = 0; i < n; ++i) d[i] = (fp[i] - fm_[i]) * inv2h;
   } else {
@@ -641,7 +673,7 @@ __device__ __forceinline__ void jac_column(const double (&x)[M::n], const double
     for (int i = 0; i < n; ++i) xd[i] = Dual1(x[i], (col == i) ? 1.0 : 0.0);
 #pragma unroll
     for (int k = 0; k < m; ++k) ud[k] = Dual1(u[k], (col == n + k) ? 1.0 : 0.0);
-    M::template step<Dual1>(xd, ud, fd, a.params, a.dt);
+    M::template step<Dual1>(xd, ud, fd, par.v, a.dt);
 #pragma unroll
     for (int i = 0; i < n; ++i) d[i] = fd[i].d;
   }
@@ -728,7 +760,7 @@ template <class M>
 struct NewtonMeasured<M, decltype((void)M::kNewtonRollout)> { static constexpr bool value = M::kNewtonRollout; };
 
 template <class M, int JAC, int CH>
-__device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const KArgs& a, const double* x0r, double eps,
+__device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const KArgs& a, const ModelParams<M>& par, const double* x0r, double eps,
                                           int fuse, double L_last, double& L_out, bool coarse) {
   constexpr int n = 2, m = 1;
   static_assert(M::n == 2 && M::m == 1, "2-state closed loop");
@@ -769,7 +801,7 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
       if (lane == j) { X[0][0] = xc[0]; X[0][1] = xc[1]; }
       double u[m], xn[n];
       u[0] = (cur.ub - eps * cur.kap) - (cur.kk[0] * (xc[0] - cur.xb[0]) + cur.kk[1] * (xc[1] - cur.xb[1]));
-      M::template step<double>(xc, u, xn, a.params, (double)CH * a.dt);
+      M::template step<double>(xc, u, xn, par.v, (double)CH * a.dt);
       xc[0] = xn[0]; xc[1] = xn[1];
       cur = nxt;
     }
@@ -778,7 +810,7 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
     for (int k = 0; k + 1 < CH; ++k) {
       double u[m], xn[n];
       u[0] = dd[k] - (Kk[k][0] * (X[k][0] - xb[k][0]) + Kk[k][1] * (X[k][1] - xb[k][1]));
-      M::template step<double>(X[k], u, xn, a.params, a.dt);
+      M::template step<double>(X[k], u, xn, par.v, a.dt);
       X[k + 1][0] = xn[0]; X[k + 1][1] = xn[1];
     }
   }
@@ -883,7 +915,7 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
         Dual2 xd[n] = {Dual2(X[k][0], 1.0, 0.0), Dual2(X[k][1], 0.0, 1.0)};
         Dual2 ud[m] = {dd[k] - (Kk[k][0] * (xd[0] - xb[k][0]) + Kk[k][1] * (xd[1] - xb[k][1]))};
         Dual2 xn[n];
-        M::template step<Dual2>(xd, ud, xn, a.params, a.dt);
+        M::template step<Dual2>(xd, ud, xn, par.v, a.dt);
 #pragma unroll
         for (int i = 0; i < n; ++i) {
           // (steps past the horizon evaluate record 0's data: their maps only enter the prefixes of later
@@ -898,7 +930,7 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
       for (int k = 0; k < CH; ++k) {
         double u[m] = {dd[k] - (Kk[k][0] * (X[k][0] - xb[k][0]) + Kk[k][1] * (X[k][1] - xb[k][1]))};
         double xn[n];
-        M::template step<double>(X[k], u, xn, a.params, a.dt);
+        M::template step<double>(X[k], u, xn, par.v, a.dt);
 #pragma unroll
         for (int i = 0; i < n; ++i) {
           const double nxt = (k + 1 < CH) ? X[(k + 1 < CH) ? k + 1 : k][i] : (i == 0 ? nx0 : nx1);
@@ -975,7 +1007,7 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
       if (valid[k]) {
         double u[m], xe[n];
         u[0] = dd[k] - (Kk[k][0] * (X[k][0] - xb[k][0]) + Kk[k][1] * (X[k][1] - xb[k][1]));
-        M::template step<double>(X[k], u, xe, a.params, a.dt);
+        M::template step<double>(X[k], u, xe, par.v, a.dt);
         const double nx_0 = (k + 1 < CH) ? X[(k + 1 < CH) ? k + 1 : k][0] : x_end[0];
         const double nx_1 = (k + 1 < CH) ? X[(k + 1 < CH) ? k + 1 : k][1] : x_end[1];
         const double d = fmax(fabs(xe[0] - nx_0), fabs(xe[1] - nx_1));
@@ -1048,7 +1080,7 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
 #pragma unroll
         for (int col = 0; col < n + m; ++col) {
           double d[n];
-          jac_column<M, JAC>(xk[k], uk[k], col, a, d);
+          jac_column<M, JAC>(xk[k], uk[k], col, a, par, d);
 #pragma unroll
           for (int i = 0; i < n; ++i) {
             if (col < n) j[Ly::FX + i * n + col] = d[i];
@@ -1071,10 +1103,10 @@ __device__ __forceinline__ bool newton_capable(const WS& w, const KArgs& a) {
   return false;
 }
 template <class M, int JAC>
-__device__ inline int rollout_newton(const WS& w, const Consts<M>& c, const KArgs& a, const double* x0r, double eps,
+__device__ inline int rollout_newton(const WS& w, const Consts<M>& c, const KArgs& a, const ModelParams<M>& par, const double* x0r, double eps,
                                      int fuse, double L_last, double& L_out, bool coarse = false) {
   if constexpr (M::n == 2 && M::m == 1 && !UsesLimits<M>::value) {
-    if (newton_capable<M>(w, a)) return rollout_newton_impl<M, JAC, 4>(w, c, a, x0r, eps, fuse, L_last, L_out, coarse);
+    if (newton_capable<M>(w, a)) return rollout_newton_impl<M, JAC, 4>(w, c, a, par, x0r, eps, fuse, L_last, L_out, coarse);
   }
   return NEWTON_FAILED;
 }
@@ -1093,7 +1125,7 @@ __device__ inline int rollout_newton(const WS& w, const Consts<M>& c, const KArg
 // `fused_out` reports what it did for the accepted trial (0: trajectory in T slot `slot_out`;
 // 1: already committed to the nominal records; 2: committed and linearized).
 template <class M, int JAC>
-__device__ inline bool linesearch(const WS& w, const Consts<M>& c, const KArgs& a, const double* x0r,
+__device__ inline bool linesearch(const WS& w, const Consts<M>& c, const KArgs& a, const ModelParams<M>& par, const double* x0r,
                                   double L_last, bool optimistic, int fuse, double& L_out, double& eps_out, int& trials,
                                   int& slot_out, int& fused_out, bool cold_start = false, bool no_newton = false) {
   fused_out = 0;
@@ -1105,8 +1137,8 @@ __device__ inline bool linesearch(const WS& w, const Consts<M>& c, const KArgs& 
   if (optimistic) {
     double L, ex;
     int nr = NEWTON_FAILED;
-    if (newton) nr = rollout_newton<M, JAC>(w, c, a, x0r, 1.0, fuse, L_last, L);
-    else if (cold_start && !no_newton && newton_capable<M>(w, a)) nr = rollout_newton<M, JAC>(w, c, a, x0r, 1.0, fuse, L_last, L, true);
+    if (newton) nr = rollout_newton<M, JAC>(w, c, a, par, x0r, 1.0, fuse, L_last, L);
+    else if (cold_start && !no_newton && newton_capable<M>(w, a)) nr = rollout_newton<M, JAC>(w, c, a, par, x0r, 1.0, fuse, L_last, L, true);
     if (nr == NEWTON_ACCEPTED) {
       L_out = L;
       eps_out = 1.0;
@@ -1122,7 +1154,7 @@ __device__ inline bool linesearch(const WS& w, const Consts<M>& c, const KArgs& 
 #ifdef MI_PROF_NEWTON
       const long long pr0 = clock64();
 #endif
-      if (!done) rollout<M, false>(w, c, a, x0r, 1.0, lane == 0 ? 0 : -1, L, ex);
+      if (!done) rollout<M, false>(w, c, a, par, x0r, 1.0, lane == 0 ? 0 : -1, L, ex);
       wave_sync();
 #ifdef MI_PROF_NEWTON
       const long long pr1 = clock64();
@@ -1148,7 +1180,7 @@ __device__ inline bool linesearch(const WS& w, const Consts<M>& c, const KArgs& 
     double L, ex;
     // the first n_store candidates keep their trajectories (coarse line searches, beta <= 0.75,
     // usually accept one of them: no second rollout needed)
-    rollout<M>(w, c, a, x0r, eps, lane < w.n_store ? lane : -1, L, ex);
+    rollout<M>(w, c, a, par, x0r, eps, lane < w.n_store ? lane : -1, L, ex);
     const bool acc = valid && ((L_last - L) > a.gamma * ex);   // ilqr.py:330-331
     const unsigned long long mask = __ballot(acc);
     if (mask != 0ull) {
@@ -1166,7 +1198,7 @@ __device__ inline bool linesearch(const WS& w, const Consts<M>& c, const KArgs& 
         const double eps_k = __shfl(eps, k);
         wave_sync();
         // (the sequential rollout of lane k already passed the acceptance test: L_last = inf here)
-        const int nr = rollout_newton<M, JAC>(w, c, a, x0r, eps_k, fuse, __builtin_inf(), L_out);
+        const int nr = rollout_newton<M, JAC>(w, c, a, par, x0r, eps_k, fuse, __builtin_inf(), L_out);
         if (nr == NEWTON_STORED) {
           wave_sync();
           double ex_;
@@ -1220,7 +1252,7 @@ __device__ inline void commit_trial(const WS& w, int slot) {
 // items over lanes.
 // ---------------------------------------------------------------------------
 template <class M, int JAC>
-__device__ __forceinline__ void jac_item(const WS& w, const KArgs& a, int t, int col) {
+__device__ __forceinline__ void jac_item(const WS& w, const KArgs& a, const ModelParams<M>& par, int t, int col) {
   constexpr int n = M::n, m = M::m;
   using Ly = Lay<n, m>;
   const double* g = w.G + t * Ly::GS;
@@ -1229,7 +1261,7 @@ __device__ __forceinline__ void jac_item(const WS& w, const KArgs& a, int t, int
   for (int i = 0; i < n; ++i) x[i] = g[Ly::XB + i];
 #pragma unroll
   for (int k = 0; k < m; ++k) u[k] = g[Ly::UB + k];
-  jac_column<M, JAC>(x, u, col, a, d);
+  jac_column<M, JAC>(x, u, col, a, par, d);
   double* j = w.J + t * Ly::JS;
   if (col < n) {
 #pragma unroll
@@ -1241,11 +1273,11 @@ __device__ __forceinline__ void jac_item(const WS& w, const KArgs& a, int t, int
 }
 
 template <class M, int JAC>
-__device__ __forceinline__ void jac_at(const WS& w, const KArgs& a, const int* list, int count) {
+__device__ __forceinline__ void jac_at(const WS& w, const KArgs& a, const ModelParams<M>& par, const int* list, int count) {
   constexpr int nc = M::n + M::m;
   for (int it = threadIdx.x; it < count * nc; it += 64) {
     const int ki = it / nc, col = it - ki * nc;
-    jac_item<M, JAC>(w, a, list[ki], col);
+    jac_item<M, JAC>(w, a, par, list[ki], col);
   }
 }
 
@@ -1261,23 +1293,23 @@ enum { TEAM_CMD_EXIT = 0, TEAM_CMD_LINEARIZE = 1 };
 typedef __attribute__((address_space(3))) volatile int lds_vint_t;      // explicit LDS pointer: ds_read/ds_write, not flat
 
 template <class M, int JAC>
-__device__ __forceinline__ void jac_rounds(const WS& w, const KArgs& a, int first, int stride, int lane) {
+__device__ __forceinline__ void jac_rounds(const WS& w, const KArgs& a, const ModelParams<M>& par, int first, int stride, int lane) {
   constexpr int nc = M::n + M::m;
   const int items = (w.N - 1) * nc;
   for (int it = 64 * first + lane; it < items; it += 64 * stride) {
     const int t = it / nc;
-    jac_item<M, JAC>(w, a, t, it - t * nc);
+    jac_item<M, JAC>(w, a, par, t, it - t * nc);
   }
 }
 
 template <class M, int JAC>
-__device__ inline void helper_wave(const WS& w, const KArgs& a, int wave, int team) {
+__device__ inline void helper_wave(const WS& w, const KArgs& a, const ModelParams<M>& par, int wave, int team) {
   const int lane = threadIdx.x & 63;
   lds_vint_t* cmd = (lds_vint_t*)w.aux;
   for (;;) {
     team_barrier();
     if (__builtin_amdgcn_readfirstlane(cmd[0]) == TEAM_CMD_EXIT) return;
-    jac_rounds<M, JAC>(w, a, wave, team, lane);
+    jac_rounds<M, JAC>(w, a, par, wave, team, lane);
     team_barrier();
   }
 }
@@ -1300,10 +1332,10 @@ struct SmallAcc {
 
 // _get_derivatives (ilqr.py:380-415) at the nominal trajectory in G.  Returns key-point count.
 template <class M, int JAC>
-__device__ inline int linearize(const WS& w, const KArgs& a) {
+__device__ inline int linearize(const WS& w, const KArgs& a, const ModelParams<M>& par) {
   SmallAcc<M::n, M::m> acc(w);
   return linearize_generic(acc, a.kp_method, a.minN, a.maxN, a.jerk_thr, a.err_thr,
-                           [&](const int* list, int count) __attribute__((always_inline)) { jac_at<M, JAC>(w, a, list, count); });
+                           [&](const int* list, int count) __attribute__((always_inline)) { jac_at<M, JAC>(w, a, par, list, count); });
 }
 
 template <int m>
@@ -2511,11 +2543,12 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
   const int lane = threadIdx.x;
   const int N = a.N;
   WS w = carve<n, m>(smem, N, a.n_store);
+  const ModelParams<M> par(a, param_row_of<M>(a, b));       // this problem's plant (the helper waves: the problem they serve)
   // Optional helper wavefronts (threads 64.., MODE_SOLVE / MODE_MPC with every step a key-point):
   // they only ever run helper_wave() - their share of the linearization.
   const int team = ((MODE == MODE_SOLVE || MODE == MODE_MPC) && a.helpers > 0) ? 1 + a.helpers : 1;
   if (team > 1 && threadIdx.x >= 64) {
-    helper_wave<M, JAC>(w, a, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), team);
+    helper_wave<M, JAC>(w, a, par, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), team);
     return;
   }
   lds_vint_t* team_cmd = (lds_vint_t*)w.aux;
@@ -2599,7 +2632,7 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
 
   if (MODE == MODE_ROLLOUT) {
     double L, ex;
-    rollout<M>(w, c, a, x0r, a.stage_in[b], lane == 0 ? 0 : -1, L, ex);
+    rollout<M>(w, c, a, par, x0r, a.stage_in[b], lane == 0 ? 0 : -1, L, ex);
     wave_sync();
     stage_out(a.x_trial + oX, w.T, Ly::TS, Ly::XN, n, N);
     stage_out(a.u_trial + oU, w.T, Ly::TS, Ly::UN, m, N - 1);
@@ -2607,7 +2640,7 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
     return;
   }
   if (MODE == MODE_LINEARIZE) {
-    const int nk = linearize<M, JAC>(w, a);
+    const int nk = linearize<M, JAC>(w, a, par);
     stage_out(a.fx + oFx, w.J, Ly::JS, Ly::FX, n * n, N - 1);
     stage_out(a.fu + oFu, w.J, Ly::JS, Ly::FU, n * m, N - 1);
     for (int i = lane; i < nk; i += 64) a.kp_list[(size_t)b * (N - 1) + i] = w.kp[i];
@@ -2690,7 +2723,7 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
       int fused = 0;
       // first iteration of the first solve on all-zero solver state (no gains, no nominal trajectory)
       const bool cold_start = cold && rs == 0 && it_this == 0 && (MODE == MODE_SOLVE || MODE == MODE_MPC);
-      const bool ok = linesearch<M, JAC>(w, c, a, x0r, L, optimistic, fuse, L_new, eps, trials, slot, fused, cold_start);
+      const bool ok = linesearch<M, JAC>(w, c, a, par, x0r, L, optimistic, fuse, L_new, eps, trials, slot, fused, cold_start);
       // expect eps = 1 next time if it was accepted now - or whenever the attempt is the cheap one
       // (sequential attempts: only after TWO first-trial acceptances in a row - on coarse line
       // searches a lone one is usually followed by a backtrack, and the failed attempt costs a rollout)
@@ -2708,14 +2741,14 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
         nk = N - 1;                                               // every step is a key-point (:396, :414)
         if (lane == 0) team_cmd[0] = TEAM_CMD_LINEARIZE;
         team_barrier();
-        jac_rounds<M, JAC>(w, a, 0, team, lane);
+        jac_rounds<M, JAC>(w, a, par, 0, team, lane);
         team_barrier();
       } else if (every_step) {                                    // same, without helpers or the key-point list
         nk = N - 1;
-        jac_rounds<M, JAC>(w, a, 0, 1, lane);
+        jac_rounds<M, JAC>(w, a, par, 0, 1, lane);
         wave_sync();
       } else {
-        nk = linearize<M, JAC>(w, a);                             // at the ACCEPTED trajectory (:370)
+        nk = linearize<M, JAC>(w, a, par);                        // at the ACCEPTED trajectory (:370)
       }
       const long long c2 = clock64();
       bool pd = true;

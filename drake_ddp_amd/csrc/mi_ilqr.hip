@@ -183,6 +183,8 @@ KArgs make_args(const mi_ilqr* h) {
   a.s2 = h->s2;
   a.x_nom_rows = h->per_problem_targets ? h->x_nom_rows : nullptr;
   a.target_steps = h->per_problem_targets ? h->target_steps : nullptr;
+  a.param_rows = h->per_problem_params ? h->param_rows : nullptr;
+  a.param_cols = (h->per_problem_params && h->batch_minor) ? h->param_cols : nullptr;
   a.spec_policy = h->x_spec ? sw.spec : 0;
   a.cluster = 1;
   a.cluster_sync = h->cluster_sync;
@@ -797,7 +799,7 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
   void* ptrs[] = {h->x_bar, h->u_bar, h->K, h->kappa, h->dV, h->fx, h->fu, h->x0, h->u_guess, h->cost_ring, h->hist, h->iter_cyc,
                   h->x_trial, h->u_trial, h->trial_cost, h->stage_in, h->costmat, h->iters_ring, h->status_ring, h->ls_ring,
                   h->kp_count, h->kp_list, h->prof, h->done_counter, h->cluster_sync, h->bm_scratch, h->x_spec, h->u_spec, h->lxu,
-                  h->ulim, h->s2, h->x_nom_rows, h->target_steps};
+                  h->ulim, h->s2, h->x_nom_rows, h->target_steps, h->param_rows, h->param_cols};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->mpc_log) (void)hipFree(h->mpc_log);
@@ -903,6 +905,52 @@ static int advance_per_problem_targets(mi_ilqr* h, int32_t times) {
   for (int32_t r = 0; r < times; ++r)
     for (size_t i = 0; i < cnt; ++i) h->h_x_nom_rows[i] += h->h_target_steps[i];
   return stage_h2d(h, h->x_nom_rows, h->h_x_nom_rows.data(), cnt * 8);
+}
+
+// Per-problem model parameters (MI_F_MODEL_PARAMS): (B, n_params) rows, problem b's plant in row b.  The host mirror h_param_rows
+// is what mi_ilqr_get returns; the device copies - the rows, and the same values batch-minor for the lane-per-problem kernels -
+// follow it on the handle's stream.  src == NULL with bytes == 0: back to the descriptor's parameters.
+static int set_model_params(mi_ilqr* h, const double* src, size_t bytes) {
+  const size_t B = h->B, np = model_of(h->d.model_id)->p.n_params;
+  if (np == 0) return MI_ILQR_E_UNSUPPORTED;
+  if (!src && bytes == 0) {                  // shared mode again: the kernels read KArgs::params, as on a handle that never left it
+    h->per_problem_params = false;
+    h->h_param_rows.clear();
+    return MI_ILQR_OK;
+  }
+  if (bytes != B * np * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  for (size_t i = 0; i < B * np; ++i) if (!std::isfinite(src[i])) return MI_ILQR_E_BAD_ARG;
+  HIPCHK(hipSetDevice(h->d.device_id));
+  if (!h->param_rows) {
+    double *rows = nullptr, *cols = nullptr;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&rows), bytes));
+    if (hipMalloc(reinterpret_cast<void**>(&cols), bytes) != hipSuccess) { (void)hipFree(rows); return MI_ILQR_E_HIP; }
+    h->param_rows = rows; h->param_cols = cols;
+  }
+  std::vector<double> cols(B * np);
+  for (size_t b = 0; b < B; ++b)
+    for (size_t k = 0; k < np; ++k) cols[k * B + b] = src[b * np + k];
+  // kernels already enqueued (mi_ilqr_solve_async) read the previous rows: stage_h2d copies on the handle's stream, behind them
+  int rc = stage_h2d(h, h->param_rows, src, bytes);
+  if (rc == MI_ILQR_OK) rc = stage_h2d(h, h->param_cols, cols.data(), bytes);
+  if (rc != MI_ILQR_OK) {                    // the device copies are undefined now: the handle falls back to what it can vouch for
+    h->per_problem_params = false;
+    h->h_param_rows.clear();
+    return rc;
+  }
+  h->h_param_rows.assign(src, src + B * np);
+  h->per_problem_params = true;
+  return MI_ILQR_OK;
+}
+
+static int get_model_params(mi_ilqr* h, double* dst, size_t bytes) {
+  const size_t B = h->B, np = model_of(h->d.model_id)->p.n_params;
+  if (np == 0) return MI_ILQR_E_UNSUPPORTED;
+  if (bytes != B * np * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (h->per_problem_params) std::memcpy(dst, h->h_param_rows.data(), bytes);
+  else for (size_t b = 0; b < B; ++b) std::memcpy(dst + b * np, h->d.model_params, np * 8);
+  return MI_ILQR_OK;
 }
 
 int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const double* Qf, const double* x_nom) {
@@ -1403,6 +1451,7 @@ int mi_ilqr_get_mpc_log(mi_ilqr_t* h, double* dst, size_t bytes) {
 int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
   if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return get_target_field(h, which, dst, bytes);
+  if (which == MI_F_MODEL_PARAMS) return get_model_params(h, dst, bytes);
   Field f = field_of(h, which);
   if (!f.ptr || f.is_int) return MI_ILQR_E_BAD_ARG;
   if (bytes != f.bytes && !prefix_ok(which, bytes, f.bytes)) return MI_ILQR_E_BAD_SHAPE;
@@ -1432,6 +1481,7 @@ int mi_ilqr_get_async(mi_ilqr_t* h, int which, void* dst, size_t bytes) {
     HIPCHK(hipStreamSynchronize(h->stream));
     return get_target_field(h, which, static_cast<double*>(dst), bytes);
   }
+  if (which == MI_F_MODEL_PARAMS) return get_model_params(h, static_cast<double*>(dst), bytes);   // (a host mirror as well)
   Field f = field_of(h, which);
   if (!f.ptr) return MI_ILQR_E_BAD_ARG;
   if (bytes != f.bytes && !prefix_ok(which, bytes, f.bytes)) return MI_ILQR_E_BAD_SHAPE;
@@ -1470,6 +1520,7 @@ int mi_ilqr_get_int(mi_ilqr_t* h, int which, int32_t* dst, size_t bytes) {
 }
 
 int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
+  if (h && which == MI_F_MODEL_PARAMS) return set_model_params(h, src, bytes);   // (src == NULL, bytes == 0: back to shared mode)
   if (!h || !src) return MI_ILQR_E_BAD_ARG;
   if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return set_target_field(h, which, src, bytes);
   Field f = field_of(h, which);
@@ -1499,6 +1550,12 @@ int mi_ilqr_device_ptr(mi_ilqr_t* h, int which, void** ptr, size_t* bytes) {
     if (!h->per_problem_targets) return MI_ILQR_E_BAD_ARG;
     *ptr = which == MI_F_X_NOM ? h->x_nom_rows : h->target_steps;
     if (bytes) *bytes = (size_t)h->B * h->n * 8;
+    return MI_ILQR_OK;
+  }
+  if (which == MI_F_MODEL_PARAMS) {                            // per-problem mode only: the (B, n_params) device rows
+    if (!h->per_problem_params) return MI_ILQR_E_BAD_ARG;
+    *ptr = h->param_rows;
+    if (bytes) *bytes = h->h_param_rows.size() * 8;
     return MI_ILQR_OK;
   }
   Field f = field_of(h, which);

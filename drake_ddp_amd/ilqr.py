@@ -40,6 +40,26 @@ class _PinnedBlock:
         self.busy = False
 
 
+def check_model_params(params, B, n_params):
+    """SetModelParameters' argument as a contiguous (B, n_params) float64 array ((n_params,) is broadcast to rows), or None for
+    None.  ValueError for any other shape and for NaN / infinity - decided here, before anything reaches the device."""
+    if params is None:
+        return None
+    if n_params == 0:
+        raise ValueError("SetModelParameters: this model has no parameters")
+    try:
+        a = np.asarray(params, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"SetModelParameters: not an array of numbers ({e})") from None
+    if a.shape == (n_params,):
+        a = np.broadcast_to(a, (B, n_params))
+    elif a.shape != (B, n_params):
+        raise ValueError(f"SetModelParameters: parameters must be ({B}, {n_params}) or ({n_params},); got {a.shape}")
+    if not np.isfinite(a).all():
+        raise ValueError("SetModelParameters: NaN or infinity")
+    return np.ascontiguousarray(a)
+
+
 class BatchedIterativeLQR:
     """B independent iLQR problems sharing model, horizon and cost, solved on one GPU.
 
@@ -153,6 +173,21 @@ class BatchedIterativeLQR:
     def _set_field(self, which, a):
         a = _capi.as_f64(a, (self.B, self.n))
         _capi.check(self._lib.mi_ilqr_set(self._h, which, _capi.ptr(a), a.nbytes), "mi_ilqr_set")
+
+    def SetModelParameters(self, params):
+        """(B, n_params): every problem its own plant - the reference's one solver object per System, B of them in one handle
+        (include/mi_ilqr.h: "Per-problem model parameters").  (n_params,): that row for every problem.  None: back to the
+        parameters of the system the solver was built with.  Takes effect for the next solve; survives Reset()."""
+        rows = check_model_params(params, self.B, int(self.system.params.size))
+        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_MODEL_PARAMS, _capi.ptr(rows), 0 if rows is None else rows.nbytes),
+                    "mi_ilqr_set")
+
+    @property
+    def model_params(self):
+        """(B, n_params): the parameters each problem is solved with (the system's own row repeated unless SetModelParameters gave others)."""
+        out = np.empty((self.B, int(self.system.params.size)))
+        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_MODEL_PARAMS, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+        return out
 
     def SetRunningCost(self, Q, R):
         assert Q.shape == (self.n, self.n)

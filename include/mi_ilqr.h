@@ -122,6 +122,7 @@ enum {
                            wave- and workgroup-per-problem kernels */
   MI_F_X_NOM = 14,      /* (B,n) per-problem targets x_nom_b (mi_ilqr_set_cost, "Per-problem targets" below)              */
   MI_F_TARGET_STEP = 15,/* (B,n) per-problem target_step_b of mi_ilqr_mpc_run                                             */
+  MI_F_MODEL_PARAMS = 16,/* (B,n_params) per-problem model parameters: problem b's plant ("Per-problem model parameters" below) */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
@@ -263,6 +264,21 @@ int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const doubl
  *   mi_ilqr_set_cost with a non-NULL x_nom returns the handle to shared mode and drops both fields: it is then bitwise a
  *   never-per-problem one.  Targets are problem data: they survive mi_ilqr_reset.  Wrong `bytes` is MI_ILQR_E_BAD_SHAPE, a NaN
  *   MI_ILQR_E_BAD_ARG (the handle keeps what it had).  Every kernel family, solve, mpc_run and the stage entries. */
+
+/* Per-problem model parameters (the reference builds one solver object per System: B objects may be B plants of one structure -
+ * domain-randomised MPC, parameter sweeps, picking the plant whose plan matches a measurement).  The model, dt and the costs stay
+ * shared by the batch; the parameters are mi_ilqr_desc.model_params until
+ *   mi_ilqr_set(MI_F_MODEL_PARAMS, rows, B*n_params*8)  gives problem b row b of the (B,n_params) array (n_params:
+ *                                        mi_ilqr_model_info) and switches the handle to PER-PROBLEM PARAMETERS;
+ *   mi_ilqr_set(MI_F_MODEL_PARAMS, NULL, 0)  returns it to the descriptor's parameters: it is then bitwise a handle that never left them;
+ *   mi_ilqr_get returns the (B,n_params) rows in both modes (shared mode: the descriptor's row repeated);
+ *   mi_ilqr_device_ptr returns the (B,n_params) device rows in per-problem mode (MI_ILQR_E_BAD_ARG in shared mode); whoever writes
+ *   them on the device must leave them alone while a solve runs (the lane-per-problem kernels read a copy of their own, made by
+ *   mi_ilqr_set: write through mi_ilqr_set there).
+ * The rows are problem data: they survive mi_ilqr_reset.  Errors: wrong `bytes` MI_ILQR_E_BAD_SHAPE; a NaN or an infinity
+ * MI_ILQR_E_BAD_ARG; a model without parameters (n_params == 0) MI_ILQR_E_UNSUPPORTED; a refused call changes nothing.  Every
+ * kernel family (cluster helpers and helper wavefronts read the row of the problem they serve), control-limited handles, solve,
+ * mpc_run in both forms and the stage entries; it combines with per-problem targets and per-problem control limits. */
 
 /* SetInitialState / SetInitialGuess (ilqr.py:102-109,148-156): x0 (B,n), u_guess (B,m,N-1).
  * u_guess becomes u_bar (the reference aliases it, ilqr.py:156).  NULL = keep.
