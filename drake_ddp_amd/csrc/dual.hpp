@@ -82,17 +82,9 @@ __host__ __device__ inline Dual2 operator/(double a, Dual2 b) {
 }
 __host__ __device__ inline double value_of(Dual2 a) { return a.v; }
 // The time-parallel rollout's Newton sweeps need cos only as the SLOPE of sin: fast_sin_slope (fastmath.hpp) - the value bit for
-// bit fast_sin, the slope to 1e-10 from the same reduction.  Same-box A/B, round 6 (tools/diag/build_variant.py cc1
-// -DMI_DUAL2_CHEAP_COS=1 against =0, three runs each): C2 43.5 -> 44.4 M it/s (kernel 0.1405 -> 0.1376 ms), the same 6193
-// iterations per step.
-#ifndef MI_DUAL2_CHEAP_COS
-#define MI_DUAL2_CHEAP_COS 1
-#endif
-#if MI_DUAL2_CHEAP_COS
+// bit fast_sin, the slope to 1e-10 from the same reduction.  Same-box A/B, round 6, against fast_sin + fast_cos (three runs
+// each): C2 43.5 -> 44.4 M it/s (kernel 0.1405 -> 0.1376 ms), the same 6193 iterations per step.
 __device__ inline Dual2 mi_sin(Dual2 a) { double c_; const double s_ = fast_sin_slope(a.v, c_); return {s_, c_ * a.d0, c_ * a.d1}; }
-#else
-__device__ inline Dual2 mi_sin(Dual2 a) { const double c_ = fast_cos(a.v); return {fast_sin(a.v), c_ * a.d0, c_ * a.d1}; }
-#endif
 __device__ inline Dual2 mi_cos(Dual2 a) { const double s_ = -fast_sin(a.v); return {fast_cos(a.v), s_ * a.d0, s_ * a.d1}; }
 __device__ inline Dual2 mi_rcp(Dual2 a) { const double r = fast_rcp(a.v), q = -(r * r); return {r, q * a.d0, q * a.d1}; }
 // The rest of the primitive set, so that one step() body serves double, Dual1 and Dual2 alike (plugin.py): the values and
@@ -103,22 +95,15 @@ __device__ inline Dual2 mi_log1p(Dual2 a) { const double g = 1.0 + a.v; return {
 
 // log(1+exp(z)) = max(z,0) + log1p(exp(-|z|)), overflow-safe and branch-free; same value as the
 // two-branch form of oracle/dual.py:softplus.  d/dz = logistic(z).
-// MI_SOFTPLUS_SKIP (round 6): once t = exp(-|z|) < 2^-53, fast_log1p01(t) returns t itself, bit for bit (f = t, 2 + f rounds to 2,
-// its reciprocal is exactly 0.5, s = t / 2, and the series term s w R ~ t^3 / 12 is below half an ulp of 2 s = t), so a wave whose
-// every lane is that far from the contact leaves the logarithm - a third of the step's dependency chain - out: one compare
-// and a scalar branch; the same bits either way.  (Branch per wave, not per lane: lanes in contact keep everybody on the long path.)
-// MEASURED, and OFF by default: in the one-wave microbenchmark the step gets 7 - 11 % shorter (tools/ubench/chain_step.hip: 715 -> 666 /
-// 635 cycles), inside the fused solve kernel it gets 12 % LONGER (same-box A/B, profiles/r06_c4_ab.txt: C4's line search 178.6 k ->
-// 201.1 k cycles per iteration) - the branch splits the rollout loop's body, both arms stay resident, and the loop that held its
-// values in 293 instructions without a register move now carries 36 v_accvgpr moves in 352 (tools/isa_mix.py).
-#ifndef MI_SOFTPLUS_SKIP
-#define MI_SOFTPLUS_SKIP 0
-#endif
+// No short cut for lanes far from the contact: once t = exp(-|z|) < 2^-53, fast_log1p01(t) returns t itself, bit for bit, so a
+// wave whose every lane is that far away could leave the logarithm - a third of the step's dependency chain - out behind one
+// compare and a scalar branch.  MEASURED (round 6, docs/ENGINEERING_LOG_r06.md): in the one-wave microbenchmark the step got
+// 7 - 11 % shorter (profiles/r06_chain_step.txt: 715 -> 666 / 635 cycles), inside the fused solve kernel 12 % LONGER
+// (profiles/r06_c4_ab.txt: C4's line search 178.6 k -> 201.1 k cycles per iteration) - the branch splits the rollout loop's body,
+// both arms stay resident, and the loop that held its values in 293 instructions without a register move carried 36 v_accvgpr
+// moves in 352.
 __device__ inline double mi_softplus(double z, const SoftplusPool& c) {
   const double t = fast_exp_nonpos(-fabs(z), c);
-#if MI_SOFTPLUS_SKIP
-  if (__builtin_amdgcn_ballot_w64(!(t < 0x1p-53)) == 0ull) return fmax(z, 0.0) + t;
-#endif
   return fmax(z, 0.0) + fast_log1p01(t, c);
 }
 __device__ inline double mi_softplus(double z) { return mi_softplus(z, SoftplusPool::literals()); }

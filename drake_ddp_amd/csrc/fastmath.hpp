@@ -38,45 +38,29 @@ constexpr double kLn2Hi = 0x1.62e42fee00000p-1, kLn2Lo = 0x1.a39ef35793c76p-33, 
 
 // Polynomial evaluation.  These kernels run ONE instruction stream per problem at one wave per SIMD: if a dependent fp64 operation
 // waited ~8 cycles for its operand while an independent one issues every 4, what a rollout step costs would be the DEPTH of its
-// dependency chain - so round 6 assumed, and built Estrin's scheme (MI_POLY_ESTRIN=1: the same polynomial in
+// dependency chain - so round 6 assumed, and built Estrin's scheme (the same polynomial in
 // ceil(log2(degree + 1)) + 1 levels of independent multiply-adds for two or three more multiplications) to shorten it.  MEASURED
-// (tools/ubench/chain_step.hip, one wave, dependent steps; profiles/r06_chain_step.txt): SLOWER - cart-pole + wall 715 -> 725
+// (one wave, dependent steps; profiles/r06_chain_step.txt, docs/ENGINEERING_LOG_r06.md): SLOWER - cart-pole + wall 715 -> 725
 // cycles per step, acrobot 670 -> 694 - and less accurate (3 ulp against Horner's 2, tools/ubench/trig_acc.hip).  The reason
 // (tools/ubench/issue_interval.hip, profiles/r06_issue_interval.txt): ONE wave issues a v_fma_f64 every 4.04 cycles from
 // independent chains and every 4.17 from a single DEPENDENT chain - a dependent fp64 operation issues back to back, there is no
 // latency for Estrin's independent multiply-adds to hide, only more instructions to issue.  What a step costs at one wave per
 // SIMD is its instruction COUNT.  Horner stays.
-#ifndef MI_POLY_ESTRIN
-#define MI_POLY_ESTRIN 0
-#endif
 // c[0] + c[1] x + ... + c[10] x^10
 template <class C>
 __device__ __forceinline__ double poly10(const C& c, double x) {
-#if MI_POLY_ESTRIN
-  const double x2 = x * x, x4 = x2 * x2, x8 = x4 * x4;
-  const double a0 = fma(c[1], x, c[0]), a1 = fma(c[3], x, c[2]), a2 = fma(c[5], x, c[4]), a3 = fma(c[7], x, c[6]), a4 = fma(c[9], x, c[8]);
-  const double b0 = fma(a1, x2, a0), b1 = fma(a3, x2, a2), b2 = fma(c[10], x2, a4);
-  return fma(b2, x8, fma(b1, x4, b0));
-#else
   double p = c[10];
 #pragma unroll
   for (int k = 9; k >= 0; --k) p = fma(p, x, c[k]);
   return p;
-#endif
 }
 // c[0] + c[1] x + ... + c[7] x^7
 template <class C>
 __device__ __forceinline__ double poly7(const C& c, double x) {
-#if MI_POLY_ESTRIN
-  const double x2 = x * x, x4 = x2 * x2;
-  const double a0 = fma(c[1], x, c[0]), a1 = fma(c[3], x, c[2]), a2 = fma(c[5], x, c[4]), a3 = fma(c[7], x, c[6]);
-  return fma(fma(a3, x2, a2), x4, fma(a1, x2, a0));
-#else
   double p = c[7];
 #pragma unroll
   for (int k = 6; k >= 0; --k) p = fma(p, x, c[k]);
   return p;
-#endif
 }
 
 // sin of a reduced argument |r| <= pi/2 (+ small margin)

@@ -195,13 +195,9 @@ __device__ __forceinline__ void cluster_release() {
 __device__ __forceinline__ void cluster_acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
 // XCC (= XCD) this wave runs on
 __device__ __forceinline__ int xcc_id() {
-#ifdef MI_NO_XCC
-  return 0;
-#else
   unsigned x;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
   return (int)(x & 15u);
-#endif
 }
 
 // Models whose step is an articulated-body algorithm cut into chains (models.hpp: PlanarQuad): cooperative
@@ -285,19 +281,12 @@ __device__ __forceinline__ void trig_gather(double v, double (&S)[NJ], double (&
 // prog != nullptr: the rollout PUBLISHES the trial as it goes, for helper workgroups that linearize it while it is still being
 // rolled out (ilqr_large_kernel: early linearization).  x_t, u_t then leave as agent-scope (write-through) stores - all from the
 // fourth wave - and lane 192 stores `tag | s` into *prog once the steps 0 .. s-1 are complete at agent scope (form (A) of the
-// hand-shake above; the helpers read the rows with agent-scope loads).  How it knows:
-//   MI_PUB_LAG = 0 (default): at the top of step t, BEFORE this step's stores are issued, the wave drains its vector-memory counter
-//     - s_waitcnt vmcnt(0): every store it has issued (steps 0 .. t-1) is complete - and publishes s = t.  No assumption about the
-//     order in which operations complete, none about how long a step takes (round 5's form rested on both, and was opened for the
-//     built-in models only).  What the wave waits for is at least half a step old (u_{t-1} left in the middle of step t-1).
-//   MI_PUB_LAG = k > 0 (A/B builds): the counted form - s_waitcnt vmcnt(3 k) "all but the youngest 3 k operations are complete" and
-//     s = t - k.  Right only while the wave has nothing but stores in flight (operations of one kind complete in the order issued;
-//     a load - a register spill's reload, say - would not be ordered with them).
-#ifndef MI_PUB_LAG
-#define MI_PUB_LAG 0
-#endif
-constexpr int kPubLag = MI_PUB_LAG;
-static_assert(kPubLag >= 0 && 3 * kPubLag <= 15, "the counted wait of large_rollout's publisher sits in the 4-bit low field of s_waitcnt's vmcnt");
+// hand-shake above; the helpers read the rows with agent-scope loads).  How it knows: at the top of step t, BEFORE this step's
+// stores are issued, the wave drains its vector-memory counter - s_waitcnt vmcnt(0): every store it has issued (steps 0 .. t-1) is
+// complete - and publishes s = t.  No assumption about the order in which operations complete, none about how long a step takes
+// (round 5's form rested on both, and was opened for the built-in models only).  What the wave waits for is at least half a step
+// old (u_{t-1} left in the middle of step t-1).  (A counted wait - s_waitcnt vmcnt(3 k), publishing s = t - k - is right only
+// while the wave has nothing but stores in flight, and measured within +- 0.5 % of this form: docs/ENGINEERING_LOG_r03_r05.md.)
 constexpr unsigned long long kPubAbort = 0x80000000ull;      // *prog = tag | kPubAbort: the trial was rejected, stop linearizing it
 // Blocks at the END of the horizon that the leader linearizes itself once the trial is accepted (early rounds): models whose
 // helpers cannot keep up with the rollout (planar quadruped: an item is two passes over the tree, ~78 k cycles) - the last
@@ -432,16 +421,8 @@ __device__ inline double large_rollout(const LView<M::n, M::m>& v, double* lds, 
       dxc[tid - 192] = xv_ - xnr;
       if (prog) {
         if (tid == 192 && t >= 1) {
-          if constexpr (kPubLag == 0) {
-            drain_stores();                                  // steps 0 .. t-1: every store this wave has issued is complete
-            __hip_atomic_store(prog, tag | (unsigned long long)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          } else {
-            // every step from the second on publishes (a count of zero claims nothing), so the wave has issued exactly
-            // (publish, x, u) x kPubLag operations since u_{t-1-kPubLag}: all but that many complete = steps 0 .. t-1-kPubLag out
-            if (t > kPubLag) __builtin_amdgcn_s_waitcnt(0x0F70 | (3 * kPubLag));
-            asm volatile("" ::: "memory");
-            __hip_atomic_store(prog, tag | (unsigned long long)(t > kPubLag ? t - kPubLag : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
+          drain_stores();                                    // steps 0 .. t-1: every store this wave has issued is complete
+          __hip_atomic_store(prog, tag | (unsigned long long)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
       // a published trial leaves in agent-scope stores (form (A) of the hand-shake: the helpers read it with agent-scope loads)
@@ -589,9 +570,6 @@ __device__ inline double large_rollout(const LView<M::n, M::m>& v, double* lds, 
       for (int j = 0; j < m; ++j) r += rrow[j] * us[j];
       acc += us[k] * r;
       if constexpr (kLx) lxu_store(v, Lxu, t * (n + m) + n + k, 2.0 * r);
-#ifdef MI_UN_RROLE
-      v.Un[(size_t)t * m + k] = us[k];
-#endif
     } else if (uorole) {
       const int k = tid - 192 - n;
       if (prog) st_shared<true>(v.Un + (size_t)t * m + k, us[k]);
@@ -1306,11 +1284,7 @@ struct TileOps {
 // that updates its column, and a column written in pivot K is read again no earlier than m - 2 + 8 instructions later.
 // (m < 4: the compiler's form - the elimination is bound by its serial chain there and the fixed s_nops only add to it.  Measured,
 // cycles per inverse, tools/ubench/gj_fmac.hip: m = 7 845 -> 829, m = 12 2 053 -> 1 609, m = 16 3 435 -> 2 416; same bits.)
-#ifndef MI_GJ_MOV_FMA
 template <int m> constexpr bool kGjAsm = m >= 4;
-#else
-template <int m> constexpr bool kGjAsm = false;
-#endif
 template <int K, bool ASM>
 __device__ __forceinline__ void fmac_row_share(double& a, double g) {
   if constexpr (ASM) asm("v_fmac_f64_dpp %0, -%0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "+v"(a) : "v"(g), "n"(K));
@@ -1507,13 +1481,8 @@ __device__ __forceinline__ void quu_inverse_pivoted(double* W_, int ws, int lane
 // OPERAND DELIVERY: two 8-byte operands per lane feed 1024 FMAs, where a VALU formulation needs a (broadcast) LDS
 // read per 1-2 FMAs and is LDS-issue-bound at one wave per SIMD (tools/ubench/t1.hip: 4.5-10.7 k cycles for T1
 // alone) - and since round 3 most operands do not even come from LDS: see "Fused chain" below.
-#ifdef MI_BACKWARD_NOINLINE
-#define MI_BP_INLINE __attribute__((noinline))
-#else
-#define MI_BP_INLINE inline
-#endif
 template <class M, bool PIV = true>
-__device__ MI_BP_INLINE void large_backward(const LView<M::n, M::m>& v, double* lds, long long* bp_acc = nullptr, bool lx_ready = false) {
+__device__ inline void large_backward(const LView<M::n, M::m>& v, double* lds, long long* bp_acc = nullptr, bool lx_ready = false) {
   constexpr int n = M::n, m = M::m, nm = n + m;
   using Ly = LLay<n, m>;
   constexpr int TS = Ly::TS, VS = Ly::VS, FS = Ly::NMP, NP = Ly::NP;
@@ -2105,7 +2074,7 @@ __device__ MI_BP_INLINE void large_backward(const LView<M::n, M::m>& v, double* 
 // its column, like the reference's dense update); only Quu is formed from the transposed column tiles (= the transpose of a
 // matrix that is symmetric up to round-off), which takes it off the step's critical path.  Two barriers per step.
 template <class M, bool PIV = true>
-__device__ MI_BP_INLINE void mid_backward(const LView<M::n, M::m>& v, double* lds, bool lx_ready = false, bool xu_staged = false) {
+__device__ inline void mid_backward(const LView<M::n, M::m>& v, double* lds, bool lx_ready = false, bool xu_staged = false) {
   constexpr int n = M::n, m = M::m, nm = n + m;
   using Ly = LLay<n, m>;
   static_assert(Ly::kMid && Ly::kSplit && m >= 1 && m <= 16, "mid-size family: n <= 32, m <= 16");
@@ -3005,15 +2974,11 @@ __device__ __forceinline__ void backward_pass(const LView<M::n, M::m>& v, double
   }
 }
 
-#ifndef MI_MID_MINBLOCKS
-#define MI_MID_MINBLOCKS 1
-#endif
-template <class M>
-constexpr int kMinBlocks = LLay<M::n, M::m>::kMid ? MI_MID_MINBLOCKS : 1;
 // PIV: the backward passes carry the pivoted-inverse cold path (quu_inverse_pivoted) - launched for on_indefinite = 1 and for cost
 // matrices that are not symmetric; modes without a backward pass exist as PIV = false only.
+// One workgroup per CU, the mid-size kernels too: two (128 + 128 registers) were measured slower, docs/ENGINEERING_LOG_r03_r05.md.
 template <class M, int JAC, int MODE, bool PIV = false>
-__global__ void __launch_bounds__(kLargeThreads, kMinBlocks<M>) ilqr_large_kernel(const KArgs a) {
+__global__ void __launch_bounds__(kLargeThreads, 1) ilqr_large_kernel(const KArgs a) {
   constexpr int n = M::n, m = M::m;
   using Ly = LLay<n, m>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -3159,10 +3124,7 @@ __global__ void __launch_bounds__(kLargeThreads, kMinBlocks<M>) ilqr_large_kerne
     else if constexpr (IsLegModel<M>::value) large_jac_at_legs<M, JAC, true>(v, a, list, count, lin_X, lin_U, lin_xs, lin_us, first, stride);
     else large_jac_at<M, JAC, true>(v, a, list, count, lin_X, lin_U, lin_xs, lin_us, first, stride);
   };
-#ifndef MI_SPIN_CAP_SHIFT
-#define MI_SPIN_CAP_SHIFT 22
-#endif
-  constexpr long long kSpinCap = 1ll << MI_SPIN_CAP_SHIFT;                 // x s_sleep(4) ~ 1 s: a lost partner ends the wait, not the device
+  constexpr long long kSpinCap = 1ll << 22;                                // x s_sleep(4) ~ 1 s: a lost partner ends the wait, not the device
   if (role > 0) {
     // ---- helper workgroup
     if (!clustered) return;

@@ -99,7 +99,7 @@ struct KArgs {
   // rolled out beside the first, [3][B][N][n] and [3][B][N-1][m]
   double *x_spec, *u_spec;
   int spec_policy;
-  int q_diag;                     // Q has no off-diagonal entry (every script of the reference): the sequential rollouts' stage cost skips the n (n - 1) products with zeros
+  int q_diag;                     // Q has no off-diagonal entry (mi_ilqr_set_cost detects it).  No kernel reads it at present: see stage_cost
   // workgroup-per-problem kernels, long horizons: the cost gradients [B][N-1][n+m] in HBM instead of LDS (ilqr_large.hpp)
   double* lxu;
   int pd_continue;                // mi_ilqr_desc.on_indefinite
@@ -166,9 +166,7 @@ __device__ __forceinline__ const double* param_row_of(const KArgs& a, size_t b) 
 // on the wave-per-problem kernels of this file it changes nothing - C2 43.19 M it/s either way - and they keep threadIdx.x).
 __device__ __forceinline__ int stage_lane() {
   int t = threadIdx.x;
-#ifndef MI_NO_STAGE_TID
   asm volatile("" : "+v"(t));
-#endif
   return t;
 }
 
@@ -403,36 +401,23 @@ struct Consts : LimitRegs<M> {
 // Lane 0 stores its trajectory into the T records; the other lanes' stores go
 // to a per-lane dump slot so the loop carries no exec-mask branches.
 // ---------------------------------------------------------------------------
-// q_diag (wave-uniform: a kernel argument): Q is diagonal - the products with its zeros are left out.  Same bits: a row sum then is
-// fma(0, dx_j, s) = s for every j != i (finite states; a diverged trial's cost is NaN or inf either way, and rejected either way).
-// 12 of the 146 instructions of a cart-pole + wall rollout step - and, MEASURED in the fused kernel (same-box A/B,
-// profiles/r06_c4_ab.txt), a line search that is 26 % LONGER (178.6 k -> 224.9 k cycles per iteration): the second arm of the branch
-// lives in the same loop, and its registers push the loop's values into the accumulation file.  OFF by default (MI_STAGE_COST_DIAG).
+// The full row sums, also where Q is diagonal (KArgs::q_diag).  A wave-uniform branch that leaves out the products with Q's zeros
+// gives the same bits and saves 12 of the 146 instructions of a cart-pole + wall rollout step, but MEASURED in the fused kernel
+// (round 6, profiles/r06_c4_ab.txt) the line search got 26 % LONGER (178.6 k -> 224.9 k cycles per iteration): the second arm of
+// the branch lives in the same loop, and its registers push the loop's values into the accumulation file.
 template <class M>
-__device__ __forceinline__ double stage_cost(const Consts<M>& c, const double (&x)[M::n], const double (&u)[M::m], bool q_diag = false) {
+__device__ __forceinline__ double stage_cost(const Consts<M>& c, const double (&x)[M::n], const double (&u)[M::m]) {
   constexpr int n = M::n, m = M::m;
   double dx[n];
 #pragma unroll
   for (int i = 0; i < n; ++i) dx[i] = x[i] - c.xnom[i];
   double q = 0.0;
-#ifndef MI_STAGE_COST_DIAG
-#define MI_STAGE_COST_DIAG 0
-#endif
-  if (MI_STAGE_COST_DIAG && n >= 4 && q_diag) {
 #pragma unroll
-    for (int i = 0; i < n; ++i) {
-      double s = 0.0;
-      s += c.Q[i][i] * dx[i];                                 // (the same fma(Q_ii, dx_i, 0) the full row sum ends up with)
-      q += dx[i] * s;
-    }
-  } else {
+  for (int i = 0; i < n; ++i) {
+    double s = 0.0;
 #pragma unroll
-    for (int i = 0; i < n; ++i) {
-      double s = 0.0;
-#pragma unroll
-      for (int j = 0; j < n; ++j) s += c.Q[i][j] * dx[j];
-      q += dx[i] * s;
-    }
+    for (int j = 0; j < n; ++j) s += c.Q[i][j] * dx[j];
+    q += dx[i] * s;
   }
   double ru = 0.0;
 #pragma unroll
@@ -511,7 +496,7 @@ __device__ __forceinline__ void rollout_step(const GRegs<M>& r, const Consts<M>&
   else M::template step<double>(x, u, xnext, par.v, a.dt);
   if (COST) {
     // stage cost (no 1/2 factor, ilqr.py:325) and expected improvement (:326)
-    L += stage_cost<M>(c, x, u, a.q_diag != 0);
+    L += stage_cost<M>(c, x, u);
     if constexpr (UsesLimits<M>::value) expd += r.dv;      // sum dV; the quadratic term is added once (rollout)
     else expd += ce * r.dv;
   }
@@ -748,9 +733,6 @@ __device__ __forceinline__ void aff2_prefix_dpp(Aff2& P) {
 // writes the trajectory straight into the nominal records (:375-376) - no T records, no separate
 // cost and commit passes; fuse = 2 additionally differentiates the dynamics at every step it holds
 // (:380-415 with every step a key-point), again from registers.
-#ifndef MI_NEWTON_MAX_SWEEPS
-#define MI_NEWTON_MAX_SWEEPS 7
-#endif
 enum { NEWTON_FAILED = 0, NEWTON_STORED = 1, NEWTON_REJECTED = 2, NEWTON_ACCEPTED = 3 };
 // Models on which the time-parallel rollout's remainder was measured (models.hpp: kNewtonRollout - the built-in smooth
 // n = 2 models); every other n = 2 model (plugins) takes the rollout too, under the stricter guard of dynamics_hold.
@@ -814,7 +796,6 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
       X[k + 1][0] = xn[0]; X[k + 1][1] = xn[1];
     }
   }
-#ifndef MI_NEWTON_NO_PREDICTOR
   else
   // Predictor: the first guess is the trajectory the backward pass itself predicts, the linearized
   // closed loop  dx_{t+1} = (fx_t - fu_t K_t) dx_t - fu_t kappa_t  around the nominal one (the same
@@ -859,11 +840,10 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
       ds[0] = n0; ds[1] = n1;
     }
   }
-#endif
   // Stop when a sweep moved the guess by less than kTol: the iteration is quadratic (error after a
   // sweep ~ 0.03 x the squared error before it, measured on C2), the update of a sweep IS the error
   // before it, so an update < 1e-7 leaves an error < 1e-15 - round-off.
-  constexpr int kMaxSweeps = MI_NEWTON_MAX_SWEEPS;
+  constexpr int kMaxSweeps = 7;
   constexpr double kTol = 1e-7;
   bool converged = false;
 #ifdef MI_PROF_NEWTON
@@ -878,10 +858,7 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
   // is left with an error ~2c u * c u^2: 6e-14 at the u = 3.5e-4 typical of C2's third sweep, where a full sweep
   // leaves 3e-19 - both far below the 1e-11 the a-posteriori guard (dynamics_hold, below) accepts.  A chord sweep
   // that does not converge is followed by a full one.
-#ifndef MI_NEWTON_FROZEN_TOL
-#define MI_NEWTON_FROZEN_TOL 5e-4
-#endif
-  constexpr double kFrozenTol = MI_NEWTON_FROZEN_TOL;
+  constexpr double kFrozenTol = 5e-4;
   double Gs[CH][n][n];                                       // closed-loop Jacobians of the last full sweep
   double prev_upd = __builtin_inf();
   bool have_g = false, last_frozen = false;
@@ -889,19 +866,6 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
   for (int sweep = 0; sweep < kMaxSweeps && !converged; ++sweep) {
 #ifdef MI_PROF_NEWTON
     ++nsw;
-#endif
-#ifdef MI_NEWTON_RELOAD
-    // A/B variant (tools/isa_mix.py): the loop-invariant nominal data of the lane's steps is read from
-    // LDS again in every sweep instead of being held in registers across the loop - 20 LDS reads for a loop without
-    // register parking in the accumulation file
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int k = 0; k < CH; ++k) {
-      const double* g = w.G + (valid[k] ? t0 + k : 0) * Ly::GS;
-#pragma unroll
-      for (int i = 0; i < n; ++i) { xb[k][i] = g[Ly::XB + i]; Kk[k][i] = g[Ly::KK + i]; }
-      dd[k] = g[Ly::UB] - eps * g[Ly::KAP];
-    }
 #endif
     const bool frozen = have_g && !last_frozen && prev_upd < kFrozenTol;      // wave-uniform
     // X_{t+1} of this lane's last step = the next lane's first guess

@@ -1,8 +1,7 @@
 // What one DEPENDENT rollout step of the cart-pole + wall model costs on one wave (the C4 line search: 199 of them in a row per
-// candidate lane), by form of the math: Horner / Estrin polynomials (-DMI_POLY_ESTRIN=0|1), with and without the wave-uniform
-// short cut of the contact force (softplus(z) = exp(z) bitwise once exp(z) < 2^-53: -DMI_SOFTPLUS_SKIP=0|1, dual.hpp).
-//   for e in 0 1; do for k in 0 1; do hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-fast-math -ffp-contract=fast -DMI_POLY_ESTRIN=$e -DMI_SOFTPLUS_SKIP=$k \
-//     -I drake_ddp_amd/csrc tools/ubench/chain_step.hip -o tools/ubench/chain_step_$e$k; done; done
+// candidate lane), far from the wall and at it; the acrobot's step beside it.  (profiles/r06_chain_step.txt: this figure for
+// Horner / Estrin polynomials and with / without a wave-uniform short cut of the contact force, forms since removed from the headers.)
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-fast-math -ffp-contract=fast -I drake_ddp_amd/csrc tools/ubench/chain_step.hip -o tools/ubench/chain_step
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "models.hpp"
@@ -54,7 +53,7 @@ int main() {
     for (double xw : {0.0, -0.21}) {                  // far from the wall (z << -37 on every lane) / at the wall (contact on every lane)
       k<CartPoleWall, 8><<<1, 64, 12 * 202 * 8>>>(out, cyc, prm, 0.01, steps, xw); hipDeviceSynchronize();
       hipMemcpy(&h, cyc, 8, hipMemcpyDeviceToHost);
-      printf("cart-pole + wall, cart at %5.2f: %.1f cycles per dependent step (MI_POLY_ESTRIN=%d MI_SOFTPLUS_SKIP=%d)\n", xw, (double)h / steps, MI_POLY_ESTRIN, MI_SOFTPLUS_SKIP);
+      printf("cart-pole + wall, cart at %5.2f: %.1f cycles per dependent step\n", xw, (double)h / steps);
     }
   }
   {
@@ -62,7 +61,7 @@ int main() {
     hipMemcpy(prm, p, sizeof p, hipMemcpyHostToDevice);
     k<Acrobot, 10><<<1, 64, 12 * 202 * 8>>>(out, cyc, prm, 0.004, steps, 0.0); hipDeviceSynchronize();
     hipMemcpy(&h, cyc, 8, hipMemcpyDeviceToHost);
-    printf("acrobot: %.1f cycles per dependent step (MI_POLY_ESTRIN=%d)\n", (double)h / steps, MI_POLY_ESTRIN);
+    printf("acrobot: %.1f cycles per dependent step\n", (double)h / steps);
   }
   return 0;
 }

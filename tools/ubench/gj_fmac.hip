@@ -1,8 +1,7 @@
-// Gauss-Jordan elimination (ilqr_large.hpp: GjOuter) with the column update as ONE v_fmac_f64_dpp against the compiler's
-// v_mov_b64_dpp + v_fma_f64 (-DMI_GJ_MOV_FMA): cycles per inverse (one wave, rows per lane, four matrices per wave) and a
-// bitwise checksum of the inverses of 256 seeded SPD matrices - the two builds must print the same checksum.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Idrake_ddp_amd/csrc tools/ubench/gj_fmac.hip -o /tmp/gj_a
-//   hipcc ... -DMI_GJ_MOV_FMA ... -o /tmp/gj_b
+// Gauss-Jordan elimination (ilqr_large.hpp: GjOuter; the column update is ONE v_fmac_f64_dpp for m >= 4, the compiler's
+// v_mov_b64_dpp + v_fma_f64 below that): cycles per inverse (one wave, rows per lane, four matrices per wave) and a bitwise
+// checksum of the inverses of 256 seeded SPD matrices - a change to the elimination must print the same checksum.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Idrake_ddp_amd/csrc tools/ubench/gj_fmac.hip -o /tmp/gj
 #include "ilqr_large.hpp"
 #include <cstdio>
 #include <cstring>
@@ -57,11 +56,7 @@ void run(const char* name) {
   hipFree(dA); hipFree(dW); hipFree(dc);
 }
 int main() {
-#ifdef MI_GJ_MOV_FMA
-  const char* name = "mov_dpp+fma ";
-#else
-  const char* name = "fmac_dpp    ";
-#endif
+  const char* name = "gauss-jordan";
   run<1>(name); run<2>(name); run<3>(name); run<4>(name); run<7>(name); run<12>(name); run<16>(name);
   return 0;
 }
