@@ -200,41 +200,6 @@ __device__ __forceinline__ int xcc_id() {
   return (int)(x & 15u);
 }
 
-// Models whose step is an articulated-body algorithm cut into chains (models.hpp: PlanarQuad): cooperative
-// step in the rollout, accessor-driven whole-tree evaluation in the linearization.
-template <class M, class = void>
-struct IsChainModel { static constexpr bool value = false; };
-template <class M>
-struct IsChainModel<M, decltype((void)M::kChainCooperative)> { static constexpr bool value = M::kChainCooperative; };
-// Models whose step is cut per LEG of a floating-base body (models.hpp: Quad3D): one lane per leg in the rollout, the
-// legs' wrenches summed over the 16-lane row; whole-step evaluation per (key-point, column) item in the linearization.
-template <class M, class = void>
-struct IsLegModel { static constexpr bool value = false; };
-template <class M>
-struct IsLegModel<M, decltype((void)M::kLegCooperative)> { static constexpr bool value = M::kLegCooperative; };
-// Models that only provide the whole step (plugins, include/mi_ilqr.h: open model interface): one lane advances the
-// dynamics in the rollout, whole-step evaluation per (key-point, column) item in the linearization.
-template <class M, class = void>
-struct IsWholeStepModel { static constexpr bool value = false; };
-template <class M>
-struct IsWholeStepModel<M, decltype((void)M::kWholeStep)> { static constexpr bool value = M::kWholeStep; };
-// Models whose step starts with the sines / cosines of kJoints independent angles (models.hpp: Arm27): the rollout evaluates
-// them on 2 kJoints lanes at once and every lane of the first 16-lane row runs the rest of the step (M::core) on the shared
-// values; lane 0 publishes the result.  Bitwise M::step.
-template <class M, class = void>
-struct IsTrigModel { static constexpr bool value = false; };
-template <class M>
-struct IsTrigModel<M, decltype((void)M::kTrigCooperative)> { static constexpr bool value = M::kTrigCooperative; };
-// Models that can declare a step infeasible (Drake's update throwing -> L = inf, ilqr.py:315-323).
-template <class M, class = void>
-struct CanFail { static constexpr bool value = false; };
-template <class M>
-struct CanFail<M, decltype((void)M::kCanFail)> { static constexpr bool value = M::kCanFail; };
-
-// Models whose rollout leaves lx_t, lu_t of the accepted trial in the backward pass's cost-gradient area.
-template <class M>
-constexpr bool kLxFromRollout = !IsChainModel<M>::value;
-
 __device__ __forceinline__ double block_sum(double v, double* red) {
   // deterministic fixed-order tree: 64-lane butterfly, then 4 wave partials
 #pragma unroll
@@ -288,15 +253,6 @@ __device__ __forceinline__ void trig_gather(double v, double (&S)[NJ], double (&
 // old (u_{t-1} left in the middle of step t-1).  (A counted wait - s_waitcnt vmcnt(3 k), publishing s = t - k - is right only
 // while the wave has nothing but stores in flight, and measured within +- 0.5 % of this form: docs/ENGINEERING_LOG_r03_r05.md.)
 constexpr unsigned long long kPubAbort = 0x80000000ull;      // *prog = tag | kPubAbort: the trial was rejected, stop linearizing it
-// Blocks at the END of the horizon that the leader linearizes itself once the trial is accepted (early rounds): models whose
-// helpers cannot keep up with the rollout (planar quadruped: an item is two passes over the tree, ~78 k cycles) - the last
-// block comes out last anyway, and the leader's hands are free by then.
-template <class M, class = void>
-struct EarlyLeaderBlocks { static constexpr int value = 0; };
-template <class M>
-struct EarlyLeaderBlocks<M, decltype((void)M::kEarlyLeaderBlocks)> { static constexpr int value = M::kEarlyLeaderBlocks; };
-template <class M>
-constexpr bool kEarlyLin = M::m * 16 <= 192;                 // (the fourth wave holds no control-law lanes: no prefetch loads on it)
 // clip(v, u_min_k, u_max_k) by comparisons (a NaN stays NaN: its trial is rejected as without limits)
 template <class M>
 __device__ __forceinline__ double lim_clamp(const double* lds, int k, double v) {
@@ -896,10 +852,6 @@ struct SeedAcc {
   const double* p; int col;
   __device__ __forceinline__ Dual1 operator[](int i) const { return Dual1(p[i], i == col ? 1.0 : 0.0); }
 };
-template <class M, class = void>
-struct HasSparsity { static constexpr bool value = false; };
-template <class M>
-struct HasSparsity<M, decltype((void)M::kMaxAffected)> { static constexpr bool value = true; };
 
 // Sparse variant: only the dofs that read input column `col` are evaluated (M::affected); the
 // rest of the column is written as the exact zeros the dense evaluation produces.

@@ -33,6 +33,7 @@
 #include "../../include/mi_ilqr.h"
 #include "fastmath.hpp"
 #include "keypoints.hpp"
+#include "model_traits.hpp"
 #include "models.hpp"
 
 namespace mi {
@@ -99,7 +100,6 @@ struct KArgs {
   // rolled out beside the first, [3][B][N][n] and [3][B][N-1][m]
   double *x_spec, *u_spec;
   int spec_policy;
-  int q_diag;                     // Q has no off-diagonal entry (mi_ilqr_set_cost detects it).  No kernel reads it at present: see stage_cost
   // workgroup-per-problem kernels, long horizons: the cost gradients [B][N-1][n+m] in HBM instead of LDS (ilqr_large.hpp)
   double* lxu;
   int pd_continue;                // mi_ilqr_desc.on_indefinite
@@ -291,36 +291,6 @@ __device__ inline void stage_out(double* dst, const double* recs, int RS, int of
   }
 }
 
-// The same model with the kernels' backward pass run as the time-parallel scan.  For n = 3..4 the scan
-// pays from two steps per lane on (N > 128) and its register appetite must not touch the kernels of
-// short horizons, so the host picks this instantiation by horizon (mi_ilqr.hip: launch_jac).
-template <class M>
-struct LongHorizon : M { static constexpr bool kScanBackward = true; };
-template <class M, class = void>
-struct UsesScanBackward : std::false_type {};
-template <class M>
-struct UsesScanBackward<M, std::void_t<decltype(M::kScanBackward)>> : std::bool_constant<M::kScanBackward> {};
-
-// The same model with the kernels' backward pass run as the reference's scalar recursion verbatim
-// (cost matrices the MFMA / scan forms do not cover: asymmetric or indefinite Q, Qf, R).
-template <class M>
-struct ExactCost : M { static constexpr bool kExactBackward = true; };
-template <class M, class = void>
-struct UsesExactBackward : std::false_type {};
-template <class M>
-struct UsesExactBackward<M, std::void_t<decltype(M::kExactBackward)>> : std::bool_constant<M::kExactBackward> {};
-
-// The same model with box control limits u_min <= u <= u_max (mi_ilqr_set_control_limits): every rollout clamps its controls,
-// the backward pass solves a box QP per step (backward_limited).  Both are sequential in time - the n = 2 Newton rollout and
-// the Riccati scans have no form that carries an active set - so the host picks this instantiation for limited handles only,
-// like LongHorizon<M> / ExactCost<M>, and the regular kernels carry neither its code nor its registers.
-template <class M>
-struct Limited : M { static constexpr bool kLimited = true; };
-template <class M, class = void>
-struct UsesLimits : std::false_type {};
-template <class M>
-struct UsesLimits<M, std::void_t<decltype(M::kLimited)>> : std::bool_constant<M::kLimited> {};
-
 // The bounds of one problem, in registers for the whole launch (Limited<M> kernels; empty otherwise).
 template <class M, bool = UsesLimits<M>::value>
 struct LimitRegs {};
@@ -401,10 +371,11 @@ struct Consts : LimitRegs<M> {
 // Lane 0 stores its trajectory into the T records; the other lanes' stores go
 // to a per-lane dump slot so the loop carries no exec-mask branches.
 // ---------------------------------------------------------------------------
-// The full row sums, also where Q is diagonal (KArgs::q_diag).  A wave-uniform branch that leaves out the products with Q's zeros
-// gives the same bits and saves 12 of the 146 instructions of a cart-pole + wall rollout step, but MEASURED in the fused kernel
-// (round 6, profiles/r06_c4_ab.txt) the line search got 26 % LONGER (178.6 k -> 224.9 k cycles per iteration): the second arm of
-// the branch lives in the same loop, and its registers push the loop's values into the accumulation file.
+// The full row sums, also where Q is diagonal.  A wave-uniform branch that leaves out the products with Q's zeros (on a flag the
+// host set for such a Q) gives the same bits and saves 12 of the 146 instructions of a cart-pole + wall rollout step, but MEASURED
+// in the fused kernel (round 6, profiles/r06_c4_ab.txt) the line search got 26 % LONGER (178.6 k -> 224.9 k cycles per iteration):
+// the second arm of the branch lives in the same loop, and its registers push the loop's values into the accumulation file.  The
+// flag and its detection in mi_ilqr_set_cost left the sources with this finding.
 template <class M>
 __device__ __forceinline__ double stage_cost(const Consts<M>& c, const double (&x)[M::n], const double (&u)[M::m]) {
   constexpr int n = M::n, m = M::m;
@@ -465,10 +436,6 @@ struct GRegs {
   }
 };
 
-template <class M, class = void>
-struct HasStepPool : std::false_type {};
-template <class M>
-struct HasStepPool<M, std::void_t<decltype(M::kHasStepPool)>> : std::bool_constant<M::kHasStepPool> {};
 struct NoPool {};
 template <class M, bool = HasStepPool<M>::value>
 struct PoolOf { using type = NoPool; __device__ __forceinline__ static NoPool make() { return {}; } };
@@ -734,12 +701,6 @@ __device__ __forceinline__ void aff2_prefix_dpp(Aff2& P) {
 // cost and commit passes; fuse = 2 additionally differentiates the dynamics at every step it holds
 // (:380-415 with every step a key-point), again from registers.
 enum { NEWTON_FAILED = 0, NEWTON_STORED = 1, NEWTON_REJECTED = 2, NEWTON_ACCEPTED = 3 };
-// Models on which the time-parallel rollout's remainder was measured (models.hpp: kNewtonRollout - the built-in smooth
-// n = 2 models); every other n = 2 model (plugins) takes the rollout too, under the stricter guard of dynamics_hold.
-template <class M, class = void>
-struct NewtonMeasured { static constexpr bool value = false; };
-template <class M>
-struct NewtonMeasured<M, decltype((void)M::kNewtonRollout)> { static constexpr bool value = M::kNewtonRollout; };
 
 template <class M, int JAC, int CH>
 __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const KArgs& a, const ModelParams<M>& par, const double* x0r, double eps,

@@ -30,10 +30,6 @@ int launch_one_large(mi_ilqr* h, const KArgs& a) {
 // the mechanism of this hipcc's miscompiles of these kernels (a VGPR spill copy placed in a zero-EXEC block prologue: DESIGN
 // section 8, tools/check_exec_spill.py), rebuilt the form on the current sources - the checker finds no such site in it, the
 // 50 planar-quadruped tests of the GPU suite pass on it - and adopted it.
-template <class M, class = void>
-struct HasPivSplit { static constexpr bool value = false; };
-template <class M>
-struct HasPivSplit<M, decltype((void)M::kPivSplit)> { static constexpr bool value = M::kPivSplit; };
 template <class M>
 constexpr bool kPivSplit = HasPivSplit<M>::value;
 

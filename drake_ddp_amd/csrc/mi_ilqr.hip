@@ -178,7 +178,6 @@ KArgs make_args(const mi_ilqr* h) {
   a.lxu = h->lxu;
   a.pd_continue = h->d.on_indefinite == 1 ? 1 : 0;
   a.cost_asym = h->cost_asym ? 1 : 0;
-  a.q_diag = h->q_diag ? 1 : 0;
   a.ulim = h->limited ? h->ulim : nullptr;
   a.s2 = h->s2;
   a.x_nom_rows = h->per_problem_targets ? h->x_nom_rows : nullptr;
@@ -1011,12 +1010,6 @@ int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const doubl
       asym = !(symmetric(cm.data(), n) && symmetric(cm.data() + n * n, m) && symmetric(cm.data() + n * n + m * m, n));
     }
     h->cost_asym = asym ? 1 : 0;
-    {
-      bool diag = true;
-      for (size_t i = 0; i < n; ++i)
-        for (size_t j = 0; j < n; ++j) if (i != j && cm[i * n + j] != 0.0) diag = false;
-      h->q_diag = diag ? 1 : 0;
-    }
     h->exact_backward = regular ? 0 : 1;
     // the device copy mirrors h_costmat: nothing to send when the caller repeats the matrices it set before
     // (Solve() pushes them on every call, like the reference reads its attributes on every call)

@@ -5,6 +5,7 @@
 // closed-form models (semi-implicit Euler) are the build's own definitions; the
 // identical formulas, in the same operation order, live in oracle/models_np.py
 // (NumPy) and oracle/ilqr_oracle.c (C).  Ids/parameter layout: include/mi_ilqr.h.
+// The optional members of a model (kWholeStep, kCanFail, kPivSplit, ...), what each selects and which wins: the table in model_traits.hpp.
 #pragma once
 #include "dual.hpp"
 

@@ -4,16 +4,15 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-fast-math -ffp-contract=fast -I drake_ddp_amd/csrc tools/ubench/chain_step.hip -o tools/ubench/chain_step
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include "model_traits.hpp"
 #include "models.hpp"
 using namespace mi;
-template <class M, class = void> struct HasPool : std::false_type {};
-template <class M> struct HasPool<M, std::void_t<decltype(M::kHasStepPool)>> : std::bool_constant<M::kHasStepPool> {};
 struct NoPool_ {};
-template <class M, bool = HasPool<M>::value> struct PoolOf_ { using type = NoPool_; __device__ static NoPool_ make() { return {}; } };
+template <class M, bool = HasStepPool<M>::value> struct PoolOf_ { using type = NoPool_; __device__ static NoPool_ make() { return {}; } };
 template <class M> struct PoolOf_<M, true> { using type = typename M::StepPool; __device__ static type make() { return M::StepPool::in_vgprs(); } };
 template <class M, class P>
 __device__ __forceinline__ void step_of(const double* x, const double* u, double* xn, const double* p, double dt, const P& pool) {
-  if constexpr (HasPool<M>::value) M::step_pooled(x, u, xn, p, dt, pool);     // (the polynomial constants in VGPRs for the loop, as in rollout())
+  if constexpr (HasStepPool<M>::value) M::step_pooled(x, u, xn, p, dt, pool);     // (the polynomial constants in VGPRs for the loop, as in rollout())
   else M::template step<double>(x, u, xn, p, dt);
 }
 template <class M, int NP>
