@@ -27,6 +27,7 @@ STATUS_FLAG_INDEFINITE = 16     # OR-ed onto the outcome: on_indefinite="continu
 F_X_BAR, F_U_BAR, F_K, F_KAPPA, F_DV, F_FX, F_FU, F_COST, F_X0, F_HIST, F_X_TRIAL, F_U_TRIAL, F_TRIAL_COST, F_ITER_CYCLES = range(14)
 F_X_NOM, F_TARGET_STEP = 14, 15   # (B, n) per-problem targets and MPC target steps (mi_ilqr.h: "Per-problem targets")
 F_MODEL_PARAMS = 16               # (B, n_params) per-problem model parameters (mi_ilqr.h: "Per-problem model parameters")
+F_COST_MATRICES = 17              # (B, 2n^2+m^2) per-problem cost matrices, row b = Q_b | R_b | Qf_b (mi_ilqr.h: "Per-problem cost matrices")
 I_ITERS, I_STATUS, I_LS_TRIALS, I_KP_COUNT, I_KP_LIST = 100, 101, 102, 103, 104
 I64_STAGE_CYCLES = 200
 I64_CLUSTER_WORDS = 201

@@ -106,6 +106,19 @@ struct mi_ilqr {
   bool per_problem_params = false;
   double *param_rows = nullptr, *param_cols = nullptr;   // allocated on first use, kept when dropped
   std::vector<double> h_param_rows;
+  // per-problem cost matrices (mi_ilqr_set MI_F_COST_MATRICES): `per_problem_costs` hands the kernels cost_rows, (B, 2 n^2 + m^2) dense,
+  // row b = Q_b | R_b | Qf_b, and - the lane-per-problem kernels - cost_cols, the same values batch-minor; the host mirror is what
+  // mi_ilqr_get returns.  Problem data: mi_ilqr_reset keeps them.  exact_backward / cost_asym above are the class the kernels run
+  // with: the shared matrices' (shared_*) in shared mode, that of the most general row (rows_*) in per-problem mode.
+  bool per_problem_costs = false;
+  bool cost_rows_synced = false;       // the device copies equal the mirror
+  double *cost_rows = nullptr, *cost_cols = nullptr;   // allocated on first use, kept when dropped
+  std::vector<double> h_cost_rows;
+  int shared_exact_backward = 0, shared_cost_asym = 0, rows_exact_backward = 0, rows_cost_asym = 0;
+  // lane-per-problem kernels: their per-problem-cost instantiations always read target ROWS; a handle without per-problem targets
+  // gets the shared x_nom broadcast into these (B, n) rows before a launch (refresh_lane_target_rows)
+  double* lane_x_nom_rows = nullptr;
+  std::vector<double> h_lane_x_nom;    // the x_nom the device rows hold now (empty: none)
 };
 
 // Run-time switches for A/B runs (README): the environment is read once per process.

@@ -35,8 +35,9 @@ namespace mi {
 // batch-minor addressing helpers: element (t, r) of an array with `rows` rows per time step
 __device__ __forceinline__ size_t bm(int t, int r, int rows, int B) { return ((size_t)t * rows + r) * B; }
 
-template <class M, int JAC, bool KP = false, bool PT = false, bool PP = false>
+template <class M, int JAC, bool KP = false, bool PT = false, bool PP = false, bool PC = false>
 __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
+  static_assert(!PC || PT, "per-problem cost matrices run with per-problem targets on (the host broadcasts a shared target into rows)");
   constexpr int n = M::n, m = M::m, nc = n + m;
   const int b = blockIdx.x * 64 + threadIdx.x;
   const int B = a.B, N = a.N;
@@ -58,7 +59,16 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
   Consts<M> c;
   // PT: per-problem targets (KArgs::x_nom_rows) - x_nom, 2 x_nom^T Q and 2 x_nom^T Qf become per-lane values.  Its own
   // instantiation: in the regular kernel they are batch-uniform (scalar registers) and stay so.
-  if constexpr (PT) c.load(a.costmat, a.x_nom_rows + (size_t)bb * n);
+  // PC: per-problem cost matrices (KArgs::cost_cols, (2 n^2 + m^2, B) batch-minor: one coalesced load per entry) - Q, R, Qf and
+  // what is derived from them become per-lane values, held in registers for the launch.  Instantiations of their own again, and
+  // only with PT: a PC handle without per-problem targets gets its shared target broadcast into rows by the host.
+  // Q, R and the derived vectors stay in registers for the launch; Qf - needed at the end of a rollout and at the start of a
+  // backward pass only - is read again where it is used (cost_at below): held as well, the forward-mode-dual form of the acrobot
+  // kernel went to scratch.
+  [[maybe_unused]] const double* const cc = PC ? a.cost_cols + bb : nullptr;
+  [[maybe_unused]] auto cost_at = [cc, B](int e) __attribute__((always_inline)) { return cc[(size_t)e * B]; };
+  if constexpr (PC) c.load_from(cost_at, a.x_nom_rows + (size_t)bb * n);
+  else if constexpr (PT) c.load(a.costmat, a.x_nom_rows + (size_t)bb * n);
   else c.load(a.costmat);
   double x0r[n];
 #pragma unroll
@@ -187,6 +197,7 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
         step(Bq, t + 1);
       }
       if (t < N - 1) step(A, t);
+      if constexpr (PC) c.reload_Qf(cost_at);
       Lc += terminal_cost<M>(c, x);                                     // :327
       if constexpr (UsesLimits<M>::value) ex = -(eps * ex - 0.5 * eps * eps * s2);
       if (run) {
@@ -218,6 +229,7 @@ __global__ void __launch_bounds__(64) ilqr_batch_kernel(const KArgs a) {
         double xT[n];
 #pragma unroll
         for (int i = 0; i < n; ++i) xT[i] = xb[bm(N - 1, i, n, B)];
+        if constexpr (PC) c.reload_Qf(cost_at);
 #pragma unroll
         for (int i = 0; i < n; ++i) {
           double s = -c.qfn[i];

@@ -2982,7 +2982,7 @@ __global__ void __launch_bounds__(kLargeThreads, 1) ilqr_large_kernel(const KArg
 
   // cost constants -> LDS ; 2 x_nom^T Q and 2 x_nom^T Qf (ilqr.py:180,203)
   {
-    const double* cm = a.costmat;
+    const double* cm = cost_of<n, m>(a, b);   // (a helper: the row of the problem it serves - its linearization and candidate rollouts)
     for (int e = tid; e < n * n; e += kLargeThreads) { lds[Ly::oQ + e] = cm[e]; lds[Ly::oQf + e] = cm[n * n + m * m + e]; }
     for (int e = tid; e < m * m; e += kLargeThreads) lds[Ly::oR + e] = cm[n * n + e];
     if (tid < n) lds[Ly::oXnom + tid] = x_nom_of<n, m>(a, b)[tid];   // (a helper: the problem it serves)

@@ -119,12 +119,24 @@ struct KArgs {
   // coalesced transaction.  Null (both): the shared `params`.  Neither array is written while a kernel runs.
   const double* param_rows;
   const double* param_cols;
+  // per-problem cost matrices (mi_ilqr_set MI_F_COST_MATRICES): Q | R | Qf of problem b is row b of cost_rows instead of the head of
+  // `costmat` (x_nom stays where the targets put it: x_nom_of).  Rows are DENSE: (B, 2 n^2 + m^2).  The lane-per-problem kernels read
+  // cost_cols, the same values batch-minor, (2 n^2 + m^2, B).  Null (both): the shared matrices.  seq_backward / cost_asym carry the
+  // class of the most general row.  Neither array is written while a kernel runs.
+  const double* cost_rows;
+  const double* cost_cols;
 };
 
 // Where problem b's target lives: row b of the per-problem targets, else the shared one in the costmat (Q | R | Qf | x_nom).
 template <int n, int m>
 __device__ __forceinline__ const double* x_nom_of(const KArgs& a, size_t b) {
   return a.x_nom_rows ? a.x_nom_rows + b * n : a.costmat + 2 * n * n + m * m;
+}
+// Where problem b's Q | R | Qf live: row b of the per-problem cost matrices, else the head of the shared costmat.  Like x_nom_of: b is
+// uniform for the wave, both arms are global pointers out of the kernel arguments, the reads stay scalar loads.
+template <int n, int m>
+__device__ __forceinline__ const double* cost_of(const KArgs& a, size_t b) {
+  return a.cost_rows ? a.cost_rows + b * (2 * n * n + m * m) : a.costmat;
 }
 // Problem b's per-re-solve step of the MPC target, component i.
 template <int n>
@@ -317,14 +329,20 @@ struct Consts : LimitRegs<M> {
   __device__ inline void load(const double* cm) { load(cm, cm + 2 * n * n + m * m); }
   // xn: this problem's target (x_nom_of); qn / qfn come from the same loop whichever array it is
   __device__ inline void load(const double* cm, const double* xn) {
+    load_from([cm](int e) __attribute__((always_inline)) { return cm[e]; }, xn);
+  }
+  // at(e): entry e of Q | R | Qf wherever the matrices live (dense: cm[e]; the lane-per-problem kernels' per-problem matrices:
+  // KArgs::cost_cols, batch-minor) - ONE loop builds the constants whichever array they came from
+  template <class At>
+  __device__ inline void load_from(At at, const double* xn) {
 #pragma unroll
     for (int i = 0; i < n; ++i)
 #pragma unroll
-      for (int j = 0; j < n; ++j) { Q[i][j] = cm[i * n + j]; Qf[i][j] = cm[n * n + m * m + i * n + j]; }
+      for (int j = 0; j < n; ++j) { Q[i][j] = at(i * n + j); Qf[i][j] = at(n * n + m * m + i * n + j); }
 #pragma unroll
     for (int i = 0; i < m; ++i)
 #pragma unroll
-      for (int j = 0; j < m; ++j) R[i][j] = cm[n * n + i * m + j];
+      for (int j = 0; j < m; ++j) R[i][j] = at(n * n + i * m + j);
 #pragma unroll
     for (int i = 0; i < n; ++i) xnom[i] = xn[i];
 #pragma unroll
@@ -334,6 +352,15 @@ struct Consts : LimitRegs<M> {
       for (int i = 0; i < n; ++i) { s += (2.0 * xnom[i]) * Q[i][j]; sf += (2.0 * xnom[i]) * Qf[i][j]; }
       qn[j] = s; qfn[j] = sf;
     }
+  }
+  // Qf alone, read again (the lane-per-problem kernels' per-problem matrices: Qf is used twice per iteration, and re-reading it
+  // there keeps n^2 values per lane out of the registers in between)
+  template <class At>
+  __device__ __forceinline__ void reload_Qf(At at) {
+#pragma unroll
+    for (int i = 0; i < n; ++i)
+#pragma unroll
+      for (int j = 0; j < n; ++j) Qf[i][j] = at(n * n + m * m + i * n + j);
   }
   // LDS image: Q | Qf | R | xnom | qn | qfn
   __device__ inline void to_lds(double* d) const {
@@ -2493,7 +2520,7 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
     // the control sequence - and consumed after the LDS arrays have been initialized: one memory
     // latency instead of one per array (a cold solve reads nothing else).  (n = 2 only: in the
     // larger kernels the extra live registers cost more in the line-search loops than this saves.)
-    c.load(a.costmat, x_nom_of<n, m>(a, b));
+    c.load(cost_of<n, m>(a, b), x_nom_of<n, m>(a, b));
 #pragma unroll
     for (int i = 0; i < n; ++i) x0r[i] = a.x0[(size_t)b * n + i];
     constexpr int UPQ = 4;
@@ -2542,7 +2569,7 @@ __global__ void __launch_bounds__(256) ilqr_small_kernel(const KArgs a) {
     stage_in(w.G, Ly::GS, Ly::DV, a.dV + oT, 1, N - 1, cold);
     stage_in(w.J, Ly::JS, Ly::FX, a.fx + oFx, n * n, N - 1, cold);
     stage_in(w.J, Ly::JS, Ly::FU, a.fu + oFu, n * m, N - 1, cold);
-    c.load(a.costmat, x_nom_of<n, m>(a, b));
+    c.load(cost_of<n, m>(a, b), x_nom_of<n, m>(a, b));
 #pragma unroll
     for (int i = 0; i < n; ++i) x0r[i] = a.x0[(size_t)b * n + i];
     if constexpr (UsesScanBackward<M>::value) c.to_lds(w.cst);

@@ -182,6 +182,10 @@ KArgs make_args(const mi_ilqr* h) {
   a.s2 = h->s2;
   a.x_nom_rows = h->per_problem_targets ? h->x_nom_rows : nullptr;
   a.target_steps = h->per_problem_targets ? h->target_steps : nullptr;
+  a.cost_rows = h->per_problem_costs ? h->cost_rows : nullptr;
+  a.cost_cols = (h->per_problem_costs && h->batch_minor) ? h->cost_cols : nullptr;
+  // (the lane kernels' per-problem-cost instantiations read target rows in any case: the shared target, broadcast by launch())
+  if (a.cost_cols && !a.x_nom_rows) a.x_nom_rows = h->lane_x_nom_rows;
   a.param_rows = h->per_problem_params ? h->param_rows : nullptr;
   a.param_cols = (h->per_problem_params && h->batch_minor) ? h->param_cols : nullptr;
   a.spec_policy = h->x_spec ? sw.spec : 0;
@@ -215,8 +219,11 @@ KArgs make_args(const mi_ilqr* h) {
 // longer known-zero for the fields the mode writes, and u_bar is materialized.
 int reduce_pending_stats(mi_ilqr* h);
 
+int refresh_lane_target_rows(mi_ilqr* h);
+
 int launch(mi_ilqr* h, int mode) {
   HIPCHK(hipSetDevice(h->d.device_id));
+  if (h->per_problem_costs && h->batch_minor && !h->per_problem_targets) { const int rc = refresh_lane_target_rows(h); if (rc != MI_ILQR_OK) return rc; }
   // any launch other than a pipelined solve reuses the current ring slot: settle the statistics still owed first
   if (!h->in_async_solve) { const int rc = reduce_pending_stats(h); if (rc != MI_ILQR_OK) return rc; }
   if (h->u_zero && !h->u_pending) HIPCHK(hipMemsetAsync(h->u_bar, 0, (size_t)h->B * h->m * (h->N - 1) * 8, h->stream));
@@ -472,6 +479,20 @@ int stage_h2d(mi_ilqr* h, void* dst, const void* src, size_t bytes) {
   HIPCHK(hipEventRecord(h->pin_ev, h->stream));
   h->pin_off += (bytes + 255) & ~(size_t)255;
   return MI_ILQR_OK;
+}
+
+// The lane-per-problem kernels' per-problem-cost instantiations on a handle with ONE target: its x_nom as (B, n) rows.
+int refresh_lane_target_rows(mi_ilqr* h) {
+  const size_t B = h->B, n = h->n;
+  const double* xn = h->h_costmat.data() + 2 * n * n + (size_t)h->m * h->m;   // the shared x_nom (host mirror)
+  if (h->lane_x_nom_rows && h->h_lane_x_nom.size() == n && std::memcmp(h->h_lane_x_nom.data(), xn, n * 8) == 0) return MI_ILQR_OK;
+  if (!h->lane_x_nom_rows) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->lane_x_nom_rows), B * n * 8));
+  std::vector<double> rows(B * n);
+  for (size_t b = 0; b < B; ++b) std::memcpy(rows.data() + b * n, xn, n * 8);
+  h->h_lane_x_nom.clear();
+  const int rc = stage_h2d(h, h->lane_x_nom_rows, rows.data(), B * n * 8);
+  if (rc == MI_ILQR_OK) h->h_lane_x_nom.assign(xn, xn + n);
+  return rc;
 }
 
 struct Field { void* ptr; size_t bytes; bool is_int; };
@@ -798,7 +819,8 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
   void* ptrs[] = {h->x_bar, h->u_bar, h->K, h->kappa, h->dV, h->fx, h->fu, h->x0, h->u_guess, h->cost_ring, h->hist, h->iter_cyc,
                   h->x_trial, h->u_trial, h->trial_cost, h->stage_in, h->costmat, h->iters_ring, h->status_ring, h->ls_ring,
                   h->kp_count, h->kp_list, h->prof, h->done_counter, h->cluster_sync, h->bm_scratch, h->x_spec, h->u_spec, h->lxu,
-                  h->ulim, h->s2, h->x_nom_rows, h->target_steps, h->param_rows, h->param_cols};
+                  h->ulim, h->s2, h->x_nom_rows, h->target_steps, h->param_rows, h->param_cols, h->cost_rows, h->cost_cols,
+                  h->lane_x_nom_rows};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
   if (h->mpc_log) (void)hipFree(h->mpc_log);
@@ -952,65 +974,146 @@ static int get_model_params(mi_ilqr* h, double* dst, size_t bytes) {
   return MI_ILQR_OK;
 }
 
+// The cost class of one set of matrices, cm = Q | R | Qf (mi_ilqr_set_cost and every row of MI_F_COST_MATRICES decide it here):
+// `regular` - symmetric, Q and Qf positive semi-definite, R positive definite: the fast backward forms; otherwise the reference's
+// recursion (exact_backward), and on the workgroup-per-problem kernels `asym` when a matrix is not symmetric.  May write cm: the
+// n >= 33 kernels' round-off symmetrisation.  MI_ILQR_E_UNSUPPORTED: a non-finite entry the workgroup-per-problem kernels cannot take
+// (mi_ilqr_set_cost only: the rows of MI_F_COST_MATRICES are finite when they get here - set_cost_rows refuses others up front,
+// for every kernel family, with the MI_ILQR_E_BAD_ARG the header documents).
+static int classify_cost(const mi_ilqr* h, double* cm, bool* regular_out, bool* asym_out) {
+  const size_t n = h->n, m = h->m;
+  // The time-parallel / matrix-core backward passes use Vxx = Vxx^T and (scan) PSD second-order terms; the
+  // reference accepts ANY Q, R, Qf and never symmetrizes (ilqr.py:182,653-667).  Matrices outside that
+  // class are served by the reference's recursion verbatim (wave- and lane-per-problem kernels), by the mid-size
+  // matrix-core pass with every use of symmetry switched off (n <= 32), or refused (n >= 33).
+  if (h->large && n > 32) {
+    // The n >= 33 workgroup-per-problem kernels' matrix-core pass has no form without symmetry (the plain-arithmetic pass that
+    // takes over - large_backward_asym - is ~4 x slower per step), and matrices built as A^T A or by float arithmetic are often
+    // symmetric only to round-off: asymmetries up to a few ulps of the largest entry are averaged away here
+    // (|A - A^T| <= 8 eps max|A|) so that they keep the fast pass; anything larger is followed as given.
+    // (n <= 32: matrices are taken as given, like the reference does.)
+    auto symmetrize = [](double* A, size_t k) {
+      double scale = 0.0;
+      for (size_t i = 0; i < k * k; ++i) scale = std::fmax(scale, std::fabs(A[i]));
+      for (size_t i = 0; i < k; ++i)
+        for (size_t j = 0; j < i; ++j) if (std::fabs(A[i * k + j] - A[j * k + i]) > 8 * 2.220446049250313e-16 * scale) return;
+      for (size_t i = 0; i < k; ++i)
+        for (size_t j = 0; j < i; ++j) A[i * k + j] = A[j * k + i] = 0.5 * (A[i * k + j] + A[j * k + i]);
+    };
+    symmetrize(cm, n); symmetrize(cm + n * n, m); symmetrize(cm + n * n + m * m, n);
+  }
+  const bool regular = is_sym_psd(cm, (int)n, false) && is_sym_psd(cm + n * n + m * m, (int)n, false) &&
+                       is_sym_psd(cm + n * n, (int)m, true);
+  bool asym = false;
+  if (!regular && h->large) {
+    // Definiteness is not required of the workgroup-per-problem kernels - they check it where it matters: every
+    // Quu = 2R + fu^T Vxx fu of every backward pass (MI_STATUS_NOT_PD, or mi_ilqr_desc.on_indefinite = 1: inverted with partial
+    // pivoting like the reference's np.linalg.inv, ilqr.py:655).  SYMMETRY: the mid-size kernels (n <= 32, mid_backward) follow
+    // the reference on any matrices - lxx = 2Q and luu = 2R as given, lx = 2Qx - 2 x_nom^T Q, Vx' = Qx - Qu^T Quu^{-1} Qux with
+    // the inverse of a Quu that is not symmetric, Vxx stored in full (ilqr.py:180-184,651-667); the n >= 33 kernels, whose
+    // matrix-core pass mirrors tiles of the symmetric products, take a plain-arithmetic pass for such matrices (round 6:
+    // large_backward_asym; they refused them before).
+    auto finite = [](const double* A, size_t k) {
+      for (size_t i = 0; i < k * k; ++i) if (!(std::fabs(A[i]) < INFINITY)) return false;
+      return true;
+    };
+    auto symmetric = [](const double* A, size_t k) {
+      for (size_t i = 0; i < k; ++i)
+        for (size_t j = 0; j < i; ++j) if (A[i * k + j] != A[j * k + i]) return false;
+      return true;
+    };
+    if (!(finite(cm, n) && finite(cm + n * n, m) && finite(cm + n * n + m * m, n))) return MI_ILQR_E_UNSUPPORTED;
+    asym = !(symmetric(cm, n) && symmetric(cm + n * n, m) && symmetric(cm + n * n + m * m, n));
+  }
+  *regular_out = regular; *asym_out = asym;
+  return MI_ILQR_OK;
+}
+
+// the class the kernels run with: the rows' in per-problem mode, the shared matrices' otherwise
+static void apply_cost_class(mi_ilqr* h) {
+  h->exact_backward = h->per_problem_costs ? h->rows_exact_backward : h->shared_exact_backward;
+  h->cost_asym = h->per_problem_costs ? h->rows_cost_asym : h->shared_cost_asym;
+}
+
+static void drop_per_problem_costs(mi_ilqr* h) {
+  h->per_problem_costs = false;
+  h->cost_rows_synced = false;
+  h->h_cost_rows.clear();
+  apply_cost_class(h);
+}
+
+// Per-problem cost matrices (MI_F_COST_MATRICES): (B, 2 n^2 + m^2) rows, row b = Q_b | R_b | Qf_b.  Every row is classified like
+// mi_ilqr_set_cost classifies the shared matrices, and the handle runs the most general form a row needs.  The host mirror
+// h_cost_rows - the rows as the kernels get them, i.e. after the n >= 33 round-off symmetrisation - is what mi_ilqr_get returns; the
+// device copies follow it on the handle's stream.  src == NULL with bytes == 0: back to the shared matrices.
+static int set_cost_rows(mi_ilqr* h, const double* src, size_t bytes) {
+  const size_t B = h->B, n = h->n, m = h->m, len = 2 * n * n + m * m;
+  if (!src && bytes == 0) { drop_per_problem_costs(h); return MI_ILQR_OK; }
+  if (bytes != B * len * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  for (size_t i = 0; i < B * len; ++i) if (!std::isfinite(src[i])) return MI_ILQR_E_BAD_ARG;
+  std::vector<double> rows(src, src + B * len);
+  bool regular_all = true, asym_any = false;
+  for (size_t b = 0; b < B; ++b) {
+    bool regular = true, asym = false;
+    const int rc = classify_cost(h, rows.data() + b * len, &regular, &asym);
+    if (rc != MI_ILQR_OK) return rc;
+    regular_all = regular_all && regular;
+    asym_any = asym_any || asym;
+  }
+  // (the rows' class is committed with the rows, below: a call that fails on the way changes nothing)
+  auto commit_class = [&] { h->rows_exact_backward = regular_all ? 0 : 1; h->rows_cost_asym = asym_any ? 1 : 0; apply_cost_class(h); };
+  // nothing to send when the caller repeats the rows it set before (Solve() pushes them on every call)
+  if (h->per_problem_costs && h->cost_rows_synced && std::memcmp(rows.data(), h->h_cost_rows.data(), bytes) == 0) { commit_class(); return MI_ILQR_OK; }
+  HIPCHK(hipSetDevice(h->d.device_id));
+  if (!h->cost_rows) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->cost_rows), bytes));
+  if (h->batch_minor && !h->cost_cols) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->cost_cols), bytes));
+  // kernels already enqueued (mi_ilqr_solve_async) read the previous rows: stage_h2d copies on the handle's stream, behind them
+  h->cost_rows_synced = false;
+  int rc = stage_h2d(h, h->cost_rows, rows.data(), bytes);
+  if (rc == MI_ILQR_OK && h->batch_minor) {
+    std::vector<double> cols(B * len);
+    for (size_t b = 0; b < B; ++b)
+      for (size_t k = 0; k < len; ++k) cols[k * B + b] = rows[b * len + k];
+    rc = stage_h2d(h, h->cost_cols, cols.data(), bytes);
+  }
+  if (rc != MI_ILQR_OK) { drop_per_problem_costs(h); return rc; }   // the device copies are undefined now: the shared matrices again
+  h->h_cost_rows.swap(rows);
+  h->cost_rows_synced = true;
+  h->per_problem_costs = true;
+  commit_class();
+  return MI_ILQR_OK;
+}
+
+static int get_cost_rows(mi_ilqr* h, double* dst, size_t bytes) {
+  const size_t B = h->B, len = 2 * (size_t)h->n * h->n + (size_t)h->m * h->m;
+  if (bytes != B * len * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (h->per_problem_costs) std::memcpy(dst, h->h_cost_rows.data(), bytes);
+  else for (size_t b = 0; b < B; ++b) std::memcpy(dst + b * len, h->h_costmat.data(), len * 8);
+  return MI_ILQR_OK;
+}
+
 int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const double* Qf, const double* x_nom) {
   if (!h) return MI_ILQR_E_BAD_ARG;
   HIPCHK(hipSetDevice(h->d.device_id));
   const size_t n = h->n, m = h->m;
   if (x_nom) drop_per_problem_targets(h);   // one target for the batch again: the per-problem targets and steps are dropped
   {
-    // The time-parallel / matrix-core backward passes use Vxx = Vxx^T and (scan) PSD second-order terms; the
-    // reference accepts ANY Q, R, Qf and never symmetrizes (ilqr.py:182,653-667).  Matrices outside that
-    // class are served by the reference's recursion verbatim (wave- and lane-per-problem kernels), by the mid-size
-    // matrix-core pass with every use of symmetry switched off (n <= 32), or refused (n >= 33).
     std::vector<double> cm = h->h_costmat;
     if (Q) std::memcpy(cm.data(), Q, n * n * 8);
     if (R) std::memcpy(cm.data() + n * n, R, m * m * 8);
     if (Qf) std::memcpy(cm.data() + n * n + m * m, Qf, n * n * 8);
     if (x_nom) std::memcpy(cm.data() + 2 * n * n + m * m, x_nom, n * 8);
-    if (h->large && n > 32) {
-      // The n >= 33 workgroup-per-problem kernels' matrix-core pass has no form without symmetry (the plain-arithmetic pass that
-      // takes over - large_backward_asym - is ~4 x slower per step), and matrices built as A^T A or by float arithmetic are often
-      // symmetric only to round-off: asymmetries up to a few ulps of the largest entry are averaged away here
-      // (|A - A^T| <= 8 eps max|A|) so that they keep the fast pass; anything larger is followed as given.
-      // (n <= 32: matrices are taken as given, like the reference does.)
-      auto symmetrize = [](double* A, size_t k) {
-        double scale = 0.0;
-        for (size_t i = 0; i < k * k; ++i) scale = std::fmax(scale, std::fabs(A[i]));
-        for (size_t i = 0; i < k; ++i)
-          for (size_t j = 0; j < i; ++j) if (std::fabs(A[i * k + j] - A[j * k + i]) > 8 * 2.220446049250313e-16 * scale) return;
-        for (size_t i = 0; i < k; ++i)
-          for (size_t j = 0; j < i; ++j) A[i * k + j] = A[j * k + i] = 0.5 * (A[i * k + j] + A[j * k + i]);
-      };
-      symmetrize(cm.data(), n); symmetrize(cm.data() + n * n, m); symmetrize(cm.data() + n * n + m * m, n);
+    bool regular = true, asym = false;
+    if (classify_cost(h, cm.data(), &regular, &asym) != MI_ILQR_OK) {
+      std::fprintf(stderr, "mi_ilqr_set_cost: Q, R, Qf must be finite\n");
+      return MI_ILQR_E_UNSUPPORTED;
     }
-    const bool regular = is_sym_psd(cm.data(), (int)n, false) && is_sym_psd(cm.data() + n * n + m * m, (int)n, false) &&
-                         is_sym_psd(cm.data() + n * n, (int)m, true);
-    bool asym = false;
-    if (!regular && h->large) {
-      // Definiteness is not required of the workgroup-per-problem kernels - they check it where it matters: every
-      // Quu = 2R + fu^T Vxx fu of every backward pass (MI_STATUS_NOT_PD, or mi_ilqr_desc.on_indefinite = 1: inverted with partial
-      // pivoting like the reference's np.linalg.inv, ilqr.py:655).  SYMMETRY: the mid-size kernels (n <= 32, mid_backward) follow
-      // the reference on any matrices - lxx = 2Q and luu = 2R as given, lx = 2Qx - 2 x_nom^T Q, Vx' = Qx - Qu^T Quu^{-1} Qux with
-      // the inverse of a Quu that is not symmetric, Vxx stored in full (ilqr.py:180-184,651-667); the n >= 33 kernels, whose
-      // matrix-core pass mirrors tiles of the symmetric products, take a plain-arithmetic pass for such matrices (round 6:
-      // large_backward_asym; they refused them before).
-      auto finite = [](const double* A, size_t k) {
-        for (size_t i = 0; i < k * k; ++i) if (!(std::fabs(A[i]) < INFINITY)) return false;
-        return true;
-      };
-      auto symmetric = [](const double* A, size_t k) {
-        for (size_t i = 0; i < k; ++i)
-          for (size_t j = 0; j < i; ++j) if (A[i * k + j] != A[j * k + i]) return false;
-        return true;
-      };
-      if (!(finite(cm.data(), n) && finite(cm.data() + n * n, m) && finite(cm.data() + n * n + m * m, n))) {
-        std::fprintf(stderr, "mi_ilqr_set_cost: Q, R, Qf must be finite\n");
-        return MI_ILQR_E_UNSUPPORTED;
-      }
-      asym = !(symmetric(cm.data(), n) && symmetric(cm.data() + n * n, m) && symmetric(cm.data() + n * n + m * m, n));
-    }
-    h->cost_asym = asym ? 1 : 0;
-    h->exact_backward = regular ? 0 : 1;
+    h->shared_cost_asym = asym ? 1 : 0;
+    h->shared_exact_backward = regular ? 0 : 1;
+    // one set of matrices for the batch again: the per-problem cost matrices are dropped (x_nom alone leaves them alone)
+    if (Q || R || Qf) drop_per_problem_costs(h);
+    else apply_cost_class(h);
     // the device copy mirrors h_costmat: nothing to send when the caller repeats the matrices it set before
     // (Solve() pushes them on every call, like the reference reads its attributes on every call)
     if (h->costmat_synced && std::memcmp(cm.data(), h->h_costmat.data(), cm.size() * 8) == 0) return MI_ILQR_OK;
@@ -1445,6 +1548,7 @@ int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
   if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return get_target_field(h, which, dst, bytes);
   if (which == MI_F_MODEL_PARAMS) return get_model_params(h, dst, bytes);
+  if (which == MI_F_COST_MATRICES) return get_cost_rows(h, dst, bytes);
   Field f = field_of(h, which);
   if (!f.ptr || f.is_int) return MI_ILQR_E_BAD_ARG;
   if (bytes != f.bytes && !prefix_ok(which, bytes, f.bytes)) return MI_ILQR_E_BAD_SHAPE;
@@ -1475,6 +1579,7 @@ int mi_ilqr_get_async(mi_ilqr_t* h, int which, void* dst, size_t bytes) {
     return get_target_field(h, which, static_cast<double*>(dst), bytes);
   }
   if (which == MI_F_MODEL_PARAMS) return get_model_params(h, static_cast<double*>(dst), bytes);   // (a host mirror as well)
+  if (which == MI_F_COST_MATRICES) return get_cost_rows(h, static_cast<double*>(dst), bytes);
   Field f = field_of(h, which);
   if (!f.ptr) return MI_ILQR_E_BAD_ARG;
   if (bytes != f.bytes && !prefix_ok(which, bytes, f.bytes)) return MI_ILQR_E_BAD_SHAPE;
@@ -1514,6 +1619,7 @@ int mi_ilqr_get_int(mi_ilqr_t* h, int which, int32_t* dst, size_t bytes) {
 
 int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
   if (h && which == MI_F_MODEL_PARAMS) return set_model_params(h, src, bytes);   // (src == NULL, bytes == 0: back to shared mode)
+  if (h && which == MI_F_COST_MATRICES) return set_cost_rows(h, src, bytes);     // (the same)
   if (!h || !src) return MI_ILQR_E_BAD_ARG;
   if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return set_target_field(h, which, src, bytes);
   Field f = field_of(h, which);
@@ -1549,6 +1655,12 @@ int mi_ilqr_device_ptr(mi_ilqr_t* h, int which, void** ptr, size_t* bytes) {
     if (!h->per_problem_params) return MI_ILQR_E_BAD_ARG;
     *ptr = h->param_rows;
     if (bytes) *bytes = h->h_param_rows.size() * 8;
+    return MI_ILQR_OK;
+  }
+  if (which == MI_F_COST_MATRICES) {                           // per-problem mode only: the (B, 2 n^2 + m^2) device rows
+    if (!h->per_problem_costs) return MI_ILQR_E_BAD_ARG;
+    *ptr = h->cost_rows;
+    if (bytes) *bytes = h->h_cost_rows.size() * 8;
     return MI_ILQR_OK;
   }
   Field f = field_of(h, which);

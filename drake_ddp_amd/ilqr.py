@@ -190,14 +190,46 @@ class BatchedIterativeLQR:
         return out
 
     def SetRunningCost(self, Q, R):
-        assert Q.shape == (self.n, self.n)
-        assert R.shape == (self.m, self.m)
+        """(n, n) and (m, m): one pair for the batch (the reference's arguments).  (B, n, n) / (B, m, m): every problem its own
+        weights - the reference's SetRunningCost called on each problem's own object (include/mi_ilqr.h: "Per-problem cost
+        matrices").  Any mix of the two forms, with SetTerminalCost's as well: the shared ones are repeated.  With all three
+        matrices 2-D again the handle is back on shared matrices.  Takes effect for the next solve; survives Reset()."""
+        assert Q.shape in ((self.n, self.n), (self.B, self.n, self.n))
+        assert R.shape in ((self.m, self.m), (self.B, self.m, self.m))
         self.Q = Q
         self.R = R
 
     def SetTerminalCost(self, Qf):
-        assert Qf.shape == (self.n, self.n)
+        """(n, n), or (B, n, n): every problem its own terminal weights (SetRunningCost)."""
+        assert Qf.shape in ((self.n, self.n), (self.B, self.n, self.n))
         self.Qf = Qf
+
+    def _per_problem_costs(self):
+        return any(np.ndim(a) == 3 for a in (self.Q, self.R, self.Qf))
+
+    def _cost_rows(self):
+        """(B, 2 n^2 + m_dev^2): row b = Q_b | R_b | Qf_b as the device takes them (MI_F_COST_MATRICES), shared matrices repeated."""
+        B, n, md = self.B, self.n, self._md
+        R = np.asarray(self.R, dtype=np.float64)
+        if self._md != self.m:                      # padding controls: a unit block, like the shared R gets
+            Rp = np.zeros(R.shape[:-2] + (md, md))
+            Rp[..., :self.m, :self.m] = R
+            Rp[..., range(self.m, md), range(self.m, md)] = 1.0
+            R = Rp
+        parts = [np.broadcast_to(np.asarray(a, dtype=np.float64), (B, k, k)).reshape(B, k * k)
+                 for a, k in ((self.Q, n), (R, md), (self.Qf, n))]
+        rows = np.ascontiguousarray(np.concatenate(parts, axis=1))
+        if not np.isfinite(rows).all():
+            raise ValueError("SetRunningCost / SetTerminalCost: NaN or infinity in per-problem cost matrices")
+        return rows
+
+    @property
+    def cost_matrices(self):
+        """(Q, R, Qf) as (B, n, n), (B, m, m), (B, n, n): the weights each problem is solved with, as set (the shared matrices
+        repeated where SetRunningCost / SetTerminalCost gave 2-D ones)."""
+        B, n, m = self.B, self.n, self.m
+        return tuple(np.array(np.broadcast_to(np.asarray(a, dtype=np.float64), (B, k, k)))
+                     for a, k in ((self.Q, n), (self.R, m), (self.Qf, n)))
 
     def SetInitialGuess(self, u_guess):
         assert u_guess.shape in ((self.m, self.N - 1), (self.B, self.m, self.N - 1))
@@ -234,11 +266,18 @@ class BatchedIterativeLQR:
     # ------------------------------------------------------------- boundary traffic
     def _push_problem(self):
         x_nom = self.x_nom             # AttributeError if SetTargetState was never called, as in the reference
-        Q, R, Qf = (_capi.as_f64(a) for a in (self.Q, self._pad_u(self.R, (0, 1), diag=1.0), self.Qf))
         per_problem = np.ndim(x_nom) == 2
         xn = None if per_problem else _capi.as_f64(x_nom, (self.n,))
-        _capi.check(self._lib.mi_ilqr_set_cost(self._h, _capi.ptr(Q), _capi.ptr(R), _capi.ptr(Qf), _capi.ptr(xn)),
-                    "mi_ilqr_set_cost")
+        if self._per_problem_costs():
+            # (B, ..) weights: the handle's per-problem cost matrices; the shared ones stay what they were, x_nom goes alone
+            rows = self._cost_rows()
+            if xn is not None:
+                _capi.check(self._lib.mi_ilqr_set_cost(self._h, None, None, None, _capi.ptr(xn)), "mi_ilqr_set_cost")
+            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_COST_MATRICES, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
+        else:                          # (shared matrices switch per-problem cost matrices off again)
+            Q, R, Qf = (_capi.as_f64(a) for a in (self.Q, self._pad_u(self.R, (0, 1), diag=1.0), self.Qf))
+            _capi.check(self._lib.mi_ilqr_set_cost(self._h, _capi.ptr(Q), _capi.ptr(R), _capi.ptr(Qf), _capi.ptr(xn)),
+                        "mi_ilqr_set_cost")
         if per_problem:                # (B, n): the handle's per-problem targets (a shared x_nom above switches them off again)
             self._set_field(_capi.F_X_NOM, x_nom)
         x0 = np.asarray(self.x0, dtype=np.float64).reshape(-1, self.n)

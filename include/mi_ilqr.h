@@ -123,6 +123,7 @@ enum {
   MI_F_X_NOM = 14,      /* (B,n) per-problem targets x_nom_b (mi_ilqr_set_cost, "Per-problem targets" below)              */
   MI_F_TARGET_STEP = 15,/* (B,n) per-problem target_step_b of mi_ilqr_mpc_run                                             */
   MI_F_MODEL_PARAMS = 16,/* (B,n_params) per-problem model parameters: problem b's plant ("Per-problem model parameters" below) */
+  MI_F_COST_MATRICES = 17,/* (B,2*n*n+m*m) per-problem cost matrices, row b = Q_b | R_b | Qf_b ("Per-problem cost matrices" below) */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
@@ -279,6 +280,26 @@ int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const doubl
  * MI_ILQR_E_BAD_ARG; a model without parameters (n_params == 0) MI_ILQR_E_UNSUPPORTED; a refused call changes nothing.  Every
  * kernel family (cluster helpers and helper wavefronts read the row of the problem they serve), control-limited handles, solve,
  * mpc_run in both forms and the stage entries; it combines with per-problem targets and per-problem control limits. */
+
+/* PER-PROBLEM COST MATRICES (the reference's SetRunningCost / SetTerminalCost are per solver object: B objects may carry B weight
+ * sets - sweeps and random searches over Q / R / Qf, inverse optimal control, a different effort penalty per robot of a fleet).
+ * The matrices are the shared ones of mi_ilqr_set_cost until
+ *   mi_ilqr_set(MI_F_COST_MATRICES, rows, B*(2*n*n+m*m)*8)  gives problem b row b of the (B,2*n*n+m*m) array, Q_b | R_b | Qf_b each
+ *                                        row-major - the order of mi_ilqr_set_cost's matrices, without x_nom, which stays with the
+ *                                        targets - and switches the handle to PER-PROBLEM COST MATRICES;
+ *   mi_ilqr_set(MI_F_COST_MATRICES, NULL, 0)  returns it to SHARED mode: to whatever mi_ilqr_set_cost last set;
+ *   mi_ilqr_set_cost with any of Q, R, Qf non-NULL returns it to shared mode as well (x_nom alone does not);
+ *   a handle back in shared mode is bitwise a handle that never left it;
+ *   mi_ilqr_get returns the (B,2*n*n+m*m) rows in both modes (shared mode: the shared matrices repeated);
+ *   mi_ilqr_device_ptr returns the device rows in per-problem mode (MI_ILQR_E_BAD_ARG in shared mode); the lane-per-problem kernels
+ *   read a copy of their own, made by mi_ilqr_set: write through mi_ilqr_set there.
+ * Every row is classified like mi_ilqr_set_cost classifies its matrices (symmetric positive semi-definite / any other / not
+ * symmetric; n >= 33: asymmetries of round-off size are averaged away first, row by row, and mi_ilqr_get returns the rows so
+ * averaged), and the handle runs the most general kernel form any of its rows needs - for all rows.  Rows that all equal the
+ * shared matrices give the shared handle's results bit for bit.  The rows are problem data: they survive mi_ilqr_reset.  Errors:
+ * wrong `bytes` MI_ILQR_E_BAD_SHAPE; a NaN or an infinity MI_ILQR_E_BAD_ARG; a refused call changes nothing.  Every kernel family
+ * (cluster helpers read the row of the problem they serve), control-limited handles, solve, mpc_run in both forms and the stage
+ * entries; it combines with per-problem targets and per-problem model parameters. */
 
 /* SetInitialState / SetInitialGuess (ilqr.py:102-109,148-156): x0 (B,n), u_guess (B,m,N-1).
  * u_guess becomes u_bar (the reference aliases it, ilqr.py:156).  NULL = keep.
