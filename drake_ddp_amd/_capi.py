@@ -28,6 +28,7 @@ F_X_BAR, F_U_BAR, F_K, F_KAPPA, F_DV, F_FX, F_FU, F_COST, F_X0, F_HIST, F_X_TRIA
 F_X_NOM, F_TARGET_STEP = 14, 15   # (B, n) per-problem targets and MPC target steps (mi_ilqr.h: "Per-problem targets")
 F_MODEL_PARAMS = 16               # (B, n_params) per-problem model parameters (mi_ilqr.h: "Per-problem model parameters")
 F_COST_MATRICES = 17              # (B, 2n^2+m^2) per-problem cost matrices, row b = Q_b | R_b | Qf_b (mi_ilqr.h: "Per-problem cost matrices")
+F_POLICY_KERNEL_MS = 18           # (1,) ms of the rollout kernel of the last mi_ilqr_policy_rollout
 I_ITERS, I_STATUS, I_LS_TRIALS, I_KP_COUNT, I_KP_LIST = 100, 101, 102, 103, 104
 I64_STAGE_CYCLES = 200
 I64_CLUSTER_WORDS = 201
@@ -44,6 +45,9 @@ EXPORTS = [
     "mi_ilqr_comm_unique_id", "mi_ilqr_comm_create", "mi_ilqr_comm_destroy", "mi_ilqr_comm_count", "mi_ilqr_allreduce_min",
     "mi_ilqr_allreduce_min_start", "mi_ilqr_allreduce_min_wait",
 ]
+# mi_ilqr_policy_rollout is declared in include/mi_ilqr_policy.h, not in mi_ilqr.h - a workaround explained there: EXPORTS is tied
+# to mi_ilqr.h's own declarations by the tests, so EXPORTS + POLICY_EXPORTS is the library's full list
+POLICY_EXPORTS = ["mi_ilqr_policy_rollout"]
 
 
 class Desc(C.Structure):
@@ -110,6 +114,7 @@ def load():
     lib.mi_ilqr_set_result_sink.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mi_ilqr_solve_into.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(Stats), C.POINTER(C.c_int32)]
+    lib.mi_ilqr_policy_rollout.argtypes = [H, C.c_int32] + [C.c_void_p] * 7
     lib.mi_ilqr_mpc_shift.argtypes = [H, C.c_int32]
     lib.mi_ilqr_mpc_run.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(Stats)]
     lib.mi_ilqr_get_mpc_log.argtypes = [H, C.c_void_p, C.c_size_t]

@@ -119,6 +119,10 @@ struct mi_ilqr {
   // gets the shared x_nom broadcast into these (B, n) rows before a launch (refresh_lane_target_rows)
   double* lane_x_nom_rows = nullptr;
   std::vector<double> h_lane_x_nom;    // the x_nom the device rows hold now (empty: none)
+  // mi_ilqr_policy_rollout: start / stop events of its rollout kernel (created on first use; MI_F_POLICY_KERNEL_MS) - its own pair,
+  // so that the solves' events and statistics stay what they were
+  hipEvent_t policy_ev0 = nullptr, policy_ev1 = nullptr;
+  bool policy_ran = false;         // the events hold a launch (a policy rollout has run on this handle)
 };
 
 // Run-time switches for A/B runs (README): the environment is read once per process.
@@ -179,6 +183,9 @@ constexpr size_t kMaxLds = 160 * 1024;
 // A model's launch entry asked with this mode answers MI_ILQR_OK when it carries Limited<M> kernels, launching nothing
 // (mi_ilqr_set_control_limits; family-1 plugins carry them when built with them: plugin.py, control_limits=True).
 constexpr int kModeProbeLimits = 0x4c494d;
+// mi_ilqr_policy_rollout: the launch entry takes a PolicyArgs (below), not a KArgs, and launches policy_rollout_kernel<M>
+// (policy_rollout.hpp) whatever kernel family serves the handle's solves.
+constexpr int kModePolicyRollout = 0x504f4c;
 constexpr int kMaxBatchPluginN = 6;      // family-0 models up to this n also get the lane-per-problem kernels
 
 // The dynamic-LDS ceiling of a kernel is raised once per (kernel, device), to the hardware maximum - not
@@ -242,6 +249,26 @@ template <class M> MI_INTERNAL int launch_jac_large_limited(mi_ilqr* h, int mode
 template <class M> MI_INTERNAL int launch_batch(mi_ilqr* h, int mode, const KArgs& a);               // launch_batch.hpp
 template <class M> MI_INTERNAL int launch_batch_limited(mi_ilqr* h, int mode, const KArgs& a);
 
+// Arguments of policy_rollout_kernel<M> (policy_rollout.hpp), all device pointers.  "Sample-minor": the sample index runs fastest.
+struct PolicyArgs {
+  const double* policy;       // (B, N-1, n + m + m n): row t = x_bar_t | u_bar_t | K_t (m x n, row-major) - the call's time-major copy
+  const double* x0;           // (B, n, S) sample-minor
+  const double* params;       // (B, n_params, S) sample-minor, or nullptr: every sample runs on param_rows
+  const double* param_rows;   // (B or 1, n_params): problem b's row at b * param_stride
+  const double* cost;         // Q | R | Qf of problem b at b * cost_stride
+  const double* x_nom;        // (n,) of problem b at b * x_nom_stride
+  const double* ulim;         // (B, 2, m) u_min | u_max, or nullptr: no clamp
+  double* cost_out;           // (B, S)
+  double* x_final;            // (B, n, S) sample-minor
+  int32_t* steps;             // (B, S)
+  double* X;                  // (B, N, n, S) sample-minor, or nullptr
+  double* U;                  // (B, N-1, m, S) sample-minor, or nullptr
+  size_t param_stride, cost_stride, x_nom_stride;
+  double dt;
+  int32_t N, S, B, m_user;    // m_user: controls m_user .. m-1 are padding and stay exact zeros
+};
+template <class M> MI_INTERNAL int launch_policy_rollout(mi_ilqr* h, const PolicyArgs& a);          // policy_rollout.hpp
+
 // The launch entry of a model's record (mi_ilqr_model_plugin::launch), built-in or plugin: the handle picks the kernel set - the
 // lane-per-problem kernels (h->batch_minor), the Limited<M> ones (h->limited), else the regular ones.  A set the model lacks is
 // nullptr; the probe (kModeProbeLimits) answers whether it has Limited<M> kernels, launching nothing.
@@ -255,5 +282,11 @@ int launch_entry(mi_ilqr* h, int mode, const void* kargs) {
   }
   if constexpr (LIMITED != nullptr) if (h->limited) return LIMITED(h, mode, a);
   return REGULAR(h, mode, a);
+}
+// ... and the same for model M with the policy rollout (kModePolicyRollout), which is one kernel per model whatever the handle's family
+template <class M, Launcher REGULAR, Launcher LIMITED = nullptr, Launcher BATCH = nullptr, Launcher BATCH_LIMITED = nullptr>
+int model_entry(mi_ilqr* h, int mode, const void* kargs) {
+  if (mode == kModePolicyRollout) return launch_policy_rollout<M>(h, *static_cast<const PolicyArgs*>(kargs));
+  return launch_entry<REGULAR, LIMITED, BATCH, BATCH_LIMITED>(h, mode, kargs);
 }
 }  // namespace mi_host

@@ -67,16 +67,17 @@ Model builtin(int family, size_t (*lds)(int32_t, int32_t), int (*launch)(mi_ilqr
   r.cluster_max_B = cluster_max_B;
   return r;
 }
-// wave-per-problem kernels (k_<model>.hip, k_<model>_lim.hip) and the lane-per-problem ones (k_batch.hip, k_batch_lim.hip)
+// wave-per-problem kernels (k_<model>.hip, k_<model>_lim.hip) and the lane-per-problem ones (k_batch.hip, k_batch_lim.hip); every
+// model's policy-rollout kernels are in k_policy.hip
 template <class M>
 Model wave_model(std::initializer_list<double> defaults) {
   return builtin<M>(0, wave_lds<M::n, M::m>,
-                    launch_entry<launch_jac<M>, launch_limited<M>, launch_batch<M>, launch_batch_limited<M>>, 0, defaults);
+                    model_entry<M, launch_jac<M>, launch_limited<M>, launch_batch<M>, launch_batch_limited<M>>, 0, defaults);
 }
 // workgroup-per-problem kernels (k_<model>.hip; with control limits, k_<model>_lim.hip)
 template <class M, Launcher LIMITED = nullptr>
 Model workgroup_model(int cluster_max_B, std::initializer_list<double> defaults) {
-  return builtin<M>(1, workgroup_lds<M::n, M::m>, launch_entry<launch_jac_large<M>, LIMITED>, cluster_max_B, defaults);
+  return builtin<M>(1, workgroup_lds<M::n, M::m>, model_entry<M, launch_jac_large<M>, LIMITED>, cluster_max_B, defaults);
 }
 
 const Model kBuiltins[] = {
@@ -376,6 +377,66 @@ __global__ void __launch_bounds__(256) broadcast_u_kernel(const double* __restri
     else { const size_t r = e / B; t = (int)(r / m); k = (int)(r - (size_t)t * m); }
     dst[e] = src[(size_t)k * len + t];
   }
+}
+
+// mi_ilqr_policy_rollout: the call's time-major copy of the policy, (B, N-1, W) with W = n + m + m n and row t = x_bar_t | u_bar_t |
+// K_t (m x n, row-major), gathered from the handle's kernel layout (LAYOUT_TL / TM / BM).  A source that is nullptr reads as zeros:
+// the state of a cold handle, the controls of a reset one.
+__global__ void __launch_bounds__(256) policy_pack_kernel(const double* __restrict__ x_bar, const double* __restrict__ u_bar,
+                                                            const double* __restrict__ K, double* __restrict__ dst,
+                                                            int B, int n, int m, int N, int layout) {
+  const int W = n + m + m * n, M1 = N - 1;
+  const size_t total = (size_t)B * M1 * W;
+  auto at = [&](const double* f, int rows, int len, int b, int r, int t) -> double {
+    if (!f) return 0.0;
+    if (layout == LAYOUT_TL) return f[((size_t)b * rows + r) * len + t];
+    if (layout == LAYOUT_TM) return f[((size_t)b * len + t) * rows + r];
+    return f[((size_t)t * rows + r) * B + b];
+  };
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const int w = (int)(e % W);
+    const size_t bt = e / W;
+    const int t = (int)(bt % M1), b = (int)(bt / M1);
+    dst[e] = w < n ? at(x_bar, n, N, b, w, t) : (w < n + m ? at(u_bar, m, M1, b, w - n, t) : at(K, m * n, M1, b, w - n - m, t));
+  }
+}
+
+// Batched (R x C) -> (C x R) transposes with pitches, 32 x 32 tiles through LDS so that reads and writes are both coalesced: matrix
+// z = (o, i), i < inner; element (r, c) is read at src[o src_outer + i src_inner + r src_r + c], written at dst[o dst_outer +
+// i dst_inner + c dst_c + r].  The sample-minor <-> boundary conversions of mi_ilqr_policy_rollout.  grid = (ceil(C/32), ceil(R/32), <= Z).
+__global__ void __launch_bounds__(256) transpose_tiles_kernel(const double* __restrict__ src, double* __restrict__ dst, int R, int C,
+                                                                int Z, int inner, size_t src_outer, size_t src_inner, size_t src_r,
+                                                                size_t dst_outer, size_t dst_inner, size_t dst_c) {
+  __shared__ double tile[32][33];
+  const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;          // 32 x 8 threads
+  for (int z = blockIdx.z; z < Z; z += gridDim.z) {
+    const int o = z / inner, i = z - o * inner;
+    const double* s_ = src + (size_t)o * src_outer + (size_t)i * src_inner;
+    double* d_ = dst + (size_t)o * dst_outer + (size_t)i * dst_inner;
+    for (int j = ty; j < 32; j += 8) {
+      const int r = r0 + j, c = c0 + tx;
+      if (r < R && c < C) tile[j][tx] = s_[(size_t)r * src_r + c];
+    }
+    __syncthreads();
+    for (int j = ty; j < 32; j += 8) {
+      const int c = c0 + j, r = r0 + tx;
+      if (r < R && c < C) d_[(size_t)c * dst_c + r] = tile[tx][j];
+    }
+    __syncthreads();
+  }
+}
+
+int transpose_tiles(mi_ilqr* h, const double* src, double* dst, int R, int C, size_t outer, int inner, size_t src_outer, size_t src_inner,
+                    size_t src_r, size_t dst_outer, size_t dst_inner, size_t dst_c) {
+  const size_t Z = outer * (size_t)inner;
+  if (Z > 0x7fffffffull) return MI_ILQR_E_UNSUPPORTED;
+  const dim3 grid((C + 31) / 32, (R + 31) / 32, (unsigned)std::min<size_t>(Z, 65535));
+  if (grid.y > 65535) return MI_ILQR_E_UNSUPPORTED;
+  hipLaunchKernelGGL(transpose_tiles_kernel, grid, dim3(256), 0, h->stream, src, dst, R, C, (int)Z, inner, src_outer, src_inner, src_r,
+                     dst_outer, dst_inner, dst_c);
+  HIPCHK(hipGetLastError());
+  return MI_ILQR_OK;
 }
 
 // rows of the (rows,len) time-last view of a double field; 0 = not a trajectory array
@@ -832,6 +893,8 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
   if (h->u_one) (void)hipFree(h->u_one);
   if (h->pin_in) (void)hipHostFree(h->pin_in);
   if (h->pin_ev) (void)hipEventDestroy(h->pin_ev);
+  if (h->policy_ev0) (void)hipEventDestroy(h->policy_ev0);
+  if (h->policy_ev1) (void)hipEventDestroy(h->policy_ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1425,6 +1488,81 @@ int mi_ilqr_backward(mi_ilqr_t* h) {
   return mi_ilqr_synchronize(h);
 }
 
+int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const double* params, double* cost, double* x_final,
+                           int32_t* steps, double* X, double* U) {
+  if (!h || S < 1 || !x0 || !cost) return MI_ILQR_E_BAD_ARG;
+  const Model* model = model_of(h->d.model_id);
+  const size_t B = h->B, n = h->n, m = h->m, N = h->N, np = model->p.n_params, Sz = (size_t)S, W = n + m + m * n;
+  if (params && np == 0) return MI_ILQR_E_UNSUPPORTED;
+  if (params) for (size_t i = 0; i < B * Sz * np; ++i) if (!std::isfinite(params[i])) return MI_ILQR_E_BAD_ARG;
+  HIPCHK(hipSetDevice(h->d.device_id));
+  // one block of the handle's grow-only scratch, in doubles: the policy's time-major copy | inputs as they arrive and sample-minor |
+  // outputs sample-minor and in the boundary's layout
+  size_t off = 0;
+  auto take = [&](size_t count) { const size_t o = off; off += (count + 31) & ~(size_t)31; return o; };
+  const size_t o_pol = take(B * (N - 1) * W), o_x0_in = take(B * Sz * n), o_x0 = take(B * n * Sz);
+  const size_t o_p_in = take(params ? B * Sz * np : 0), o_p = take(params ? B * np * Sz : 0), o_prow = take(np ? np : 1);
+  const size_t o_cost = take(B * Sz), o_steps = take((B * Sz + 1) / 2), o_xf = take(B * n * Sz), o_xf_out = take(B * Sz * n);
+  const size_t o_X = take(X ? B * N * n * Sz : 0), o_X_out = take(X ? B * Sz * n * N : 0);
+  const size_t o_U = take(U ? B * (N - 1) * m * Sz : 0), o_U_out = take(U ? B * Sz * m * (N - 1) : 0);
+  int rc = ensure_scratch(h, off * 8);
+  if (rc != MI_ILQR_OK) return rc;
+  double* const sc = h->scratch;
+  if (!h->policy_ev0) {
+    HIPCHK(hipEventCreate(&h->policy_ev0));
+    HIPCHK(hipEventCreate(&h->policy_ev1));
+  }
+  // the policy as the handle holds it now: a cold handle's x_bar and K read as zeros, a reset one's u_bar too, a pending initial
+  // guess is the u_bar the next launch would start from - nothing of the handle is written
+  const double* u_src = h->u_pending ? h->u_guess : (h->u_zero ? nullptr : h->u_bar);
+  {
+    const size_t total = B * (N - 1) * W;
+    const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
+    hipLaunchKernelGGL(policy_pack_kernel, dim3(blocks), dim3(256), 0, h->stream, h->cold ? nullptr : h->x_bar, u_src,
+                       h->cold ? nullptr : h->K, sc + o_pol, (int)B, (int)n, (int)m, (int)N,
+                       h->batch_minor ? LAYOUT_BM : (h->large ? LAYOUT_TM : LAYOUT_TL));
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(sc + o_x0_in, x0, B * Sz * n * 8, hipMemcpyHostToDevice, h->stream));
+  if ((rc = transpose_tiles(h, sc + o_x0_in, sc + o_x0, S, (int)n, B, 1, Sz * n, 0, n, n * Sz, 0, Sz)) != MI_ILQR_OK) return rc;
+  if (params) {
+    HIPCHK(hipMemcpyAsync(sc + o_p_in, params, B * Sz * np * 8, hipMemcpyHostToDevice, h->stream));
+    if ((rc = transpose_tiles(h, sc + o_p_in, sc + o_p, S, (int)np, B, 1, Sz * np, 0, np, np * Sz, 0, Sz)) != MI_ILQR_OK) return rc;
+  } else if (np && !h->per_problem_params) {
+    if ((rc = stage_h2d(h, sc + o_prow, h->d.model_params, np * 8)) != MI_ILQR_OK) return rc;
+  }
+  PolicyArgs a{};
+  a.policy = sc + o_pol; a.x0 = sc + o_x0; a.params = params ? sc + o_p : nullptr;
+  a.param_rows = h->per_problem_params ? h->param_rows : sc + o_prow; a.param_stride = h->per_problem_params ? np : 0;
+  a.cost = h->per_problem_costs ? h->cost_rows : h->costmat; a.cost_stride = h->per_problem_costs ? 2 * n * n + m * m : 0;
+  a.x_nom = h->per_problem_targets ? h->x_nom_rows : h->costmat + 2 * n * n + m * m; a.x_nom_stride = h->per_problem_targets ? n : 0;
+  a.ulim = h->limited ? h->ulim : nullptr;
+  a.cost_out = sc + o_cost; a.x_final = sc + o_xf; a.steps = reinterpret_cast<int32_t*>(sc + o_steps);
+  a.X = X ? sc + o_X : nullptr; a.U = U ? sc + o_U : nullptr;
+  a.dt = h->d.dt; a.N = (int32_t)N; a.S = S; a.B = (int32_t)B; a.m_user = model->p.m_user > 0 ? model->p.m_user : (int32_t)m;
+  h->policy_ran = false;
+  if ((rc = model->p.launch(h, kModePolicyRollout, &a)) != MI_ILQR_OK) return rc;
+  h->policy_ran = true;
+  // sample-minor -> the boundary's layouts: x_final (B,S,n), X (B,S,n,N), U (B,S,m,N-1)
+  HIPCHK(hipMemcpyAsync(cost, sc + o_cost, B * Sz * 8, hipMemcpyDeviceToHost, h->stream));
+  if (steps) HIPCHK(hipMemcpyAsync(steps, sc + o_steps, B * Sz * 4, hipMemcpyDeviceToHost, h->stream));
+  if (x_final) {
+    if ((rc = transpose_tiles(h, sc + o_xf, sc + o_xf_out, (int)n, S, B, 1, n * Sz, 0, Sz, Sz * n, 0, n)) != MI_ILQR_OK) return rc;
+    HIPCHK(hipMemcpyAsync(x_final, sc + o_xf_out, B * Sz * n * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (X) {
+    if ((rc = transpose_tiles(h, sc + o_X, sc + o_X_out, (int)N, S, B, (int)n, N * n * Sz, Sz, n * Sz, Sz * n * N, N, n * N)) != MI_ILQR_OK) return rc;
+    HIPCHK(hipMemcpyAsync(X, sc + o_X_out, B * Sz * n * N * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (U) {
+    if ((rc = transpose_tiles(h, sc + o_U, sc + o_U_out, (int)N - 1, S, B, (int)m, (N - 1) * m * Sz, Sz, m * Sz, Sz * m * (N - 1), N - 1,
+                              m * (N - 1))) != MI_ILQR_OK) return rc;
+    HIPCHK(hipMemcpyAsync(U, sc + o_U_out, B * Sz * m * (N - 1) * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return MI_ILQR_OK;
+}
+
 int mi_ilqr_mpc_shift(mi_ilqr_t* h, int32_t replan_steps) {
   if (!h) return MI_ILQR_E_BAD_ARG;
   if (replan_steps < 1 || replan_steps >= h->N - 1) return MI_ILQR_E_BAD_ARG;
@@ -1549,6 +1687,16 @@ int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
   if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return get_target_field(h, which, dst, bytes);
   if (which == MI_F_MODEL_PARAMS) return get_model_params(h, dst, bytes);
   if (which == MI_F_COST_MATRICES) return get_cost_rows(h, dst, bytes);
+  if (which == MI_F_POLICY_KERNEL_MS) {        // the rollout kernel of the last mi_ilqr_policy_rollout, from its own events
+    if (bytes != 8) return MI_ILQR_E_BAD_SHAPE;
+    if (!h->policy_ran) return MI_ILQR_E_BAD_ARG;
+    float ms = 0.0f;
+    HIPCHK(hipSetDevice(h->d.device_id));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipEventElapsedTime(&ms, h->policy_ev0, h->policy_ev1));
+    *dst = (double)ms;
+    return MI_ILQR_OK;
+  }
   Field f = field_of(h, which);
   if (!f.ptr || f.is_int) return MI_ILQR_E_BAD_ARG;
   if (bytes != f.bytes && !prefix_ok(which, bytes, f.bytes)) return MI_ILQR_E_BAD_SHAPE;

@@ -60,6 +60,47 @@ def check_model_params(params, B, n_params):
     return np.ascontiguousarray(a)
 
 
+def check_rollout_args(x0, params, B, n, n_params):
+    """RolloutPolicy's arguments as contiguous (B, S, n) and (B, S, n_params) float64 arrays (None for params=None).
+    ValueError for a wrong rank or size and for NaN / infinity in params - decided here, before anything reaches the device.
+    A non-finite x0 is data: that sample ends before its first step."""
+    try:
+        x0 = np.asarray(x0, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"RolloutPolicy: x0 is not an array of numbers ({e})") from None
+    if x0.ndim == 2 and x0.shape[1] == n and x0.shape[0] >= 1:
+        x0 = np.broadcast_to(x0, (B,) + x0.shape)
+    elif not (x0.ndim == 3 and x0.shape[0] == B and x0.shape[1] >= 1 and x0.shape[2] == n):
+        raise ValueError(f"RolloutPolicy: x0 must be ({B}, S, {n}) or (S, {n}) with S >= 1; got {x0.shape}")
+    S = x0.shape[1]
+    if params is not None:
+        if n_params == 0:
+            raise ValueError("RolloutPolicy: this model has no parameters")
+        try:
+            params = np.asarray(params, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"RolloutPolicy: params is not an array of numbers ({e})") from None
+        if params.shape == (S, n_params):
+            params = np.broadcast_to(params, (B, S, n_params))
+        elif params.shape != (B, S, n_params):
+            raise ValueError(f"RolloutPolicy: params must be ({B}, {S}, {n_params}) or ({S}, {n_params}); got {params.shape}")
+        if not np.isfinite(params).all():
+            raise ValueError("RolloutPolicy: NaN or infinity in params")
+        params = np.ascontiguousarray(params)
+    return np.ascontiguousarray(x0), params
+
+
+class PolicyRollout:
+    """What RolloutPolicy returns: cost, x_final, steps and - asked for - the trajectories X, U (else None)."""
+    __slots__ = ("cost", "x_final", "steps", "X", "U")
+
+    def __init__(self, cost, x_final, steps, X=None, U=None):
+        self.cost, self.x_final, self.steps, self.X, self.U = cost, x_final, steps, X, U
+
+    def _without_batch_axis(self):
+        return PolicyRollout(*(None if a is None else a[0] for a in (self.cost, self.x_final, self.steps, self.X, self.U)))
+
+
 class BatchedIterativeLQR:
     """B independent iLQR problems sharing model, horizon and cost, solved on one GPU.
 
@@ -265,21 +306,7 @@ class BatchedIterativeLQR:
 
     # ------------------------------------------------------------- boundary traffic
     def _push_problem(self):
-        x_nom = self.x_nom             # AttributeError if SetTargetState was never called, as in the reference
-        per_problem = np.ndim(x_nom) == 2
-        xn = None if per_problem else _capi.as_f64(x_nom, (self.n,))
-        if self._per_problem_costs():
-            # (B, ..) weights: the handle's per-problem cost matrices; the shared ones stay what they were, x_nom goes alone
-            rows = self._cost_rows()
-            if xn is not None:
-                _capi.check(self._lib.mi_ilqr_set_cost(self._h, None, None, None, _capi.ptr(xn)), "mi_ilqr_set_cost")
-            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_COST_MATRICES, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
-        else:                          # (shared matrices switch per-problem cost matrices off again)
-            Q, R, Qf = (_capi.as_f64(a) for a in (self.Q, self._pad_u(self.R, (0, 1), diag=1.0), self.Qf))
-            _capi.check(self._lib.mi_ilqr_set_cost(self._h, _capi.ptr(Q), _capi.ptr(R), _capi.ptr(Qf), _capi.ptr(xn)),
-                        "mi_ilqr_set_cost")
-        if per_problem:                # (B, n): the handle's per-problem targets (a shared x_nom above switches them off again)
-            self._set_field(_capi.F_X_NOM, x_nom)
+        self._push_costs()
         x0 = np.asarray(self.x0, dtype=np.float64).reshape(-1, self.n)
         x0 = np.ascontiguousarray(x0 if len(x0) == self.B else np.broadcast_to(x0, (self.B, self.n)))
         ug = None
@@ -300,6 +327,24 @@ class BatchedIterativeLQR:
             _capi.check(self._lib.mi_ilqr_set_initial_shared(self._h, _capi.ptr(x0), _capi.ptr(ug)), "mi_ilqr_set_initial_shared")
         else:
             _capi.check(self._lib.mi_ilqr_set_initial(self._h, _capi.ptr(x0), _capi.ptr(ug)), "mi_ilqr_set_initial")
+
+    def _push_costs(self):
+        """The cost matrices and targets as set on this object, to the handle (what every Solve / stage call does first)."""
+        x_nom = self.x_nom             # AttributeError if SetTargetState was never called, as in the reference
+        per_problem = np.ndim(x_nom) == 2
+        xn = None if per_problem else _capi.as_f64(x_nom, (self.n,))
+        if self._per_problem_costs():
+            # (B, ..) weights: the handle's per-problem cost matrices; the shared ones stay what they were, x_nom goes alone
+            rows = self._cost_rows()
+            if xn is not None:
+                _capi.check(self._lib.mi_ilqr_set_cost(self._h, None, None, None, _capi.ptr(xn)), "mi_ilqr_set_cost")
+            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_COST_MATRICES, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
+        else:                          # (shared matrices switch per-problem cost matrices off again)
+            Q, R, Qf = (_capi.as_f64(a) for a in (self.Q, self._pad_u(self.R, (0, 1), diag=1.0), self.Qf))
+            _capi.check(self._lib.mi_ilqr_set_cost(self._h, _capi.ptr(Q), _capi.ptr(R), _capi.ptr(Qf), _capi.ptr(xn)),
+                        "mi_ilqr_set_cost")
+        if per_problem:                # (B, n): the handle's per-problem targets (a shared x_nom above switches them off again)
+            self._set_field(_capi.F_X_NOM, x_nom)
 
     _POOL_CAP = 4
 
@@ -613,6 +658,33 @@ class BatchedIterativeLQR:
         self._push_problem()
         _capi.check(self._lib.mi_ilqr_backward(self._h), "mi_ilqr_backward")
 
+    # ------------------------------------------------------------- Monte-Carlo rollouts of the policy
+    def RolloutPolicy(self, x0, params=None, trajectories=False):
+        """Roll out S samples per problem under the policy the solver holds - u = u_bar - K (x - x_bar), the reason SaveSolution
+        stores K (ilqr.py:712-733) - one GPU lane per sample, in one call (include/mi_ilqr_policy.h: mi_ilqr_policy_rollout).
+        x0: (B, S, n), or (S, n) for every problem.  params: None - each problem's own plant - or (B, S, n_params) / (S, n_params),
+        a plant per sample.  Costs, targets and control limits are the solver's, per-problem where set.  Returns a PolicyRollout:
+        cost (B, S) - +inf for a sample that ended at an infeasible or non-finite step -, x_final (B, S, n), steps (B, S) and, with
+        trajectories=True, X (B, S, n, N) and U (B, S, m, N-1) with NaN in the columns a sample did not reach.  Changes nothing in
+        the solver: a Solve() after the call is the Solve() without it."""
+        x0, params = check_rollout_args(x0, params, self.B, self.n, int(self.system.params.size))
+        self._push_costs()
+        B, S = self.B, x0.shape[1]
+        cost, x_final, steps = np.empty((B, S)), np.empty((B, S, self.n)), np.empty((B, S), dtype=np.int32)
+        X = np.empty((B, S, self.n, self.N)) if trajectories else None
+        U = np.empty((B, S, self._md, self.N - 1)) if trajectories else None
+        _capi.check(self._lib.mi_ilqr_policy_rollout(self._h, S, _capi.ptr(x0), _capi.ptr(params), _capi.ptr(cost), _capi.ptr(x_final),
+                                                     _capi.ptr(steps), _capi.ptr(X), _capi.ptr(U)), "mi_ilqr_policy_rollout")
+        if U is not None and self._md != self.m:
+            U = np.ascontiguousarray(U[:, :, :self.m, :])
+        return PolicyRollout(cost, x_final, steps, X, U)
+
+    def policy_kernel_ms(self):
+        """Milliseconds of the rollout kernel of the last RolloutPolicy call (HIP events of its own)."""
+        out = np.empty(1)
+        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_KERNEL_MS, _capi.ptr(out), 8), "mi_ilqr_get")
+        return float(out[0])
+
     # ------------------------------------------------------------- multi-GPU helper
     def best_cost_allreduce(self):
         """min over all ranks of the best converged cost — the ONE collective of the
@@ -746,6 +818,12 @@ class IterativeLinearQuadraticRegulator(BatchedIterativeLQR):
         if res is not None:
             return res[0].reshape(self.n, self.N), res[1][0], total_time, float(res[2][0])
         return self.x_bar, self.u_bar, total_time, float(self.cost[0])
+
+    def RolloutPolicy(self, x0, params=None, trajectories=False):
+        """x0 (S, n), params None or (S, n_params): cost (S,), x_final (S, n), steps (S,)[, X (S, n, N), U (S, m, N-1)]."""
+        if np.ndim(x0) != 2:
+            raise ValueError(f"RolloutPolicy: x0 must be (S, {self.n}); got {np.shape(x0)}")
+        return super().RolloutPolicy(x0, params, trajectories)._without_batch_axis()
 
     def SaveSolution(self, fname):
         """ilqr.py:712-733: npz with t, x_bar (last step dropped), u_bar, K."""

@@ -124,6 +124,7 @@ enum {
   MI_F_TARGET_STEP = 15,/* (B,n) per-problem target_step_b of mi_ilqr_mpc_run                                             */
   MI_F_MODEL_PARAMS = 16,/* (B,n_params) per-problem model parameters: problem b's plant ("Per-problem model parameters" below) */
   MI_F_COST_MATRICES = 17,/* (B,2*n*n+m*m) per-problem cost matrices, row b = Q_b | R_b | Qf_b ("Per-problem cost matrices" below) */
+  MI_F_POLICY_KERNEL_MS = 18,/* (1,) read-only: milliseconds of the rollout kernel of the last policy rollout, from its own HIP events (mi_ilqr_policy.h) */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
@@ -487,4 +488,6 @@ size_t mi_ilqr_lds_bytes(const mi_ilqr_desc* desc);
 #ifdef __cplusplus
 }
 #endif
+/* the policy rollouts: declared in a companion header for now (a workaround, explained there) */
+#include "mi_ilqr_policy.h"
 #endif /* MI_ILQR_H */

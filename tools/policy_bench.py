@@ -1,0 +1,97 @@
+"""Sample-steps per second of the policy rollout (BatchedIterativeLQR.RolloutPolicy, csrc/policy_rollout.hpp) on one GPU, beside the
+only equivalent the library offered before it: a (B S)-problem handle with the policy replicated by set_state and one
+stage_rollout(0.0).
+
+    python tools/policy_bench.py [--reps R] [--warmup W] [--configs pendulum,quad3d] [--samples 64,1024] [--emulate-up-to P]
+
+Shapes: pendulum B = 1024, N = 200; Quad3D B = 64, N = 40; each at S = 64 and S = 1024 samples per problem.  The policy is what a
+capped solve leaves on the handle; the samples are the problems' own x0 plus seeded perturbations (all rollouts run to the end).
+Both paths are timed with HIP events around their ONE kernel (policy_kernel_ms / last_kernel_ms): `reps` launches after `warmup`,
+median and the min .. max spread; sample-steps/s = B S (N - 1) / kernel time.  The emulation's handle holds the whole solver state
+of B S problems (fx alone is B S n^2 (N-1) doubles: 27 GB for Quad3D at S = 1024, which still runs), so it runs where B S <=
+--emulate-up-to (default 65536: everything but the pendulum at S = 1024, a 1 M-problem handle) - the rates are per sample-step and
+compare across S.  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import warnings
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def problem(config):
+    from drake_ddp_amd import workloads as W
+    if config == "quad3d":
+        p, B = W.quad3d_problem(40), 64
+        return p, B, W.quad3d_batch_x0(B), W.quad3d_u_guess(40), 1e-3
+    p, B = W.pendulum_problem(), 1024
+    return p, B, W.pendulum_batch_x0(B), np.zeros((1, p["N"] - 1)), 0.05
+
+
+def solver(p, B, **kw):
+    from drake_ddp_amd.ilqr import BatchedIterativeLQR
+    from drake_ddp_amd.models import ModelSystem
+    s = BatchedIterativeLQR(ModelSystem(p["model_id"], p["dt"]), p["N"], B, delta=p["delta"], beta=p["beta"], gamma=p["gamma"],
+                            hist_cap=2, pinned_results=False, **kw)
+    s.SetTargetState(p["x_nom"]); s.SetRunningCost(p["Q"], p["R"]); s.SetTerminalCost(p["Qf"])
+    return s
+
+
+def summary(ms, work):
+    ms = np.asarray(ms)
+    med = float(np.median(ms))
+    return dict(kernel_ms=med, kernel_ms_min=float(ms.min()), kernel_ms_max=float(ms.max()), sample_steps_per_s=work / (med * 1e-3))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--configs", default="pendulum,quad3d")
+    ap.add_argument("--samples", default="64,1024")
+    ap.add_argument("--emulate-up-to", type=int, default=65536)
+    a = ap.parse_args()
+    out = {}
+    for config in a.configs.split(","):
+        p, B, x0b, ug, sigma = problem(config)
+        N, n = p["N"], x0b.shape[1]
+        s = solver(p, B, max_iters=5)
+        s.SetInitialState(x0b); s.SetInitialGuess(ug)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            s.Solve()
+        pol = dict(x_bar=np.array(s.x_bar), u_bar=np.array(s.u_bar), K=np.array(s.K))
+        for S in (int(v) for v in a.samples.split(",")):
+            rng = np.random.default_rng(S)
+            x0 = x0b[:, None, :] + sigma * rng.standard_normal((B, S, n))
+            work = float(B) * S * (N - 1)
+            ms = []
+            for i in range(a.warmup + a.reps):
+                r = s.RolloutPolicy(x0)
+                if i >= a.warmup:
+                    ms.append(s.policy_kernel_ms())
+            res = dict(B=B, S=S, N=N, full_rollouts=int((r.steps == N - 1).sum()), policy_rollout=summary(ms, work))
+            if B * S <= a.emulate_up_to:
+                e = solver(p, B * S)
+                e.set_state(**{k: np.repeat(v, S, axis=0) for k, v in pol.items()})
+                e.SetInitialState(x0.reshape(B * S, n))
+                ms = []
+                for i in range(a.warmup + a.reps):
+                    _, _, L, _ = e.stage_rollout(0.0)
+                    if i >= a.warmup:
+                        ms.append(e.last_kernel_ms())
+                res["emulation"] = summary(ms, work)
+                res["speedup"] = res["emulation"]["kernel_ms"] / res["policy_rollout"]["kernel_ms"]
+                fin = np.isfinite(r.cost.ravel())
+                res["max_rel_cost_difference"] = float(np.max(np.abs(L[fin] - r.cost.ravel()[fin]) / np.abs(L[fin])))
+                del e
+            out["%s_S%d" % (config, S)] = res
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
