@@ -43,11 +43,8 @@ EXPORTS = [
     "mi_ilqr_get", "mi_ilqr_get_int", "mi_ilqr_get_async", "mi_ilqr_set", "mi_ilqr_device_ptr", "mi_ilqr_get_stream",
     "mi_ilqr_synchronize", "mi_ilqr_last_kernel_ms", "mi_ilqr_set_timing", "mi_ilqr_get_cycles", "mi_ilqr_bytes_per_iteration", "mi_ilqr_lds_bytes",
     "mi_ilqr_comm_unique_id", "mi_ilqr_comm_create", "mi_ilqr_comm_destroy", "mi_ilqr_comm_count", "mi_ilqr_allreduce_min",
-    "mi_ilqr_allreduce_min_start", "mi_ilqr_allreduce_min_wait",
+    "mi_ilqr_allreduce_min_start", "mi_ilqr_allreduce_min_wait", "mi_ilqr_policy_rollout",
 ]
-# mi_ilqr_policy_rollout is declared in include/mi_ilqr_policy.h, not in mi_ilqr.h - a workaround explained there: EXPORTS is tied
-# to mi_ilqr.h's own declarations by the tests, so EXPORTS + POLICY_EXPORTS is the library's full list
-POLICY_EXPORTS = ["mi_ilqr_policy_rollout"]
 
 
 class Desc(C.Structure):

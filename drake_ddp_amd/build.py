@@ -34,7 +34,7 @@ def sources():
 
 def headers():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")) + \
-        [os.path.join(HERE, "..", "include", f) for f in ("mi_ilqr.h", "mi_ilqr_policy.h")]
+        [os.path.join(HERE, "..", "include", "mi_ilqr.h")]
 
 
 def _obj(src, tag):

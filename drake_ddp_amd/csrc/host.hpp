@@ -17,6 +17,20 @@
 // library-internal: hidden from the dynamic symbol table (the C ABI is mi_ilqr.h)
 #define MI_INTERNAL __attribute__((visibility("hidden")))
 
+// One per-problem (B, width) array of a handle (mi_ilqr_set MI_F_X_NOM / MI_F_TARGET_STEP / MI_F_MODEL_PARAMS / MI_F_COST_MATRICES;
+// mi_ilqr.hip: store_upload / store_drop / store_read).  The host mirror is the truth: what mi_ilqr_get returns without touching the
+// stream and what mi_ilqr_mpc_run advances; the device copies follow it on the handle's stream.  `synced` - they equal it - is the
+// array's per-problem mode: only then do the kernels get the pointers, a failed copy leaves the mode, and rows the caller repeats
+// (Solve() pushes them on every call) are not sent again.  The buffers are allocated on first use and kept when the mode is
+// dropped, so a handle that alternates between the modes allocates once.  Problem data: mi_ilqr_reset keeps the rows.
+struct RowStore {
+  size_t width = 0;                // doubles per problem
+  bool batch_minor_copy = false;   // `cols` exists: lane-per-problem handles, the arrays their kernels read per lane
+  double *rows = nullptr, *cols = nullptr;   // (B, width) dense; the same values batch-minor, (width, B)
+  std::vector<double> mirror;
+  bool synced = false;
+};
+
 struct mi_ilqr {
   mi_ilqr_desc d;
   int n, m, N, B;
@@ -94,31 +108,17 @@ struct mi_ilqr {
   bool limited = false;
   double* ulim = nullptr;          // (B, 2, m): u_min | u_max per problem (allocated on first use, kept when cleared)
   double* s2 = nullptr;            // (B,): S2 of each problem's last limited backward pass (KArgs::s2)
-  // per-problem targets (mi_ilqr_set MI_F_X_NOM / MI_F_TARGET_STEP): `per_problem_targets` hands the kernels x_nom_rows /
-  // target_steps; the host mirrors are what mi_ilqr_get returns (mi_ilqr_mpc_run advances both copies)
-  bool per_problem_targets = false;
+  // the per-problem arrays: targets and target_steps, (B, n) each, enter and leave their mode together; params (B, n_params);
+  // costs (B, 2 n^2 + m^2), row b = Q_b | R_b | Qf_b as the kernels get it (after the n >= 33 round-off symmetrisation)
+  RowStore targets, target_steps, params, costs;
   bool target_steps_moving = false;   // a row of the steps is non-zero (cluster helpers' candidate groups need a still target)
-  double *x_nom_rows = nullptr, *target_steps = nullptr;   // (B, n) each, allocated on first use, kept when dropped
-  std::vector<double> h_x_nom_rows, h_target_steps;
-  // per-problem model parameters (mi_ilqr_set MI_F_MODEL_PARAMS): `per_problem_params` hands the kernels param_rows, (B, n_params)
-  // dense, and - the lane-per-problem kernels - param_cols, the same values batch-minor, (n_params, B); the host mirror is what
-  // mi_ilqr_get returns.  Problem data: mi_ilqr_reset keeps them.
-  bool per_problem_params = false;
-  double *param_rows = nullptr, *param_cols = nullptr;   // allocated on first use, kept when dropped
-  std::vector<double> h_param_rows;
-  // per-problem cost matrices (mi_ilqr_set MI_F_COST_MATRICES): `per_problem_costs` hands the kernels cost_rows, (B, 2 n^2 + m^2) dense,
-  // row b = Q_b | R_b | Qf_b, and - the lane-per-problem kernels - cost_cols, the same values batch-minor; the host mirror is what
-  // mi_ilqr_get returns.  Problem data: mi_ilqr_reset keeps them.  exact_backward / cost_asym above are the class the kernels run
-  // with: the shared matrices' (shared_*) in shared mode, that of the most general row (rows_*) in per-problem mode.
-  bool per_problem_costs = false;
-  bool cost_rows_synced = false;       // the device copies equal the mirror
-  double *cost_rows = nullptr, *cost_cols = nullptr;   // allocated on first use, kept when dropped
-  std::vector<double> h_cost_rows;
+  // exact_backward / cost_asym above are the class the kernels run with: the shared matrices' (shared_*) in shared mode, that of
+  // the most general row of `costs` (rows_*) in per-problem mode
   int shared_exact_backward = 0, shared_cost_asym = 0, rows_exact_backward = 0, rows_cost_asym = 0;
-  // lane-per-problem kernels: their per-problem-cost instantiations always read target ROWS; a handle without per-problem targets
-  // gets the shared x_nom broadcast into these (B, n) rows before a launch (refresh_lane_target_rows)
-  double* lane_x_nom_rows = nullptr;
-  std::vector<double> h_lane_x_nom;    // the x_nom the device rows hold now (empty: none)
+  // lane-per-problem kernels: their per-problem-cost instantiations always read target ROWS; a handle with one target gets the
+  // shared x_nom broadcast into these (B, n) rows before a launch (refresh_lane_target_rows)
+  RowStore lane_targets;
+  std::vector<void*> owned;        // every device allocation of the handle (dev_alloc): what mi_ilqr_destroy frees
   // mi_ilqr_policy_rollout: start / stop events of its rollout kernel (created on first use; MI_F_POLICY_KERNEL_MS) - its own pair,
   // so that the solves' events and statistics stay what they were
   hipEvent_t policy_ev0 = nullptr, policy_ev1 = nullptr;
@@ -274,7 +274,7 @@ template <class M> MI_INTERNAL int launch_policy_rollout(mi_ilqr* h, const Polic
 // nullptr; the probe (kModeProbeLimits) answers whether it has Limited<M> kernels, launching nothing.
 template <Launcher REGULAR, Launcher LIMITED = nullptr, Launcher BATCH = nullptr, Launcher BATCH_LIMITED = nullptr>
 int launch_entry(mi_ilqr* h, int mode, const void* kargs) {
-  if (mode == kModeProbeLimits) return LIMITED ? MI_ILQR_OK : MI_ILQR_E_UNSUPPORTED;
+  if (mode == kModeProbeLimits) return LIMITED != nullptr ? MI_ILQR_OK : MI_ILQR_E_UNSUPPORTED;
   const KArgs& a = *static_cast<const KArgs*>(kargs);
   if (h->batch_minor) {
     if constexpr (BATCH != nullptr && BATCH_LIMITED != nullptr) return h->limited ? BATCH_LIMITED(h, mode, a) : BATCH(h, mode, a);

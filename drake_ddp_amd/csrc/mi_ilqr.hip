@@ -135,6 +135,14 @@ int cluster_size(const mi_ilqr* h) {
   return std::clamp(h->n_cus > 0 ? h->n_cus / h->B : 1, 1, 8);
 }
 
+// costmat and its host mirror are Q | R | Qf | x_nom: the length of the matrices, and the shared x_nom (host mirror) behind them
+size_t cost_len(const mi_ilqr* h) { return 2 * (size_t)h->n * h->n + (size_t)h->m * h->m; }
+const double* shared_x_nom(const mi_ilqr* h) { return h->h_costmat.data() + cost_len(h); }
+
+// a per-problem array's device rows / batch-minor copy (host.hpp: RowStore) - in its per-problem mode only, else nullptr
+const double* device_rows(const RowStore& s) { return s.synced ? s.rows : nullptr; }
+const double* device_cols(const RowStore& s) { return s.synced ? s.cols : nullptr; }
+
 KArgs make_args(const mi_ilqr* h) {
   KArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -181,14 +189,14 @@ KArgs make_args(const mi_ilqr* h) {
   a.cost_asym = h->cost_asym ? 1 : 0;
   a.ulim = h->limited ? h->ulim : nullptr;
   a.s2 = h->s2;
-  a.x_nom_rows = h->per_problem_targets ? h->x_nom_rows : nullptr;
-  a.target_steps = h->per_problem_targets ? h->target_steps : nullptr;
-  a.cost_rows = h->per_problem_costs ? h->cost_rows : nullptr;
-  a.cost_cols = (h->per_problem_costs && h->batch_minor) ? h->cost_cols : nullptr;
+  a.x_nom_rows = device_rows(h->targets);
+  a.target_steps = device_rows(h->target_steps);
+  a.cost_rows = device_rows(h->costs);
+  a.cost_cols = device_cols(h->costs);
   // (the lane kernels' per-problem-cost instantiations read target rows in any case: the shared target, broadcast by launch())
-  if (a.cost_cols && !a.x_nom_rows) a.x_nom_rows = h->lane_x_nom_rows;
-  a.param_rows = h->per_problem_params ? h->param_rows : nullptr;
-  a.param_cols = (h->per_problem_params && h->batch_minor) ? h->param_cols : nullptr;
+  if (a.cost_cols && !a.x_nom_rows) a.x_nom_rows = device_rows(h->lane_targets);
+  a.param_rows = device_rows(h->params);
+  a.param_cols = device_cols(h->params);
   a.spec_policy = h->x_spec ? sw.spec : 0;
   a.cluster = 1;
   a.cluster_sync = h->cluster_sync;
@@ -209,7 +217,7 @@ KArgs make_args(const mi_ilqr* h) {
     // the cost constants - a target that does not move inside the launch
     bool still = true;
     for (int i = 0; i < h->n; ++i) still = still && h->mpc_target_step[i] == 0.0;
-    if (h->per_problem_targets && h->target_steps_moving) still = false;
+    if (h->target_steps_moving) still = false;
     const bool lsg = sw.ls_groups && still && h->spec_slots >= 4 * g - 1 && g > 1;
     a.cluster = g | ((sw.cluster_order & 3) << 8) | ((sw.early ? 1 : 0) << 10) | ((lsg ? 1 : 0) << 11);
   }
@@ -224,7 +232,7 @@ int refresh_lane_target_rows(mi_ilqr* h);
 
 int launch(mi_ilqr* h, int mode) {
   HIPCHK(hipSetDevice(h->d.device_id));
-  if (h->per_problem_costs && h->batch_minor && !h->per_problem_targets) { const int rc = refresh_lane_target_rows(h); if (rc != MI_ILQR_OK) return rc; }
+  if (h->costs.synced && h->batch_minor && !h->targets.synced) { const int rc = refresh_lane_target_rows(h); if (rc != MI_ILQR_OK) return rc; }
   // any launch other than a pipelined solve reuses the current ring slot: settle the statistics still owed first
   if (!h->in_async_solve) { const int rc = reduce_pending_stats(h); if (rc != MI_ILQR_OK) return rc; }
   if (h->u_zero && !h->u_pending) HIPCHK(hipMemsetAsync(h->u_bar, 0, (size_t)h->B * h->m * (h->N - 1) * 8, h->stream));
@@ -301,6 +309,7 @@ __global__ void mpc_shift_kernel_bm(const double* x_bar, const double* u_bar, do
 // [t][row][b] (lane-per-problem kernels).  The conversions run on the DEVICE, between the field and a
 // staging buffer; the host copy is then one linear transfer.
 enum { LAYOUT_TL = 0, LAYOUT_TM = 1, LAYOUT_BM = 2 };
+int layout_of(const mi_ilqr* h) { return h->batch_minor ? LAYOUT_BM : (h->large ? LAYOUT_TM : LAYOUT_TL); }
 
 // TL <-> TM: a per-problem (rows x len) transpose; both sides of a problem fit the caches, a gather is enough.
 __global__ void __launch_bounds__(256) relayout_tm_kernel(const double* __restrict__ src, double* __restrict__ dst,
@@ -343,19 +352,41 @@ __global__ void __launch_bounds__(256) relayout_bm_kernel(const double* __restri
   }
 }
 
+// The handle's device memory: every allocation is recorded in h->owned, which is what mi_ilqr_destroy frees - a buffer allocated on
+// first use, or by a create that fails half-way, needs no line of its own there.  dev_free releases one early (buffers that are re-grown).
+template <class T>
+int dev_alloc(mi_ilqr* h, T*& p, size_t count, bool zero = false) {
+  void* q = nullptr;
+  HIPCHK(hipMalloc(&q, count * sizeof(T)));
+  h->owned.push_back(q);
+  if (zero) HIPCHK(hipMemset(q, 0, count * sizeof(T)));
+  p = static_cast<T*>(q);
+  return MI_ILQR_OK;
+}
+template <class T>
+int dev_free(mi_ilqr* h, T*& p) {
+  if (!p) return MI_ILQR_OK;
+  void* q = p;
+  const auto it = std::find(h->owned.begin(), h->owned.end(), q);
+  if (it != h->owned.end()) h->owned.erase(it);
+  p = nullptr;
+  HIPCHK(hipFree(q));
+  return MI_ILQR_OK;
+}
+
 int ensure_scratch(mi_ilqr* h, size_t bytes) {
   if (h->scratch_bytes >= bytes) return MI_ILQR_OK;
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (h->scratch) HIPCHK(hipFree(h->scratch));
-  h->scratch = nullptr; h->scratch_bytes = 0;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->scratch), bytes));
-  h->scratch_bytes = bytes;
-  return MI_ILQR_OK;
+  h->scratch_bytes = 0;
+  int rc = dev_free(h, h->scratch);
+  if (rc == MI_ILQR_OK) rc = dev_alloc(h, h->scratch, (bytes + 7) / 8);
+  if (rc == MI_ILQR_OK) h->scratch_bytes = bytes;
+  return rc;
 }
 
 // Convert between the handle's kernel layout and time-last, on the handle's stream.
 int relayout(mi_ilqr* h, const double* src, double* dst, int rows, int len, bool to_kernel_layout) {
-  if (h->batch_minor) {
+  if (layout_of(h) == LAYOUT_BM) {
     const dim3 grid((len + 31) / 32, (h->B + 31) / 32, rows);
     hipLaunchKernelGGL(relayout_bm_kernel, grid, dim3(256), 0, h->stream, src, dst, h->B, rows, len, to_kernel_layout ? 1 : 0);
   } else {
@@ -454,6 +485,15 @@ int traj_rows(const mi_ilqr* h, int which, int* len) {
   return 0;
 }
 
+// Does this double field cross the boundary through a layout conversion (relayout), and with which rows and length?  The
+// trajectory arrays of the handles whose kernel layout is not time-last - except single-row ones in the time-major layout, which
+// are the same bytes either way.  A control sequence handed to mi_ilqr_set_initial has MI_F_U_BAR's shape.
+bool needs_relayout(const mi_ilqr* h, int which, int* rows, int* len) {
+  const int layout = layout_of(h);
+  *rows = layout == LAYOUT_TL ? 0 : traj_rows(h, which, len);
+  return *rows > 1 || (layout == LAYOUT_BM && *rows == 1);
+}
+
 // Aggregate per-problem results on the device so a blocking solve costs ONE small host read
 // (pinned, device-mapped) instead of four D2H copies.
 
@@ -542,18 +582,71 @@ int stage_h2d(mi_ilqr* h, void* dst, const void* src, size_t bytes) {
   return MI_ILQR_OK;
 }
 
+// The protocol of a per-problem array (host.hpp: RowStore).  store_upload: (B, width) rows from the host become the array's contents
+// and the handle enters its per-problem mode.  Rows that equal what the device already holds are not sent.  Kernels already enqueued
+// (mi_ilqr_solve_async) read the previous rows: stage_h2d copies on the handle's stream, behind them.  The mirror is committed only
+// once every copy is enqueued; a failed allocation or copy leaves the mode - the device copies are undefined then, and the handle
+// falls back to what it can vouch for - and returns the error.
+void store_drop(RowStore& s) {
+  s.synced = false;
+  s.mirror.clear();
+}
+
+int store_upload(mi_ilqr* h, RowStore& s, const double* src) {
+  const size_t B = h->B, cnt = B * s.width;
+  if (s.synced && std::memcmp(s.mirror.data(), src, cnt * 8) == 0) return MI_ILQR_OK;
+  store_drop(s);
+  HIPCHK(hipSetDevice(h->d.device_id));
+  int rc = MI_ILQR_OK;
+  if (!s.rows) rc = dev_alloc(h, s.rows, cnt);
+  if (rc == MI_ILQR_OK && s.batch_minor_copy && !s.cols) rc = dev_alloc(h, s.cols, cnt);
+  if (rc == MI_ILQR_OK) rc = stage_h2d(h, s.rows, src, cnt * 8);
+  if (rc == MI_ILQR_OK && s.batch_minor_copy) {
+    std::vector<double> cols(cnt);
+    for (size_t b = 0; b < B; ++b)
+      for (size_t k = 0; k < s.width; ++k) cols[k * B + b] = src[b * s.width + k];
+    rc = stage_h2d(h, s.cols, cols.data(), cnt * 8);
+  }
+  if (rc != MI_ILQR_OK) return rc;
+  s.mirror.assign(src, src + cnt);
+  s.synced = true;
+  return MI_ILQR_OK;
+}
+
+// ... and the same with ONE row for every problem
+int store_upload_broadcast(mi_ilqr* h, RowStore& s, const double* row) {
+  std::vector<double> rows((size_t)h->B * s.width);
+  for (size_t b = 0; b < (size_t)h->B; ++b) std::memcpy(rows.data() + b * s.width, row, s.width * 8);
+  return store_upload(h, s, rows.data());
+}
+
+// mi_ilqr_get of a per-problem array: the mirror; in shared mode `shared_row` for every problem, or zeros (nullptr)
+int store_read(const mi_ilqr* h, const RowStore& s, const double* shared_row, double* dst, size_t bytes) {
+  if (s.width == 0) return MI_ILQR_E_UNSUPPORTED;
+  if (bytes != (size_t)h->B * s.width * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (s.synced) std::memcpy(dst, s.mirror.data(), bytes);
+  else if (!shared_row) std::memset(dst, 0, bytes);
+  else for (size_t b = 0; b < (size_t)h->B; ++b) std::memcpy(dst + b * s.width, shared_row, s.width * 8);
+  return MI_ILQR_OK;
+}
+
+// The selectors of mi_ilqr_get / mi_ilqr_device_ptr that are per-problem arrays: the store, and the row every problem reports in shared mode
+struct RowField { RowStore* store; const double* shared_row; };
+RowField row_field(mi_ilqr* h, int which) {
+  switch (which) {
+    case MI_F_X_NOM: return {&h->targets, shared_x_nom(h)};
+    case MI_F_TARGET_STEP: return {&h->target_steps, nullptr};
+    case MI_F_MODEL_PARAMS: return {&h->params, h->d.model_params};
+    case MI_F_COST_MATRICES: return {&h->costs, h->h_costmat.data()};
+  }
+  return {nullptr, nullptr};
+}
+
 // The lane-per-problem kernels' per-problem-cost instantiations on a handle with ONE target: its x_nom as (B, n) rows.
 int refresh_lane_target_rows(mi_ilqr* h) {
-  const size_t B = h->B, n = h->n;
-  const double* xn = h->h_costmat.data() + 2 * n * n + (size_t)h->m * h->m;   // the shared x_nom (host mirror)
-  if (h->lane_x_nom_rows && h->h_lane_x_nom.size() == n && std::memcmp(h->h_lane_x_nom.data(), xn, n * 8) == 0) return MI_ILQR_OK;
-  if (!h->lane_x_nom_rows) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->lane_x_nom_rows), B * n * 8));
-  std::vector<double> rows(B * n);
-  for (size_t b = 0; b < B; ++b) std::memcpy(rows.data() + b * n, xn, n * 8);
-  h->h_lane_x_nom.clear();
-  const int rc = stage_h2d(h, h->lane_x_nom_rows, rows.data(), B * n * 8);
-  if (rc == MI_ILQR_OK) h->h_lane_x_nom.assign(xn, xn + n);
-  return rc;
+  RowStore& s = h->lane_targets;      // (only ever one row repeated: the first says what all of them are, on every launch)
+  if (s.synced && std::memcmp(s.mirror.data(), shared_x_nom(h), s.width * 8) == 0) return MI_ILQR_OK;
+  return store_upload_broadcast(h, s, shared_x_nom(h));
 }
 
 struct Field { void* ptr; size_t bytes; bool is_int; };
@@ -602,6 +695,120 @@ double bytes_per_iteration(int n, int m, int N, int ls) {
   const double deriv = (N - 1.0) * ((n + m) + ((double)n * n + (double)n * m));
   const double back = (N - 1.0) * ((n + m) + ((double)n * n + (double)n * m) + ((double)m * n + m + 1)) + n;
   return 8.0 * (ls * roll + deriv + back);
+}
+
+// The device and host resources of a new handle, zeroed.  mi_ilqr_create destroys the handle when this fails, which frees whatever
+// was allocated up to there.
+int create_resources(mi_ilqr* h, bool lxu_hbm) {
+  const size_t n = h->n, m = h->m, N = h->N, B = h->B;
+  const bool large = h->large, batch_minor = h->batch_minor, every_step = every_step_keypoint(h->d);
+  {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->d.device_id) == hipSuccess) h->n_cus = cus;
+  }
+  int rc = MI_ILQR_OK;      // (sticky: after a failed allocation the ones behind it are not tried)
+  auto zeroed = [&](auto*& p, size_t count) { if (rc == MI_ILQR_OK) rc = dev_alloc(h, p, count, true); };
+  zeroed(h->x_bar, B * n * N);
+  zeroed(h->u_bar, B * m * (N - 1));
+  zeroed(h->K, B * m * n * (N - 1));
+  zeroed(h->kappa, B * m * (N - 1));
+  zeroed(h->dV, B * (N - 1));
+  zeroed(h->fx, B * n * n * (N - 1));
+  zeroed(h->fu, B * n * m * (N - 1));
+  const bool host_rec = B <= 4;              // (host.hpp: host_records)
+  const bool host_in = host_rec && !large && !batch_minor;   // ... and the inputs x0, u_guess (wave-per-problem kernels: the boundary's layout)
+  if (!host_in) {
+    zeroed(h->x0, B * n);
+    zeroed(h->u_guess, B * m * (N - 1));
+  }
+  zeroed(h->cost_ring, B * mi_ilqr::kStatsRing);
+  if (host_rec) {
+    auto up = [](size_t v) { return (v + 63) & ~(size_t)63; };
+    const size_t s_hist = up(B * (size_t)h->d.hist_cap * 4 * 8), s_prof = up(B * 4 * 8), s_ring = up(B * mi_ilqr::kStatsRing * 4);
+    const size_t s_x0 = host_in ? up(B * n * 8) : 0, s_ug = host_in ? up(B * m * (N - 1) * 8) : 0;
+    h->host_records_bytes = 2 * s_hist + s_prof + 2 * s_ring + s_x0 + s_ug;
+    void* dv = nullptr;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->host_records), h->host_records_bytes, hipHostMallocMapped));
+    HIPCHK(hipHostGetDevicePointer(&dv, h->host_records, 0));
+    std::memset(h->host_records, 0, h->host_records_bytes);
+    h->host_records_dev = static_cast<char*>(dv);
+    char* q = h->host_records_dev;
+    h->hist = reinterpret_cast<double*>(q); q += s_hist;
+    h->iter_cyc = reinterpret_cast<double*>(q); q += s_hist;
+    h->prof = reinterpret_cast<long long*>(q); q += s_prof;
+    h->iters_ring = reinterpret_cast<int32_t*>(q); q += s_ring;
+    h->status_ring = reinterpret_cast<int32_t*>(q); q += s_ring;
+    if (host_in) { h->x0 = reinterpret_cast<double*>(q); q += s_x0; h->u_guess = reinterpret_cast<double*>(q); h->host_inputs = true; }
+  } else {
+    zeroed(h->hist, B * (size_t)h->d.hist_cap * 4);
+    zeroed(h->iter_cyc, B * (size_t)h->d.hist_cap * 4);
+  }
+  zeroed(h->x_trial, B * n * N);
+  zeroed(h->u_trial, B * m * (N - 1));
+  zeroed(h->trial_cost, B * 2);
+  zeroed(h->stage_in, B);
+  zeroed(h->costmat, cost_len(h) + n);
+  if (!host_rec) {
+    zeroed(h->iters_ring, B * mi_ilqr::kStatsRing);
+    zeroed(h->status_ring, B * mi_ilqr::kStatsRing);
+    zeroed(h->prof, B * 4);
+  }
+  zeroed(h->ls_ring, B * mi_ilqr::kStatsRing);
+  zeroed(h->kp_count, B);
+  zeroed(h->kp_list, B * (N - 1));
+  zeroed(h->done_counter, 1);
+  if (large) zeroed(h->cluster_sync, B * kSyncWords);
+  if (lxu_hbm) zeroed(h->lxu, B * (N - 1) * (n + m));
+  if (batch_minor && !every_step) zeroed(h->bm_scratch, B * 6 * (N - 1));
+  if (rc != MI_ILQR_OK) return rc;
+  if (large && n <= 32) {
+    // mid-size kernels: four line-search candidates per pass - an optimization, so a batch too large for three more
+    // trial buffers simply searches one candidate at a time (make_args: spec_policy = 0 without them)
+    // (batches small enough for clusters: 31 slots - the candidates 1 .. 31 of a first pass that the leader and up to seven helper
+    //  workgroups roll out together, ilqr_large.hpp: candidate groups)
+    // ... as many as the cluster size make_args will pick asks for (cluster_size): 4 g - 1 (15 at B = 64 on 256 CUs), 3 when the
+    // launch will not be clustered - plugin models unless MI_ILQR_CLUSTER forces it, batches beyond 64, fewer than two CUs per
+    // problem.  (Round 5 allocated 31 for every batch up to 64: 1 GB of HBM for nothing on an n = 32, N = 2000 plugin.)
+    // (a failure here is an answer, not an error: plain hipMalloc, and the pair joins the handle's allocations once it stands)
+    const int g = cluster_size(h);
+    h->spec_slots = g > 1 ? 4 * g - 1 : 3;
+    for (;;) {
+      const size_t xb = (size_t)h->spec_slots * B * n * N * sizeof(double), ub = (size_t)h->spec_slots * B * m * (N - 1) * sizeof(double);
+      if (hipMalloc(reinterpret_cast<void**>(&h->x_spec), xb) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&h->u_spec), ub) == hipSuccess) break;
+      (void)hipGetLastError();
+      if (h->x_spec) (void)hipFree(h->x_spec);
+      h->x_spec = nullptr; h->u_spec = nullptr;
+      if (h->spec_slots == 3) { h->spec_slots = 0; break; }
+      h->spec_slots = 3;
+    }
+    if (h->x_spec) { h->owned.push_back(h->x_spec); h->owned.push_back(h->u_spec); }
+  }
+  if (batch_minor && every_step) {
+    // the KP = false lane-per-problem kernels never write the key-point list: every step is a key-point (ilqr.py:417-432), the
+    // same list for every problem and every linearization - stored once here
+    std::vector<int32_t> kl(B * (N - 1));
+    for (size_t i = 0; i < kl.size(); ++i) kl[i] = (int32_t)(i % (N - 1));
+    HIPCHK(hipMemcpy(h->kp_list, kl.data(), kl.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  // defaults Q=I, R=I, Qf=I, x_nom=0 (ilqr.py:61-67)
+  {
+    std::vector<double> cm(cost_len(h) + n, 0.0);
+    for (size_t i = 0; i < n; ++i) { cm[i * n + i] = 1.0; cm[n * n + m * m + i * n + i] = 1.0; }
+    for (size_t i = 0; i < m; ++i) cm[n * n + i * m + i] = 1.0;
+    HIPCHK(hipMemcpy(h->costmat, cm.data(), cm.size() * 8, hipMemcpyHostToDevice));
+    h->h_costmat = cm;
+    h->costmat_synced = true;
+  }
+  HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  for (int i = 0; i < mi_ilqr::kStatsRing; ++i) {
+    HIPCHK(hipEventCreate(&h->ring_ev0[i]));
+    HIPCHK(hipEventCreate(&h->ring_ev1[i]));
+  }
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_ring), sizeof(DevStats) * mi_ilqr::kStatsRing, hipHostMallocMapped));
+  HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_ring), h->h_ring, 0));
+  std::memset(h->h_ring, 0, sizeof(DevStats) * mi_ilqr::kStatsRing);
+  select_stats_slot(h, 0);
+  return MI_ILQR_OK;
 }
 
 }  // namespace
@@ -745,125 +952,12 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   h->large = large;
   h->n_store = n_store;
   h->batch_minor = batch_minor;
-  {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, desc->device_id) == hipSuccess) h->n_cus = cus;
-  }
-  const size_t n = h->n, m = h->m, N = h->N, B = h->B;
-
-#define ALLOC(p, count, T)                                             \
-  do {                                                                 \
-    if (hipMalloc(reinterpret_cast<void**>(&(p)), (count) * sizeof(T)) != hipSuccess) { mi_ilqr_destroy(h); return MI_ILQR_E_HIP; } \
-    if (hipMemset((p), 0, (count) * sizeof(T)) != hipSuccess) { mi_ilqr_destroy(h); return MI_ILQR_E_HIP; } \
-  } while (0)
-  ALLOC(h->x_bar, B * n * N, double);
-  ALLOC(h->u_bar, B * m * (N - 1), double);
-  ALLOC(h->K, B * m * n * (N - 1), double);
-  ALLOC(h->kappa, B * m * (N - 1), double);
-  ALLOC(h->dV, B * (N - 1), double);
-  ALLOC(h->fx, B * n * n * (N - 1), double);
-  ALLOC(h->fu, B * n * m * (N - 1), double);
-  const bool host_rec = B <= 4;              // (host.hpp: host_records)
-  const bool host_in = host_rec && !large && !batch_minor;   // ... and the inputs x0, u_guess (wave-per-problem kernels: the boundary's layout)
-  if (!host_in) {
-    ALLOC(h->x0, B * n, double);
-    ALLOC(h->u_guess, B * m * (N - 1), double);
-  }
-  ALLOC(h->cost_ring, B * mi_ilqr::kStatsRing, double);
-  if (host_rec) {
-    auto up = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    const size_t s_hist = up(B * (size_t)h->d.hist_cap * 4 * 8), s_prof = up(B * 4 * 8), s_ring = up(B * mi_ilqr::kStatsRing * 4);
-    const size_t s_x0 = host_in ? up(B * n * 8) : 0, s_ug = host_in ? up(B * m * (N - 1) * 8) : 0;
-    h->host_records_bytes = 2 * s_hist + s_prof + 2 * s_ring + s_x0 + s_ug;
-    void* dv = nullptr;
-    if (hipHostMalloc(reinterpret_cast<void**>(&h->host_records), h->host_records_bytes, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer(&dv, h->host_records, 0) != hipSuccess) { mi_ilqr_destroy(h); return MI_ILQR_E_HIP; }
-    std::memset(h->host_records, 0, h->host_records_bytes);
-    h->host_records_dev = static_cast<char*>(dv);
-    char* q = h->host_records_dev;
-    h->hist = reinterpret_cast<double*>(q); q += s_hist;
-    h->iter_cyc = reinterpret_cast<double*>(q); q += s_hist;
-    h->prof = reinterpret_cast<long long*>(q); q += s_prof;
-    h->iters_ring = reinterpret_cast<int32_t*>(q); q += s_ring;
-    h->status_ring = reinterpret_cast<int32_t*>(q); q += s_ring;
-    if (host_in) { h->x0 = reinterpret_cast<double*>(q); q += s_x0; h->u_guess = reinterpret_cast<double*>(q); h->host_inputs = true; }
-  } else {
-    ALLOC(h->hist, B * (size_t)h->d.hist_cap * 4, double);
-    ALLOC(h->iter_cyc, B * (size_t)h->d.hist_cap * 4, double);
-  }
-  ALLOC(h->x_trial, B * n * N, double);
-  ALLOC(h->u_trial, B * m * (N - 1), double);
-  ALLOC(h->trial_cost, B * 2, double);
-  ALLOC(h->stage_in, B, double);
-  ALLOC(h->costmat, 2 * n * n + m * m + n, double);
-  if (!host_rec) {
-    ALLOC(h->iters_ring, B * mi_ilqr::kStatsRing, int32_t);
-    ALLOC(h->status_ring, B * mi_ilqr::kStatsRing, int32_t);
-    ALLOC(h->prof, B * 4, long long);
-  }
-  ALLOC(h->ls_ring, B * mi_ilqr::kStatsRing, int32_t);
-  ALLOC(h->kp_count, B, int32_t);
-  ALLOC(h->kp_list, B * (N - 1), int32_t);
-  ALLOC(h->done_counter, 1, int32_t);
-  if (large) ALLOC(h->cluster_sync, B * kSyncWords, unsigned long long);
-  if (lxu_hbm) ALLOC(h->lxu, B * (N - 1) * (n + m), double);
-  if (large && n <= 32) {
-    // mid-size kernels: four line-search candidates per pass - an optimization, so a batch too large for three more
-    // trial buffers simply searches one candidate at a time (make_args: spec_policy = 0 without them)
-    // (batches small enough for clusters: 31 slots - the candidates 1 .. 31 of a first pass that the leader and up to seven helper
-    //  workgroups roll out together, ilqr_large.hpp: candidate groups)
-    // ... as many as the cluster size make_args will pick asks for (cluster_size): 4 g - 1 (15 at B = 64 on 256 CUs), 3 when the
-    // launch will not be clustered - plugin models unless MI_ILQR_CLUSTER forces it, batches beyond 64, fewer than two CUs per
-    // problem.  (Round 5 allocated 31 for every batch up to 64: 1 GB of HBM for nothing on an n = 32, N = 2000 plugin.)
-    const int g = cluster_size(h);
-    h->spec_slots = g > 1 ? 4 * g - 1 : 3;
-    for (;;) {
-      const size_t xb = (size_t)h->spec_slots * B * n * N * sizeof(double), ub = (size_t)h->spec_slots * B * m * (N - 1) * sizeof(double);
-      if (hipMalloc(reinterpret_cast<void**>(&h->x_spec), xb) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&h->u_spec), ub) == hipSuccess) break;
-      (void)hipGetLastError();
-      if (h->x_spec) (void)hipFree(h->x_spec);
-      h->x_spec = nullptr; h->u_spec = nullptr;
-      if (h->spec_slots == 3) { h->spec_slots = 0; break; }
-      h->spec_slots = 3;
-    }
-  }
-  if (batch_minor && !(desc->keypoint_method == MI_KP_SET_INTERVAL && desc->minN == 1)) ALLOC(h->bm_scratch, B * 6 * (N - 1), int32_t);
-#undef ALLOC
-  if (batch_minor && desc->keypoint_method == MI_KP_SET_INTERVAL && desc->minN == 1) {
-    // the KP = false lane-per-problem kernels never write the key-point list: every step is a key-point (ilqr.py:417-432), the
-    // same list for every problem and every linearization - stored once here
-    std::vector<int32_t> kl(B * (N - 1));
-    for (size_t i = 0; i < kl.size(); ++i) kl[i] = (int32_t)(i % (N - 1));
-    if (hipMemcpy(h->kp_list, kl.data(), kl.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { mi_ilqr_destroy(h); return MI_ILQR_E_HIP; }
-  }
-  // defaults Q=I, R=I, Qf=I, x_nom=0 (ilqr.py:61-67)
-  {
-    std::vector<double> cm(2 * n * n + m * m + n, 0.0);
-    for (size_t i = 0; i < n; ++i) { cm[i * n + i] = 1.0; cm[n * n + m * m + i * n + i] = 1.0; }
-    for (size_t i = 0; i < m; ++i) cm[n * n + i * m + i] = 1.0;
-    if (hipMemcpy(h->costmat, cm.data(), cm.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { mi_ilqr_destroy(h); return MI_ILQR_E_HIP; }
-    h->h_costmat = cm;
-    h->costmat_synced = true;
-  }
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-    mi_ilqr_destroy(h);
-    return MI_ILQR_E_HIP;
-  }
-  for (int i = 0; i < mi_ilqr::kStatsRing; ++i) {
-    if (hipEventCreate(&h->ring_ev0[i]) != hipSuccess || hipEventCreate(&h->ring_ev1[i]) != hipSuccess) {
-      mi_ilqr_destroy(h);
-      return MI_ILQR_E_HIP;
-    }
-  }
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->h_ring), sizeof(DevStats) * mi_ilqr::kStatsRing, hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_ring), h->h_ring, 0) != hipSuccess) {
-    mi_ilqr_destroy(h);
-    return MI_ILQR_E_HIP;
-  }
-  std::memset(h->h_ring, 0, sizeof(DevStats) * mi_ilqr::kStatsRing);
-  select_stats_slot(h, 0);
-  h->cold = true;
-  h->u_pending = false;
+  h->targets.width = h->target_steps.width = h->lane_targets.width = h->n;
+  h->params.width = model.n_params;
+  h->costs.width = cost_len(h);
+  h->params.batch_minor_copy = h->costs.batch_minor_copy = batch_minor;   // (what the lane kernels read batch-minor: KArgs::param_cols, cost_cols)
+  const int rc = create_resources(h, lxu_hbm);
+  if (rc != MI_ILQR_OK) { mi_ilqr_destroy(h); return rc; }
   *out = h;
   return MI_ILQR_OK;
 }
@@ -872,26 +966,14 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
   if (!h) return;
   (void)hipSetDevice(h->d.device_id);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->host_records) {                               // (the five record buffers point into this block)
-    (void)hipHostFree(h->host_records);
-    h->hist = h->iter_cyc = nullptr; h->prof = nullptr; h->iters_ring = h->status_ring = nullptr;
-    if (h->host_inputs) h->x0 = h->u_guess = nullptr;
-  }
-  void* ptrs[] = {h->x_bar, h->u_bar, h->K, h->kappa, h->dV, h->fx, h->fu, h->x0, h->u_guess, h->cost_ring, h->hist, h->iter_cyc,
-                  h->x_trial, h->u_trial, h->trial_cost, h->stage_in, h->costmat, h->iters_ring, h->status_ring, h->ls_ring,
-                  h->kp_count, h->kp_list, h->prof, h->done_counter, h->cluster_sync, h->bm_scratch, h->x_spec, h->u_spec, h->lxu,
-                  h->ulim, h->s2, h->x_nom_rows, h->target_steps, h->param_rows, h->param_cols, h->cost_rows, h->cost_cols,
-                  h->lane_x_nom_rows};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
+  for (void* p : h->owned) (void)hipFree(p);
+  if (h->host_records) (void)hipHostFree(h->host_records);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
-  if (h->mpc_log) (void)hipFree(h->mpc_log);
-  if (h->scratch) (void)hipFree(h->scratch);
+  if (h->pin_in) (void)hipHostFree(h->pin_in);
   for (int i = 0; i < mi_ilqr::kStatsRing; ++i) {
     if (h->ring_ev0[i]) (void)hipEventDestroy(h->ring_ev0[i]);
     if (h->ring_ev1[i]) (void)hipEventDestroy(h->ring_ev1[i]);
   }
-  if (h->u_one) (void)hipFree(h->u_one);
-  if (h->pin_in) (void)hipHostFree(h->pin_in);
   if (h->pin_ev) (void)hipEventDestroy(h->pin_ev);
   if (h->policy_ev0) (void)hipEventDestroy(h->policy_ev0);
   if (h->policy_ev1) (void)hipEventDestroy(h->policy_ev1);
@@ -923,46 +1005,30 @@ static bool is_sym_psd(const double* A, int k, bool strict) {
   return true;
 }
 
-// Per-problem targets (MI_F_X_NOM / MI_F_TARGET_STEP).  The host mirrors h_x_nom_rows / h_target_steps are the truth that
-// mi_ilqr_get returns; the device copies follow them on the handle's stream.
+// Per-problem targets (MI_F_X_NOM / MI_F_TARGET_STEP): the two arrays enter and leave their mode together.
 static void drop_per_problem_targets(mi_ilqr* h) {
-  h->per_problem_targets = false;
+  store_drop(h->targets);
+  store_drop(h->target_steps);
   h->target_steps_moving = false;
-  h->h_x_nom_rows.clear();
-  h->h_target_steps.clear();
 }
 
-static const double* shared_x_nom(const mi_ilqr* h) { return h->h_costmat.data() + 2 * (size_t)h->n * h->n + (size_t)h->m * h->m; }
-
-// Switch to per-problem targets: rows = the shared x_nom broadcast, steps = zeros (both then overwritten by the caller's field).
-static int enter_per_problem_targets(mi_ilqr* h) {
-  if (h->per_problem_targets) return MI_ILQR_OK;
-  const size_t B = h->B, n = h->n;
-  if (!h->x_nom_rows) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->x_nom_rows), B * n * 8));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->target_steps), B * n * 8));
-  }
-  h->h_x_nom_rows.resize(B * n);
-  for (size_t b = 0; b < B; ++b) std::memcpy(h->h_x_nom_rows.data() + b * n, shared_x_nom(h), n * 8);
-  h->h_target_steps.assign(B * n, 0.0);
-  int rc = stage_h2d(h, h->x_nom_rows, h->h_x_nom_rows.data(), B * n * 8);
-  if (rc == MI_ILQR_OK) rc = stage_h2d(h, h->target_steps, h->h_target_steps.data(), B * n * 8);
-  if (rc != MI_ILQR_OK) { drop_per_problem_targets(h); return rc; }
-  h->per_problem_targets = true;
-  h->target_steps_moving = false;
-  return MI_ILQR_OK;
+static int upload_target_rows(mi_ilqr* h, RowStore& s, const double* src) {
+  const int rc = store_upload(h, s, src);
+  if (rc != MI_ILQR_OK) drop_per_problem_targets(h);
+  return rc;
 }
 
 static int set_target_field(mi_ilqr* h, int which, const double* src, size_t bytes) {
   const size_t cnt = (size_t)h->B * h->n;
   if (bytes != cnt * 8) return MI_ILQR_E_BAD_SHAPE;
   for (size_t i = 0; i < cnt; ++i) if (src[i] != src[i]) return MI_ILQR_E_BAD_ARG;
-  HIPCHK(hipSetDevice(h->d.device_id));
-  int rc = enter_per_problem_targets(h);
-  if (rc != MI_ILQR_OK) return rc;
-  std::vector<double>& mirror = which == MI_F_X_NOM ? h->h_x_nom_rows : h->h_target_steps;
-  std::memcpy(mirror.data(), src, bytes);
-  if ((rc = stage_h2d(h, which == MI_F_X_NOM ? h->x_nom_rows : h->target_steps, mirror.data(), bytes)) != MI_ILQR_OK) return rc;
+  int rc;
+  if (!h->targets.synced) {     // entering the mode: the field the caller does not set starts from the shared x_nom broadcast / zero steps
+    if (which == MI_F_X_NOM) rc = store_upload(h, h->target_steps, std::vector<double>(cnt, 0.0).data());
+    else rc = store_upload_broadcast(h, h->targets, shared_x_nom(h));
+    if (rc != MI_ILQR_OK) { drop_per_problem_targets(h); return rc; }
+  }
+  if ((rc = upload_target_rows(h, which == MI_F_X_NOM ? h->targets : h->target_steps, src)) != MI_ILQR_OK) return rc;
   if (which == MI_F_TARGET_STEP) {
     h->target_steps_moving = false;
     for (size_t i = 0; i < cnt; ++i) if (src[i] != 0.0) h->target_steps_moving = true;
@@ -970,71 +1036,24 @@ static int set_target_field(mi_ilqr* h, int which, const double* src, size_t byt
   return MI_ILQR_OK;
 }
 
-static int get_target_field(mi_ilqr* h, int which, double* dst, size_t bytes) {
-  const size_t B = h->B, n = h->n;
-  if (bytes != B * n * 8) return MI_ILQR_E_BAD_SHAPE;
-  if (h->per_problem_targets) {
-    std::memcpy(dst, (which == MI_F_X_NOM ? h->h_x_nom_rows : h->h_target_steps).data(), bytes);
-  } else if (which == MI_F_X_NOM) {
-    for (size_t b = 0; b < B; ++b) std::memcpy(dst + b * n, shared_x_nom(h), n * 8);
-  } else {
-    std::memset(dst, 0, bytes);
-  }
-  return MI_ILQR_OK;
-}
-
 // mpc_run with per-problem targets: every row moves by its own step, once per re-solve - fp64 repeated addition, what the kernels do
 static int advance_per_problem_targets(mi_ilqr* h, int32_t times) {
-  const size_t cnt = (size_t)h->B * h->n;
+  std::vector<double> rows = h->targets.mirror;
   for (int32_t r = 0; r < times; ++r)
-    for (size_t i = 0; i < cnt; ++i) h->h_x_nom_rows[i] += h->h_target_steps[i];
-  return stage_h2d(h, h->x_nom_rows, h->h_x_nom_rows.data(), cnt * 8);
+    for (size_t i = 0; i < rows.size(); ++i) rows[i] += h->target_steps.mirror[i];
+  return upload_target_rows(h, h->targets, rows.data());
 }
 
-// Per-problem model parameters (MI_F_MODEL_PARAMS): (B, n_params) rows, problem b's plant in row b.  The host mirror h_param_rows
-// is what mi_ilqr_get returns; the device copies - the rows, and the same values batch-minor for the lane-per-problem kernels -
-// follow it on the handle's stream.  src == NULL with bytes == 0: back to the descriptor's parameters.
+// Per-problem model parameters (MI_F_MODEL_PARAMS): (B, n_params) rows, problem b's plant in row b.  src == NULL with bytes == 0:
+// back to the descriptor's parameters - the kernels read KArgs::params, as on a handle that never left them.
 static int set_model_params(mi_ilqr* h, const double* src, size_t bytes) {
-  const size_t B = h->B, np = model_of(h->d.model_id)->p.n_params;
-  if (np == 0) return MI_ILQR_E_UNSUPPORTED;
-  if (!src && bytes == 0) {                  // shared mode again: the kernels read KArgs::params, as on a handle that never left it
-    h->per_problem_params = false;
-    h->h_param_rows.clear();
-    return MI_ILQR_OK;
-  }
-  if (bytes != B * np * 8) return MI_ILQR_E_BAD_SHAPE;
+  const size_t cnt = (size_t)h->B * h->params.width;
+  if (cnt == 0) return MI_ILQR_E_UNSUPPORTED;
+  if (!src && bytes == 0) { store_drop(h->params); return MI_ILQR_OK; }
+  if (bytes != cnt * 8) return MI_ILQR_E_BAD_SHAPE;
   if (!src) return MI_ILQR_E_BAD_ARG;
-  for (size_t i = 0; i < B * np; ++i) if (!std::isfinite(src[i])) return MI_ILQR_E_BAD_ARG;
-  HIPCHK(hipSetDevice(h->d.device_id));
-  if (!h->param_rows) {
-    double *rows = nullptr, *cols = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&rows), bytes));
-    if (hipMalloc(reinterpret_cast<void**>(&cols), bytes) != hipSuccess) { (void)hipFree(rows); return MI_ILQR_E_HIP; }
-    h->param_rows = rows; h->param_cols = cols;
-  }
-  std::vector<double> cols(B * np);
-  for (size_t b = 0; b < B; ++b)
-    for (size_t k = 0; k < np; ++k) cols[k * B + b] = src[b * np + k];
-  // kernels already enqueued (mi_ilqr_solve_async) read the previous rows: stage_h2d copies on the handle's stream, behind them
-  int rc = stage_h2d(h, h->param_rows, src, bytes);
-  if (rc == MI_ILQR_OK) rc = stage_h2d(h, h->param_cols, cols.data(), bytes);
-  if (rc != MI_ILQR_OK) {                    // the device copies are undefined now: the handle falls back to what it can vouch for
-    h->per_problem_params = false;
-    h->h_param_rows.clear();
-    return rc;
-  }
-  h->h_param_rows.assign(src, src + B * np);
-  h->per_problem_params = true;
-  return MI_ILQR_OK;
-}
-
-static int get_model_params(mi_ilqr* h, double* dst, size_t bytes) {
-  const size_t B = h->B, np = model_of(h->d.model_id)->p.n_params;
-  if (np == 0) return MI_ILQR_E_UNSUPPORTED;
-  if (bytes != B * np * 8) return MI_ILQR_E_BAD_SHAPE;
-  if (h->per_problem_params) std::memcpy(dst, h->h_param_rows.data(), bytes);
-  else for (size_t b = 0; b < B; ++b) std::memcpy(dst + b * np, h->d.model_params, np * 8);
-  return MI_ILQR_OK;
+  for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(src[i])) return MI_ILQR_E_BAD_ARG;
+  return store_upload(h, h->params, src);
 }
 
 // The cost class of one set of matrices, cm = Q | R | Qf (mi_ilqr_set_cost and every row of MI_F_COST_MATRICES decide it here):
@@ -1094,23 +1113,21 @@ static int classify_cost(const mi_ilqr* h, double* cm, bool* regular_out, bool* 
 
 // the class the kernels run with: the rows' in per-problem mode, the shared matrices' otherwise
 static void apply_cost_class(mi_ilqr* h) {
-  h->exact_backward = h->per_problem_costs ? h->rows_exact_backward : h->shared_exact_backward;
-  h->cost_asym = h->per_problem_costs ? h->rows_cost_asym : h->shared_cost_asym;
+  h->exact_backward = h->costs.synced ? h->rows_exact_backward : h->shared_exact_backward;
+  h->cost_asym = h->costs.synced ? h->rows_cost_asym : h->shared_cost_asym;
 }
 
 static void drop_per_problem_costs(mi_ilqr* h) {
-  h->per_problem_costs = false;
-  h->cost_rows_synced = false;
-  h->h_cost_rows.clear();
+  store_drop(h->costs);
   apply_cost_class(h);
 }
 
 // Per-problem cost matrices (MI_F_COST_MATRICES): (B, 2 n^2 + m^2) rows, row b = Q_b | R_b | Qf_b.  Every row is classified like
-// mi_ilqr_set_cost classifies the shared matrices, and the handle runs the most general form a row needs.  The host mirror
-// h_cost_rows - the rows as the kernels get them, i.e. after the n >= 33 round-off symmetrisation - is what mi_ilqr_get returns; the
-// device copies follow it on the handle's stream.  src == NULL with bytes == 0: back to the shared matrices.
+// mi_ilqr_set_cost classifies the shared matrices, and the handle runs the most general form a row needs.  What is stored (and
+// mi_ilqr_get returns) is the rows as the kernels get them, i.e. after the n >= 33 round-off symmetrisation.  src == NULL with
+// bytes == 0: back to the shared matrices.
 static int set_cost_rows(mi_ilqr* h, const double* src, size_t bytes) {
-  const size_t B = h->B, n = h->n, m = h->m, len = 2 * n * n + m * m;
+  const size_t B = h->B, len = cost_len(h);
   if (!src && bytes == 0) { drop_per_problem_costs(h); return MI_ILQR_OK; }
   if (bytes != B * len * 8) return MI_ILQR_E_BAD_SHAPE;
   if (!src) return MI_ILQR_E_BAD_ARG;
@@ -1124,36 +1141,11 @@ static int set_cost_rows(mi_ilqr* h, const double* src, size_t bytes) {
     regular_all = regular_all && regular;
     asym_any = asym_any || asym;
   }
-  // (the rows' class is committed with the rows, below: a call that fails on the way changes nothing)
-  auto commit_class = [&] { h->rows_exact_backward = regular_all ? 0 : 1; h->rows_cost_asym = asym_any ? 1 : 0; apply_cost_class(h); };
-  // nothing to send when the caller repeats the rows it set before (Solve() pushes them on every call)
-  if (h->per_problem_costs && h->cost_rows_synced && std::memcmp(rows.data(), h->h_cost_rows.data(), bytes) == 0) { commit_class(); return MI_ILQR_OK; }
-  HIPCHK(hipSetDevice(h->d.device_id));
-  if (!h->cost_rows) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->cost_rows), bytes));
-  if (h->batch_minor && !h->cost_cols) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->cost_cols), bytes));
-  // kernels already enqueued (mi_ilqr_solve_async) read the previous rows: stage_h2d copies on the handle's stream, behind them
-  h->cost_rows_synced = false;
-  int rc = stage_h2d(h, h->cost_rows, rows.data(), bytes);
-  if (rc == MI_ILQR_OK && h->batch_minor) {
-    std::vector<double> cols(B * len);
-    for (size_t b = 0; b < B; ++b)
-      for (size_t k = 0; k < len; ++k) cols[k * B + b] = rows[b * len + k];
-    rc = stage_h2d(h, h->cost_cols, cols.data(), bytes);
-  }
-  if (rc != MI_ILQR_OK) { drop_per_problem_costs(h); return rc; }   // the device copies are undefined now: the shared matrices again
-  h->h_cost_rows.swap(rows);
-  h->cost_rows_synced = true;
-  h->per_problem_costs = true;
-  commit_class();
-  return MI_ILQR_OK;
-}
-
-static int get_cost_rows(mi_ilqr* h, double* dst, size_t bytes) {
-  const size_t B = h->B, len = 2 * (size_t)h->n * h->n + (size_t)h->m * h->m;
-  if (bytes != B * len * 8) return MI_ILQR_E_BAD_SHAPE;
-  if (h->per_problem_costs) std::memcpy(dst, h->h_cost_rows.data(), bytes);
-  else for (size_t b = 0; b < B; ++b) std::memcpy(dst + b * len, h->h_costmat.data(), len * 8);
-  return MI_ILQR_OK;
+  // the rows' class is committed with the rows: a call refused above changes nothing, a failed copy leaves the shared matrices' class
+  const int rc = store_upload(h, h->costs, rows.data());
+  if (rc == MI_ILQR_OK) { h->rows_exact_backward = regular_all ? 0 : 1; h->rows_cost_asym = asym_any ? 1 : 0; }
+  apply_cost_class(h);
+  return rc;
 }
 
 int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const double* Qf, const double* x_nom) {
@@ -1166,7 +1158,7 @@ int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const doubl
     if (Q) std::memcpy(cm.data(), Q, n * n * 8);
     if (R) std::memcpy(cm.data() + n * n, R, m * m * 8);
     if (Qf) std::memcpy(cm.data() + n * n + m * m, Qf, n * n * 8);
-    if (x_nom) std::memcpy(cm.data() + 2 * n * n + m * m, x_nom, n * 8);
+    if (x_nom) std::memcpy(cm.data() + cost_len(h), x_nom, n * 8);
     bool regular = true, asym = false;
     if (classify_cost(h, cm.data(), &regular, &asym) != MI_ILQR_OK) {
       std::fprintf(stderr, "mi_ilqr_set_cost: Q, R, Qf must be finite\n");
@@ -1214,12 +1206,13 @@ int mi_ilqr_set_initial(mi_ilqr_t* h, const double* x0, const double* u_guess) {
   if (x0) { const int rc = stage_h2d(h, h->x0, x0, (size_t)h->B * h->n * 8); if (rc != MI_ILQR_OK) return rc; }
   if (u_guess) {
     const size_t cnt = (size_t)h->B * h->m * (h->N - 1);
-    if ((h->large || h->batch_minor) && (h->m > 1 || h->batch_minor)) {
+    int rows = 0, len = 0;
+    if (needs_relayout(h, MI_F_U_BAR, &rows, &len)) {
       int rc = ensure_scratch(h, cnt * 8);
       if (rc != MI_ILQR_OK) return rc;
       HIPCHK(hipStreamSynchronize(h->stream));
       HIPCHK(hipMemcpy(h->scratch, u_guess, cnt * 8, hipMemcpyHostToDevice));
-      if ((rc = relayout(h, h->scratch, h->u_guess, h->m, h->N - 1, true)) != MI_ILQR_OK) return rc;
+      if ((rc = relayout(h, h->scratch, h->u_guess, rows, len, true)) != MI_ILQR_OK) return rc;
       HIPCHK(hipStreamSynchronize(h->stream));
     } else {
       const int rc = stage_h2d(h, h->u_guess, u_guess, cnt * 8);
@@ -1238,13 +1231,12 @@ int mi_ilqr_set_initial_shared(mi_ilqr_t* h, const double* x0, const double* u_g
   if (x0) { const int rc = stage_h2d(h, h->x0, x0, (size_t)h->B * h->n * 8); if (rc != MI_ILQR_OK) return rc; }
   if (u_guess_one) {
     const size_t one = (size_t)h->m * (h->N - 1);
-    if (!h->u_one) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->u_one), one * 8));
-    int rc = stage_h2d(h, h->u_one, u_guess_one, one * 8);
+    int rc = h->u_one ? MI_ILQR_OK : dev_alloc(h, h->u_one, one);
+    if (rc == MI_ILQR_OK) rc = stage_h2d(h, h->u_one, u_guess_one, one * 8);
     if (rc != MI_ILQR_OK) return rc;
-    const int layout = h->batch_minor ? 2 : (h->large ? 1 : 0);
     const size_t total = one * h->B;
     const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(broadcast_u_kernel, dim3(blocks), dim3(256), 0, h->stream, h->u_one, h->u_guess, h->B, h->m, h->N - 1, layout);
+    hipLaunchKernelGGL(broadcast_u_kernel, dim3(blocks), dim3(256), 0, h->stream, h->u_one, h->u_guess, h->B, h->m, h->N - 1, layout_of(h));
     HIPCHK(hipGetLastError());
     h->u_pending = true;
     h->u_zero = false;
@@ -1352,9 +1344,10 @@ int mi_ilqr_set_control_limits(mi_ilqr_t* h, const double* u_min, const double* 
     if (lo != lo || hi != hi || lo > hi) return MI_ILQR_E_BAD_ARG;   // NaN, or an empty box
   }
   HIPCHK(hipSetDevice(h->d.device_id));
-  if (!h->ulim) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->ulim), (size_t)B * 2 * m * 8));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->s2), (size_t)B * 8));
+  if (!h->s2) {
+    int rc = h->ulim ? MI_ILQR_OK : dev_alloc(h, h->ulim, (size_t)B * 2 * m);
+    if (rc == MI_ILQR_OK) rc = dev_alloc(h, h->s2, (size_t)B);
+    if (rc != MI_ILQR_OK) return rc;
     HIPCHK(hipMemsetAsync(h->s2, 0, (size_t)B * 8, h->stream));
   }
   std::vector<double> box((size_t)B * 2 * m);     // (B, 2, m): u_min | u_max, shared bounds broadcast here
@@ -1520,7 +1513,7 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
     const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
     hipLaunchKernelGGL(policy_pack_kernel, dim3(blocks), dim3(256), 0, h->stream, h->cold ? nullptr : h->x_bar, u_src,
                        h->cold ? nullptr : h->K, sc + o_pol, (int)B, (int)n, (int)m, (int)N,
-                       h->batch_minor ? LAYOUT_BM : (h->large ? LAYOUT_TM : LAYOUT_TL));
+                       layout_of(h));
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipMemcpyAsync(sc + o_x0_in, x0, B * Sz * n * 8, hipMemcpyHostToDevice, h->stream));
@@ -1528,14 +1521,19 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
   if (params) {
     HIPCHK(hipMemcpyAsync(sc + o_p_in, params, B * Sz * np * 8, hipMemcpyHostToDevice, h->stream));
     if ((rc = transpose_tiles(h, sc + o_p_in, sc + o_p, S, (int)np, B, 1, Sz * np, 0, np, np * Sz, 0, Sz)) != MI_ILQR_OK) return rc;
-  } else if (np && !h->per_problem_params) {
+  } else if (np && !h->params.synced) {
     if ((rc = stage_h2d(h, sc + o_prow, h->d.model_params, np * 8)) != MI_ILQR_OK) return rc;
   }
   PolicyArgs a{};
   a.policy = sc + o_pol; a.x0 = sc + o_x0; a.params = params ? sc + o_p : nullptr;
-  a.param_rows = h->per_problem_params ? h->param_rows : sc + o_prow; a.param_stride = h->per_problem_params ? np : 0;
-  a.cost = h->per_problem_costs ? h->cost_rows : h->costmat; a.cost_stride = h->per_problem_costs ? 2 * n * n + m * m : 0;
-  a.x_nom = h->per_problem_targets ? h->x_nom_rows : h->costmat + 2 * n * n + m * m; a.x_nom_stride = h->per_problem_targets ? n : 0;
+  // every per-problem array: its device rows with a row's stride, else the one shared row with stride 0
+  auto rows_or = [](const RowStore& s, const double* shared_row, size_t* stride) {
+    *stride = s.synced ? s.width : 0;
+    return s.synced ? s.rows : shared_row;
+  };
+  a.param_rows = rows_or(h->params, sc + o_prow, &a.param_stride);
+  a.cost = rows_or(h->costs, h->costmat, &a.cost_stride);
+  a.x_nom = rows_or(h->targets, h->costmat + cost_len(h), &a.x_nom_stride);
   a.ulim = h->limited ? h->ulim : nullptr;
   a.cost_out = sc + o_cost; a.x_final = sc + o_xf; a.steps = reinterpret_cast<int32_t*>(sc + o_steps);
   a.X = X ? sc + o_X : nullptr; a.U = U ? sc + o_U : nullptr;
@@ -1602,14 +1600,14 @@ __global__ void __launch_bounds__(256) mpc_log_fill_kernel(const double* __restr
 int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, const double* target_step, mi_ilqr_stats* stats) {
   if (!h) return MI_ILQR_E_BAD_ARG;
   if (num_resolves < 1 || replan_steps < 1 || replan_steps >= h->N - 1) return MI_ILQR_E_BAD_ARG;
-  if (h->per_problem_targets && target_step) return MI_ILQR_E_BAD_ARG;   // the steps are the field MI_F_TARGET_STEP then
+  if (h->targets.synced && target_step) return MI_ILQR_E_BAD_ARG;   // the steps are the field MI_F_TARGET_STEP then
   HIPCHK(hipSetDevice(h->d.device_id));
   int rc;
   if (h->mpc_log_resolves < num_resolves) {
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->mpc_log) HIPCHK(hipFree(h->mpc_log));
-    h->mpc_log = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->mpc_log), ((size_t)h->B * num_resolves * (h->n + 2) + h->B) * 8));
+    h->mpc_log_resolves = 0;
+    if ((rc = dev_free(h, h->mpc_log)) != MI_ILQR_OK) return rc;
+    if ((rc = dev_alloc(h, h->mpc_log, (size_t)h->B * num_resolves * (h->n + 2) + h->B)) != MI_ILQR_OK) return rc;
     h->mpc_log_resolves = num_resolves;
   }
   // rows a problem never reaches (it failed in an earlier re-solve: both forms of the loop stop logging it there) read as zeros
@@ -1622,7 +1620,7 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
     std::vector<double> xn(h->n);
     // x_nom from the host mirror: mi_ilqr_set_cost uploads asynchronously on the handle's stream, so a blocking
     // null-stream read of the device copy could still see the previous target
-    if (target_step) std::memcpy(xn.data(), h->h_costmat.data() + 2 * (size_t)h->n * h->n + (size_t)h->m * h->m, h->n * 8);
+    if (target_step) std::memcpy(xn.data(), shared_x_nom(h), h->n * 8);
     mi_ilqr_stats acc; std::memset(&acc, 0, sizeof(acc)); acc.best_cost = INFINITY; acc.best_index = -1;
     for (int r = 0; r < num_resolves; ++r) {
       if ((rc = mi_ilqr_mpc_shift(h, replan_steps)) != MI_ILQR_OK) return rc;
@@ -1630,7 +1628,7 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
         for (int i = 0; i < h->n; ++i) xn[i] += target_step[i];
         if ((rc = mi_ilqr_set_cost(h, nullptr, nullptr, nullptr, xn.data())) != MI_ILQR_OK) return rc;
       }
-      if (h->per_problem_targets && (rc = advance_per_problem_targets(h, 1)) != MI_ILQR_OK) return rc;   // one (B, n) upload
+      if (h->targets.synced && (rc = advance_per_problem_targets(h, 1)) != MI_ILQR_OK) return rc;   // one (B, n) upload
       mi_ilqr_stats st;
       if ((rc = mi_ilqr_solve(h, &st)) != MI_ILQR_OK) return rc;
       hipLaunchKernelGGL(mpc_log_fill_kernel, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, h->x0, h->cost, h->iters, h->status, h->mpc_log,
@@ -1657,17 +1655,17 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
                        h->B, h->d_ring, h->cur_slot, (int)mi_ilqr::kStatsRing);
     HIPCHK(hipGetLastError());
   }
-  if (h->per_problem_targets) {   // the rows the kernel moved, every problem's num_resolves times (a failed problem's included)
+  if (h->targets.synced) {   // the rows the kernel moved, every problem's num_resolves times (a failed problem's included)
     HIPCHK(hipStreamSynchronize(h->stream));
     if ((rc = advance_per_problem_targets(h, num_resolves)) != MI_ILQR_OK) return rc;
   }
   if (target_step) {          // keep the handle's x_nom in step with what the kernel accumulated
     std::vector<double> xn(h->n);
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(xn.data(), h->costmat + 2 * (size_t)h->n * h->n + (size_t)h->m * h->m, h->n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(xn.data(), h->costmat + cost_len(h), h->n * 8, hipMemcpyDeviceToHost));
     for (int i = 0; i < h->n; ++i) xn[i] += num_resolves * target_step[i];
-    HIPCHK(hipMemcpy(h->costmat + 2 * (size_t)h->n * h->n + (size_t)h->m * h->m, xn.data(), h->n * 8, hipMemcpyHostToDevice));
-    std::memcpy(h->h_costmat.data() + 2 * (size_t)h->n * h->n + (size_t)h->m * h->m, xn.data(), h->n * 8);   // (the host mirror too)
+    HIPCHK(hipMemcpy(h->costmat + cost_len(h), xn.data(), h->n * 8, hipMemcpyHostToDevice));
+    std::memcpy(h->h_costmat.data() + cost_len(h), xn.data(), h->n * 8);   // (the host mirror too)
   }
   if (stats) return mi_ilqr_collect_stats(h, stats);
   return mi_ilqr_synchronize(h);
@@ -1684,9 +1682,7 @@ int mi_ilqr_get_mpc_log(mi_ilqr_t* h, double* dst, size_t bytes) {
 
 int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
-  if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return get_target_field(h, which, dst, bytes);
-  if (which == MI_F_MODEL_PARAMS) return get_model_params(h, dst, bytes);
-  if (which == MI_F_COST_MATRICES) return get_cost_rows(h, dst, bytes);
+  if (const RowField r = row_field(h, which); r.store) return store_read(h, *r.store, r.shared_row, dst, bytes);   // (host mirrors)
   if (which == MI_F_POLICY_KERNEL_MS) {        // the rollout kernel of the last mi_ilqr_policy_rollout, from its own events
     if (bytes != 8) return MI_ILQR_E_BAD_SHAPE;
     if (!h->policy_ran) return MI_ILQR_E_BAD_ARG;
@@ -1705,9 +1701,8 @@ int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
   if (h->cold && is_state_field(which)) { std::memset(dst, 0, bytes); return MI_ILQR_OK; }
   if (which == MI_F_U_BAR && h->u_zero && !h->u_pending) { std::memset(dst, 0, bytes); return MI_ILQR_OK; }
   const double* src = (h->u_pending && which == MI_F_U_BAR) ? h->u_guess : static_cast<const double*>(f.ptr);
-  int len = 0;
-  const int rows = (h->large || h->batch_minor) ? traj_rows(h, which, &len) : 0;
-  if (rows > 1 || (h->batch_minor && rows == 1)) {
+  int rows = 0, len = 0;
+  if (needs_relayout(h, which, &rows, &len)) {
     int rc = ensure_scratch(h, bytes);
     if (rc != MI_ILQR_OK) return rc;
     if ((rc = relayout(h, src, h->scratch, rows, len, false)) != MI_ILQR_OK) return rc;
@@ -1721,22 +1716,21 @@ int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
 
 int mi_ilqr_get_async(mi_ilqr_t* h, int which, void* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
-  if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) {      // (host mirrors: the copy is done when the call returns)
-    HIPCHK(hipSetDevice(h->d.device_id));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return get_target_field(h, which, static_cast<double*>(dst), bytes);
+  if (const RowField r = row_field(h, which); r.store) {       // (host mirrors: the copy is done when the call returns)
+    if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) {
+      HIPCHK(hipSetDevice(h->d.device_id));
+      HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return store_read(h, *r.store, r.shared_row, static_cast<double*>(dst), bytes);
   }
-  if (which == MI_F_MODEL_PARAMS) return get_model_params(h, static_cast<double*>(dst), bytes);   // (a host mirror as well)
-  if (which == MI_F_COST_MATRICES) return get_cost_rows(h, static_cast<double*>(dst), bytes);
   Field f = field_of(h, which);
   if (!f.ptr) return MI_ILQR_E_BAD_ARG;
   if (bytes != f.bytes && !prefix_ok(which, bytes, f.bytes)) return MI_ILQR_E_BAD_SHAPE;
   HIPCHK(hipSetDevice(h->d.device_id));
   if (!f.is_int) {
-    int len = 0;
-    const int rows = (h->large || h->batch_minor) ? traj_rows(h, which, &len) : 0;
+    int rows = 0, len = 0;
     // fields that need a layout conversion (or are known-zero) take the blocking path
-    if (rows > 1 || (h->batch_minor && rows == 1) || (h->cold && is_state_field(which)) ||
+    if (needs_relayout(h, which, &rows, &len) || (h->cold && is_state_field(which)) ||
         (which == MI_F_U_BAR && h->u_zero && !h->u_pending))
       return mi_ilqr_get(h, which, static_cast<double*>(dst), bytes);
   }
@@ -1776,9 +1770,8 @@ int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
   HIPCHK(hipSetDevice(h->d.device_id));
   if (is_state_field(which)) { int rc = materialize_zero_state(h); if (rc != MI_ILQR_OK) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
-  int len = 0;
-  const int rows = (h->large || h->batch_minor) ? traj_rows(h, which, &len) : 0;
-  if (rows > 1 || (h->batch_minor && rows == 1)) {
+  int rows = 0, len = 0;
+  if (needs_relayout(h, which, &rows, &len)) {
     int rc = ensure_scratch(h, bytes);
     if (rc != MI_ILQR_OK) return rc;
     HIPCHK(hipMemcpy(h->scratch, src, bytes, hipMemcpyHostToDevice));
@@ -1793,22 +1786,10 @@ int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
 
 int mi_ilqr_device_ptr(mi_ilqr_t* h, int which, void** ptr, size_t* bytes) {
   if (!h || !ptr) return MI_ILQR_E_BAD_ARG;
-  if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) {      // per-problem mode only: the (B, n) device copies
-    if (!h->per_problem_targets) return MI_ILQR_E_BAD_ARG;
-    *ptr = which == MI_F_X_NOM ? h->x_nom_rows : h->target_steps;
-    if (bytes) *bytes = (size_t)h->B * h->n * 8;
-    return MI_ILQR_OK;
-  }
-  if (which == MI_F_MODEL_PARAMS) {                            // per-problem mode only: the (B, n_params) device rows
-    if (!h->per_problem_params) return MI_ILQR_E_BAD_ARG;
-    *ptr = h->param_rows;
-    if (bytes) *bytes = h->h_param_rows.size() * 8;
-    return MI_ILQR_OK;
-  }
-  if (which == MI_F_COST_MATRICES) {                           // per-problem mode only: the (B, 2 n^2 + m^2) device rows
-    if (!h->per_problem_costs) return MI_ILQR_E_BAD_ARG;
-    *ptr = h->cost_rows;
-    if (bytes) *bytes = h->h_cost_rows.size() * 8;
+  if (const RowStore* s = row_field(h, which).store) {         // per-problem mode only: the (B, width) device rows
+    if (!s->synced) return MI_ILQR_E_BAD_ARG;
+    *ptr = s->rows;
+    if (bytes) *bytes = s->mirror.size() * 8;
     return MI_ILQR_OK;
   }
   Field f = field_of(h, which);

@@ -661,7 +661,7 @@ class BatchedIterativeLQR:
     # ------------------------------------------------------------- Monte-Carlo rollouts of the policy
     def RolloutPolicy(self, x0, params=None, trajectories=False):
         """Roll out S samples per problem under the policy the solver holds - u = u_bar - K (x - x_bar), the reason SaveSolution
-        stores K (ilqr.py:712-733) - one GPU lane per sample, in one call (include/mi_ilqr_policy.h: mi_ilqr_policy_rollout).
+        stores K (ilqr.py:712-733) - one GPU lane per sample, in one call (include/mi_ilqr.h: mi_ilqr_policy_rollout).
         x0: (B, S, n), or (S, n) for every problem.  params: None - each problem's own plant - or (B, S, n_params) / (S, n_params),
         a plant per sample.  Costs, targets and control limits are the solver's, per-problem where set.  Returns a PolicyRollout:
         cost (B, S) - +inf for a sample that ended at an infeasible or non-finite step -, x_final (B, S, n), steps (B, S) and, with

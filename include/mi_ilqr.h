@@ -124,7 +124,7 @@ enum {
   MI_F_TARGET_STEP = 15,/* (B,n) per-problem target_step_b of mi_ilqr_mpc_run                                             */
   MI_F_MODEL_PARAMS = 16,/* (B,n_params) per-problem model parameters: problem b's plant ("Per-problem model parameters" below) */
   MI_F_COST_MATRICES = 17,/* (B,2*n*n+m*m) per-problem cost matrices, row b = Q_b | R_b | Qf_b ("Per-problem cost matrices" below) */
-  MI_F_POLICY_KERNEL_MS = 18,/* (1,) read-only: milliseconds of the rollout kernel of the last policy rollout, from its own HIP events (mi_ilqr_policy.h) */
+  MI_F_POLICY_KERNEL_MS = 18,/* (1,) read-only: milliseconds of the rollout kernel of the last policy rollout, from its own HIP events (mi_ilqr_policy_rollout) */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
@@ -485,9 +485,32 @@ double mi_ilqr_bytes_per_iteration(int32_t n, int32_t m, int32_t N, int32_t ls);
 /* LDS bytes one problem occupies in the wave-per-problem kernels (0 if unsupported). */
 size_t mi_ilqr_lds_bytes(const mi_ilqr_desc* desc);
 
+/* Monte-Carlo rollouts of the feedback policy the handle holds (x_bar, u_bar, K - after a solve, mpc_run or mi_ilqr_set; the reference
+ * stores K for exactly this, ilqr.py:712-733): S samples per problem, one GPU lane per sample, in ONE call.  For problem b, sample s,
+ * x_0 = x0[b,s], t = 0 .. N-2:
+ *     u_t = u_bar[b,:,t] - K[b,:,:,t] (x_t - x_bar[b,:,t])      (ilqr.py:313 with eps = 0; clamped to problem b's box on a handle
+ *                                                                 with control limits set)
+ *     x_{t+1} = f(x_t, u_t; params[b,s], dt)
+ *     L += (x_t - x_nom_b)' Q_b (x_t - x_nom_b) + u_t' R_b u_t  (ilqr.py:325),   L += the Qf_b term at x_{N-1}  (ilqr.py:327)
+ * with the handle's cost matrices and targets (per-problem where set).  All pointers are HOST arrays:
+ *   x0      (B,S,n)       in   initial states
+ *   params  (B,S,n_params) in  or NULL: every sample of problem b runs on problem b's own parameters (MI_F_MODEL_PARAMS row, else
+ *                              the descriptor's)
+ *   cost    (B,S)         out  +inf for a sample that ended early
+ *   x_final (B,S,n)       out  or NULL: the last state the sample held
+ *   steps   (B,S) int32   out  or NULL: steps completed, N-1 for a full rollout
+ *   X       (B,S,n,N)     out  or NULL;   U (B,S,m,N-1) out or NULL: the trajectories, NaN in the columns a sample did not reach
+ * A sample ENDS at a step the model declares infeasible (MI_MODEL_PLANAR_QUAD, MI_MODEL_QUAD3D: ilqr.py:315-323) or whose result is
+ * not finite, and before its first step when its x0 is not finite - that is data, not an error: steps then says how far it came
+ * (X holds steps + 1 columns, U steps), x_final is the state it stopped in, and the other samples are unaffected.
+ * The handle is only READ: solver state, x0, warm start, statistics, events and MI_F_* results stay what they were, a solve after
+ * the call is bitwise the solve without it.  Runs on the handle's stream with one synchronization; staging memory is the handle's
+ * grow-only scratch.  Errors: S < 1, NULL x0 or cost MI_ILQR_E_BAD_ARG; params for a model with n_params == 0
+ * MI_ILQR_E_UNSUPPORTED; a NaN or an infinity in params MI_ILQR_E_BAD_ARG.  Every model and kernel family (additive in ABI 10). */
+int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const double* params, double* cost, double* x_final,
+                           int32_t* steps, double* X, double* U);
+
 #ifdef __cplusplus
 }
 #endif
-/* the policy rollouts: declared in a companion header for now (a workaround, explained there) */
-#include "mi_ilqr_policy.h"
 #endif /* MI_ILQR_H */

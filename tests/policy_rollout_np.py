@@ -1,4 +1,4 @@
-"""NumPy statement of mi_ilqr_policy_rollout (include/mi_ilqr_policy.h): one sample rolled out under a time-varying feedback policy.
+"""NumPy statement of mi_ilqr_policy_rollout (include/mi_ilqr.h): one sample rolled out under a time-varying feedback policy.
 
     u_t = u_bar[:, t] - eps kappa[:, t] - K[:, :, t] (x_t - x_bar[:, t])           ilqr.py:313 (the device entry has eps = 0)
     u_t = clip(u_t, u_min, u_max)                                                  control-limited handles only

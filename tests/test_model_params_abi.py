@@ -10,8 +10,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mi_ilqr.h")
 
-# the entry points of ABI 10 as the per-problem targets left them: this selector adds none
-ABI10_ENTRY_POINTS = 47
+# the entry points of ABI 10: the 47 the per-problem targets left (this selector adds none) and mi_ilqr_policy_rollout
+ABI10_ENTRY_POINTS = 48
 
 
 def _header():

@@ -1,6 +1,5 @@
-"""mi_ilqr_policy_rollout in the C ABI and the Python classes: include/mi_ilqr_policy.h - the companion header include/mi_ilqr.h
-pulls in at its end - declares it, the library exports it, the ctypes binding
-has its prototype, the ABI version stays 10, and RolloutPolicy decides shapes and non-finite parameters on the host.  CPU only."""
+"""mi_ilqr_policy_rollout in the C ABI and the Python classes: include/mi_ilqr.h declares it, the library exports it, the ctypes
+binding lists it in EXPORTS and has its prototype, the ABI version stays 10, and RolloutPolicy decides shapes and non-finite parameters on the host.  CPU only."""
 import os
 import re
 
@@ -9,24 +8,22 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mi_ilqr.h")
-POLICY_HEADER = os.path.join(ROOT, "include", "mi_ilqr_policy.h")
 
 
-def _header(path=HEADER):
-    with open(path) as f:
+def _header():
+    with open(HEADER) as f:
         return f.read()
 
 
 def test_the_symbol_is_declared_and_exported():
     from drake_ddp_amd import _capi
-    src = _header(POLICY_HEADER)
-    assert re.search(r'^#include "mi_ilqr_policy.h"', _header(), re.M)          # a host that includes mi_ilqr.h has the entry
+    src = _header()
     m = re.search(r"^int mi_ilqr_policy_rollout\(([^;]*)\);", src, re.M)
-    assert m, "include/mi_ilqr_policy.h does not declare mi_ilqr_policy_rollout"
+    assert m, "include/mi_ilqr.h does not declare mi_ilqr_policy_rollout"
     args = [a.strip() for a in " ".join(m.group(1).split()).split(",")]
     assert args == ["mi_ilqr_t* h", "int32_t S", "const double* x0", "const double* params", "double* cost", "double* x_final",
                     "int32_t* steps", "double* X", "double* U"]
-    assert _capi.POLICY_EXPORTS == ["mi_ilqr_policy_rollout"]
+    assert _capi.EXPORTS.count("mi_ilqr_policy_rollout") == 1 and not hasattr(_capi, "POLICY_EXPORTS")
     lib = _capi.load()
     assert hasattr(lib, "mi_ilqr_policy_rollout")
     assert len(lib.mi_ilqr_policy_rollout.argtypes) == 9
@@ -42,7 +39,7 @@ def test_the_abi_version_stays_10():
 
 
 def test_the_header_documents_the_conventions():
-    src = " ".join(re.sub(r"\n\s*\*", " ", _header(POLICY_HEADER)).split())
+    src = " ".join(re.sub(r"\n\s*\*", " ", _header()).split())
     for phrase in ("one GPU lane per sample", "+inf for a sample that ended early", "steps completed, N-1 for a full rollout",
                    "the last state the sample held", "The handle is only READ", "params for a model with n_params == 0 MI_ILQR_E_UNSUPPORTED",
                    "a NaN or an infinity in params MI_ILQR_E_BAD_ARG", "S < 1, NULL x0 or cost MI_ILQR_E_BAD_ARG"):
