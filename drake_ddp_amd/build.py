@@ -5,11 +5,13 @@
 One translation unit per model's kernels (csrc/k_<model>.hip) plus the host side of the C ABI
 (csrc/mi_ilqr.hip), compiled in parallel and linked into drake_ddp_amd/lib/libmi_ilqr.so (git-ignored,
 but it travels to the GPU box with the gpurun snapshot).  hipcc cross-compiles without a GPU.
-Objects are cached in drake_ddp_amd/lib/obj and rebuilt when their source, any header or the flags change.
+Objects are cached in drake_ddp_amd/lib/obj, each beside the dependency file the compiler wrote for it (<obj>.d), and rebuilt
+when their source, a file it includes or the flags change.
 """
 import concurrent.futures
 import hashlib
 import os
+import re
 import subprocess
 import sys
 
@@ -41,11 +43,25 @@ def _obj(src, tag):
     return os.path.join(OBJDIR, os.path.basename(src)[:-4] + tag + ".o")
 
 
+def _deps(obj):
+    """The files `obj` was compiled from, out of the compiler's dependency file (-MD -MF obj.d), or None when there is none."""
+    try:
+        with open(obj + ".d") as f:
+            text = f.read()
+    except (OSError, UnicodeDecodeError):
+        return None
+    words = re.split(r"(?<!\\)\s+", text.replace("\\\n", " ").strip())      # (a space inside a path is written "\ ")
+    colon = next((i for i, w in enumerate(words) if w.endswith(":")), None)
+    return None if colon is None else [w.replace("\\ ", " ") for w in words[colon + 1:]]
+
+
 def _stale(obj, src):
-    if not os.path.exists(obj):
+    """An object is rebuilt when its source or a file it includes is newer - or gone - or when it has no dependency file."""
+    deps = _deps(obj)
+    if not os.path.exists(obj) or deps is None:
         return True
     t = os.path.getmtime(obj)
-    return any(os.path.getmtime(d) > t for d in [src] + headers() if os.path.exists(d))
+    return any(not os.path.exists(d) or os.path.getmtime(d) > t for d in [src] + deps)
 
 
 def needs_build():
@@ -56,7 +72,7 @@ def needs_build():
 
 
 def _compile(src, obj, flags, verbose):
-    cmd = [HIPCC] + flags + ["-c", src, "-o", obj]
+    cmd = [HIPCC] + flags + ["-MD", "-MF", obj + ".d", "-c", src, "-o", obj]
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
@@ -105,7 +121,7 @@ def build_asan(verbose=False):
     obj = os.path.join(OBJDIR, "mi_ilqr-asan.o")
     if _stale(obj, host_src):
         cmd = [HIPCC] + [f for f in FLAGS if f != "-O3"] + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address", "-shared-libsan",
-                                                           "-Wno-option-ignored", "-c", host_src, "-o", obj]
+                                                           "-Wno-option-ignored", "-MD", "-MF", obj + ".d", "-c", host_src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../include/mi_ilqr.h"
-#include "ilqr_small.hpp"
+#include "kernel_args.hpp"   // KArgs, KernelMode, DevStats, kMaxStateDim
 
 // library-internal: hidden from the dynamic symbol table (the C ABI is mi_ilqr.h)
 #define MI_INTERNAL __attribute__((visibility("hidden")))

@@ -26,8 +26,10 @@
 #include <stdint.h>
 
 #include "../../include/mi_ilqr.h"
+#include "cost_terms.hpp"    // Consts, stage_cost, terminal_cost, invert_small, box_qp_step
 #include "fastmath.hpp"
-#include "ilqr_small.hpp"   // KArgs, Consts, stage_cost, terminal_cost, invert_small
+#include "kernel_args.hpp"   // KArgs, KernelMode
+#include "model_traits.hpp"
 #include "models.hpp"
 
 namespace mi {

@@ -25,74 +25,17 @@
 
 #include "../../include/mi_ilqr.h"
 #include "fastmath.hpp"
-#include "ilqr_small.hpp"   // KArgs, KernelMode
+#include "kernel_args.hpp"   // KArgs, KernelMode, kSyncWords, ModelParams, x_nom_of, cost_of, target_step_of, param_row_of
 #include "keypoints.hpp"
+#include "lds_layout.hpp"    // kLargeThreads, LLay, the slots of its reduction scratch, int_row, large_lds_bytes
+#include "model_traits.hpp"
 #include "models.hpp"
+#include "wave_ops.hpp"      // stage_lane, row16_sum, row_share
 
 namespace mi {
 
-constexpr int kLargeThreads = 256;
-constexpr int kPdFlag = 8;          // slot of the reduction scratch (LLay::oRed) where a backward pass leaves "a Quu was not positive definite"
-// Control limits (Limited<M> kernels of the mid-size family, mi_ilqr_set_control_limits): further slots of the reduction scratch
-// (block_sum uses 0..3) - S2 = sum_t kappa_t^T Quu_t kappa_t of the last backward pass, and the problem's bounds u_min | u_max,
-// read once per launch.  The LDS layout and large_lds_bytes stay what they are.
-constexpr int kS2Slot = 9, kLimSlot = 16;
-
-// The thread index of a STAGE (a backward pass, a rollout, a linearization): see stage_lane (ilqr_small.hpp).
+// The thread index of a STAGE (a backward pass, a rollout, a linearization): see stage_lane (wave_ops.hpp).
 __device__ __forceinline__ int stage_tid() { return stage_lane(); }
-
-template <int n, int m>
-struct LLay {
-  static constexpr int nm = n + m;
-  // doubles
-  static constexpr int QC = m * (m + 1) / 2;               // packed lower triangle of Quu
-  static constexpr int T16 = 16;                           // MFMA tile edge
-  static constexpr int NP = ((n + 15) / 16) * 16;          // n padded to whole tiles (rows of Vxx)
-  static constexpr int KN = (n + 3) / 4, NK = 4 * KN;      // MFMA k-steps over a contraction of length n, n padded to them
-  // Columns of the augmented matrices F = [fx | fu], T1, H.  COMPACT: u follows x directly and the last column tile
-  // holds the tail of x together with all of u (n = 36, m = 12: three tiles).  SPLIT (that tile would not start inside
-  // x, or n is not a multiple of 4: n = 37): x is padded to whole tiles and u gets a tile of its own - the pad
-  // rows / columns are zero and never stored, so Quu still sits at the corner of the last diagonal tile.
-  // MID (n <= 32: one or two row tiles, any m <= 16 - mid_backward): always split, and always 48 columns - a row stride
-  // of 48 doubles keeps the four rows of a k-step on disjoint banks for the 64-bit reads (32 would put them on the same).
-  static constexpr bool kMid = n <= 32;
-  static constexpr int NMPc = ((nm + 15) / 16) * 16;
-  // (COMPACT only when x's tail and u fill the last tile exactly - (36, 12), (40, 8): with pad columns behind u, Quu would not
-  //  end at the tile's corner, which the solver wave's row mapping relies on; (36, 4), (36, 8), (40, 4) take the split layout)
-  static constexpr bool kSplit = kMid || !(NMPc - 16 <= n && n % 4 == 0 && nm == NMPc);
-  static constexpr int UC = kSplit ? NP : n;               // column of u_0
-  static constexpr int NMP = kMid ? 48 : (kSplit ? NP + ((m + 15) / 16) * 16 : NMPc);
-  static constexpr int TS = NMP + 4;                       // row stride of T1 / H: whole tiles + the Vx/first-order column
-  static constexpr int VS = NK | 1;                        // odd row stride of Vxx: conflict-free column-of-tile reads
-  static constexpr int oQ = 0, oQf = oQ + n * n, oR = oQf + n * n, oXnom = oR + m * m, oQn = oXnom + n,
-                       oQfn = oQn + n, oVxx = oQfn + n, oVx = oVxx + NP * VS, oF = oVx + NK + (NK & 1),
-                       oT1 = oF + NK * NMP, oH = oT1 + NK * TS, oXs = oH + NMP * TS, oUs = oXs + n,
-                       oRed = oUs + m, oXb = oRed + kLargeThreads, oQc = oXb + n + m + ((n + m) & 1),
-                       oQT = oQc + m * m + m + (m & 1), oS = oQT + (kSplit ? 0 : n * n + ((n * n) & 1)),
-                       oEnd = oS + 16 * 17 + 1;                // 16x16 tile, odd row stride
-  static constexpr size_t doubles = oEnd + 8;
-};
-
-// Integer scratch of the key-point code: five arrays of N (or 2 N) ints - and, while every step is a key-point, the home of the
-// cluster hand-shake's state (aux[0..3], the leader's six counters / a helper's last round in `need`): each array is therefore
-// at least kIntRowMin ints long.  (Round 5's last session moved that state from registers into these arrays; with N = 3 aux[3]
-// WAS need[0] - the leader's round counter - and every clustered solve of a three-step horizon ended with MI_STATUS_INTERNAL.  Found
-// in round 6 by running the GPU suite with clusters forced: test_shortest_horizons_vs_c_oracle swallowed the RuntimeError.)
-constexpr int kIntRowMin = 8;
-__host__ __device__ constexpr int int_row(int N) { return N > kIntRowMin ? N : kIntRowMin; }
-template <int n, int m>
-__host__ __device__ constexpr size_t large_lds_bytes(int N) {
-  // fixed block + per-step cost gradients [N][n+m] + integer scratch of the key-point code
-  return (LLay<n, m>::doubles + (size_t)N * (n + m)) * 8 + (size_t)7 * int_row(N) * 4 + 16;
-}
-
-// Horizons whose cost gradients do not fit next to the fixed block any more (N > 148 for (36, 12), > 319 for (27, 7)): the
-// gradients go to HBM (KArgs::lxu) and LDS keeps the fixed block + the key-point scratch - a slower backward step (one L2 read
-// of lx_t | lu_t per step on the wave that forms the first-order column), but no horizon limit short of 160 KB of integers.
-template <int n, int m>
-__host__ __device__ constexpr size_t large_lds_bytes_hbm(int N) {
-  return (size_t)LLay<n, m>::doubles * 8 + (size_t)7 * int_row(N) * 4 + 16;
-}
 
 // Per-problem views of the time-major HBM arrays.
 template <int n, int m>

@@ -25,262 +25,26 @@
 //     (backward_mfma); the rollout is sequential, evaluated wave-uniformly.
 // Time is the fastest LDS axis (the reference's own layout), so
 // HBM<->LDS staging is a linear, fully coalesced copy per array.
+//
+// This file holds the wave-per-problem family only.  What it shares with the other families and the host has its own
+// headers: the kernel arguments (kernel_args.hpp), the LDS records of this family - Lay, WS, ws_bytes, carve - (lds_layout.hpp),
+// the lane and wave primitives (wave_ops.hpp), the cost constants and the m <= 2 dense algebra (cost_terms.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 
 #include "../../include/mi_ilqr.h"
+#include "cost_terms.hpp"    // LimitRegs, Consts, stage_cost, terminal_cost, invert_small, box_qp_step
 #include "fastmath.hpp"
+#include "kernel_args.hpp"   // KArgs, KernelMode, DevStats, ModelParams, x_nom_of, cost_of, target_step_of, param_row_of
 #include "keypoints.hpp"
+#include "lds_layout.hpp"    // Lay, WS, ws_bytes, carve
 #include "model_traits.hpp"
 #include "models.hpp"
+#include "wave_ops.hpp"      // wave_sync, team_barrier, wave_sum, row_share, dpp_f64_or_zero, ...
 
 namespace mi {
-
-enum KernelMode { MODE_SOLVE = 0, MODE_ROLLOUT = 1, MODE_FORWARD = 2, MODE_LINEARIZE = 3, MODE_BACKWARD = 4, MODE_MPC = 5 };
-
-constexpr int kMaxStateDim = 40;   // largest model state (Synth36: 36), for by-value kernel arguments
-
-// Per-solve aggregate over the batch, written into pinned, device-mapped host memory (one small host
-// read after a blocking solve instead of four D2H copies).
-struct DevStats {
-  long long total_iters, total_ls;
-  int n_conv, n_max, n_fail, max_iters_seen, best_index, n_internal, n_not_pd, pad_;
-  double best_cost;
-};
-
-constexpr int kSyncWords = MI_ILQR_CLUSTER_WORDS;      // (= 40) 64-bit handshake words per problem (KArgs::cluster_sync): 8 + the costs of 4 x 7 line-search candidates
-struct KArgs {
-  // persistent per-problem solver state, reference layout with a leading batch axis
-  double *x_bar, *u_bar, *K, *kappa, *dV, *fx, *fu;
-  const double* x0;        // (B,n)
-  const double* u_guess;   // (B,m,N-1) pending SetInitialGuess input (used when u_pending)
-  double* cost;            // (B,)
-  double* hist;            // (B,hist_cap,4)
-  double* iter_cyc;        // (B,hist_cap,4) per-iteration stopwatches: line search, linearization, backward pass, whole iteration (cycles)
-  double *x_trial, *u_trial, *trial_cost;   // stage outputs
-  const double* stage_in;  // (B,) eps (ROLLOUT) or L_last (FORWARD)
-  const double* costmat;   // Q[n*n] R[m*m] Qf[n*n] x_nom[n]
-  int32_t *iters, *status, *ls_trials, *kp_count, *kp_list;
-  long long* prof;         // (B,4) shader-clock cycles: line search, linearization, backward pass, whole solve
-  double params[MI_ILQR_MAX_PARAMS];
-  double dt, delta, beta, gamma, jerk_thr, err_thr, fd_h;
-  int32_t N, B, kp_method, minN, maxN, max_iters, hist_cap;
-  int32_t n_store;    // line-search candidates whose trajectories are kept in LDS (>= 1)
-  int32_t cold;       // 1: persistent state is all-zero, do not read it
-  int32_t u_pending;  // 1: take u_bar from u_guess
-  // MODE_MPC: receding-horizon loop kept on the device (acrobot.py:145-155, mini_cheetah.py:190-201)
-  int32_t mpc_resolves, mpc_replan;
-  double mpc_target_step[kMaxStateDim];   // added to x_nom before every re-solve (mini_cheetah.py:151-156); zeros = fixed target
-  double* mpc_log;             // (B, mpc_resolves, n+2): x0 of the re-solve | cost | iterations
-  int32_t helpers;             // extra wavefronts per problem that share the linearization (0, 1 or 3), see ilqr_small_kernel
-  int32_t seq_backward;        // 0: fastest backward pass; 1: sequential sweep (A/B measurements); 2: the reference's scalar recursion verbatim (asymmetric / indefinite costs)
-  int32_t newton_rollout;      // 1: the eps = 1 trial is rolled out parallel in time (Newton on the trajectory) when it converges
-  // MODE_SOLVE / MODE_MPC of the wave-per-problem kernels: the last workgroup to finish aggregates the
-  // batch statistics itself (no second kernel per solve).  Null: the host launches stats_kernel.
-  DevStats* stats_out;
-  int32_t* done_counter;       // zero between launches
-  // workgroup-per-problem kernels, MODE_SOLVE / MODE_MPC with every step a key-point: `cluster` workgroups per
-  // problem - one leader that runs the solve and cluster-1 helpers that share its linearizations
-  // (ilqr_large.hpp: cluster handshake).  cluster_sync: kSyncWords 64-bit words per problem, zero at launch.
-  // cluster: bits 0-7 workgroups per problem, bits 8-9 their placement (0: consecutive blocks, a cluster spans XCDs; 1, 2: all on
-  // one XCD), bit 10: early linearization (the helpers linearize the line search's first trial while it is being rolled out),
-  // bit 11: candidate groups (mid-size kernels: the helpers roll out line-search candidates 4 .. beside the leader's four).
-  int32_t cluster;
-  unsigned long long* cluster_sync;
-  // wave-per-problem kernels: optional RESULT SINK (mi_ilqr_set_result_sink) - device-visible, page-locked HOST arrays
-  // that receive x_bar (B,n,N), u_bar (B,m,N-1) and the costs (B,) straight from the kernel's write-back, problem by
-  // problem as each one finishes: the copy-out of a batch overlaps the launch's stragglers instead of following it.
-  double *sink_x, *sink_u, *sink_cost;
-  // lane-per-problem kernels with key-points (ilqr_batch.hpp, KP = true): 6 (N-1) x B ints, batch-minor - the lanes' key-point
-  // lists, "derivative evaluated" flags and the two bin buffers of the iterative-error bisection
-  int32_t* bm_scratch;
-  // mid-size workgroup-per-problem kernels (ilqr_large.hpp: mid_rollout4): trial trajectories of the line-search candidates
-  // rolled out beside the first, [3][B][N][n] and [3][B][N-1][m]
-  double *x_spec, *u_spec;
-  int spec_policy;
-  // workgroup-per-problem kernels, long horizons: the cost gradients [B][N-1][n+m] in HBM instead of LDS (ilqr_large.hpp)
-  double* lxu;
-  int pd_continue;                // mi_ilqr_desc.on_indefinite
-  int cost_asym;                  // workgroup-per-problem kernels, n <= 32: Q, R or Qf is not symmetric (mi_ilqr_set_cost)
-  // control limits (mi_ilqr_set_control_limits; read by the Limited<M> kernels only): (B, 2, m) - u_min | u_max per problem -
-  // and S2 = sum_t kappa_t^T Quu_t kappa_t of each problem's last backward pass, (B,), the quadratic term of the expected improvement
-  const double* ulim;
-  double* s2;
-  // per-problem targets (mi_ilqr_set MI_F_X_NOM / MI_F_TARGET_STEP), (B, n) each: x_nom of problem b is row b of x_nom_rows instead
-  // of the costmat's shared one, and MODE_MPC adds row b of target_steps (instead of mpc_target_step) before every re-solve.
-  // Null: the shared target.
-  const double* x_nom_rows;
-  const double* target_steps;
-  // per-problem model parameters (mi_ilqr_set MI_F_MODEL_PARAMS): the plant of problem b is row b of param_rows instead of `params`.
-  // Rows are DENSE: (B, n_params), the row stride is the model's n_params doubles - what mi_ilqr_device_ptr hands out.  The
-  // lane-per-problem kernels read param_cols, the same values batch-minor, (n_params, B): a wave's load of parameter k is one
-  // coalesced transaction.  Null (both): the shared `params`.  Neither array is written while a kernel runs.
-  const double* param_rows;
-  const double* param_cols;
-  // per-problem cost matrices (mi_ilqr_set MI_F_COST_MATRICES): Q | R | Qf of problem b is row b of cost_rows instead of the head of
-  // `costmat` (x_nom stays where the targets put it: x_nom_of).  Rows are DENSE: (B, 2 n^2 + m^2).  The lane-per-problem kernels read
-  // cost_cols, the same values batch-minor, (2 n^2 + m^2, B).  Null (both): the shared matrices.  seq_backward / cost_asym carry the
-  // class of the most general row.  Neither array is written while a kernel runs.
-  const double* cost_rows;
-  const double* cost_cols;
-};
-
-// Where problem b's target lives: row b of the per-problem targets, else the shared one in the costmat (Q | R | Qf | x_nom).
-template <int n, int m>
-__device__ __forceinline__ const double* x_nom_of(const KArgs& a, size_t b) {
-  return a.x_nom_rows ? a.x_nom_rows + b * n : a.costmat + 2 * n * n + m * m;
-}
-// Where problem b's Q | R | Qf live: row b of the per-problem cost matrices, else the head of the shared costmat.  Like x_nom_of: b is
-// uniform for the wave, both arms are global pointers out of the kernel arguments, the reads stay scalar loads.
-template <int n, int m>
-__device__ __forceinline__ const double* cost_of(const KArgs& a, size_t b) {
-  return a.cost_rows ? a.cost_rows + b * (2 * n * n + m * m) : a.costmat;
-}
-// Problem b's per-re-solve step of the MPC target, component i.
-template <int n>
-__device__ __forceinline__ double target_step_of(const KArgs& a, size_t b, int i) {
-  return a.target_steps ? a.target_steps[b * n + i] : a.mpc_target_step[i];
-}
-
-// The model parameters of problem b as VALUES: row b of the per-problem rows, else the shared copy in the kernel arguments.  b is
-// uniform for the wave (a wave or a workgroup serves one problem): the row is read through the constant address space - scalar
-// loads into scalar registers, where the shared copy lives too - once, by whoever constructs this, and handed on as values.  No
-// pointer ever selects between the two sources (that would be a generic-address-space or a scratch access).
-typedef const double __attribute__((address_space(4))) * const_row_t;
-template <class M>
-struct ModelParams {
-  double v[M::n_params > 0 ? M::n_params : 1];
-  // row: this problem's row of KArgs::param_rows, or nullptr
-  __device__ __forceinline__ ModelParams(const KArgs& a, const double* row) {
-    if (row != nullptr) {
-      const const_row_t r = (const_row_t)row;
-#pragma unroll
-      for (int i = 0; i < M::n_params; ++i) v[i] = r[i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < M::n_params; ++i) v[i] = a.params[i];
-    }
-    if constexpr (M::n_params == 0) v[0] = 0.0;
-  }
-};
-template <class M>
-__device__ __forceinline__ const double* param_row_of(const KArgs& a, size_t b) {
-  return a.param_rows ? a.param_rows + b * M::n_params : nullptr;
-}
-
-// threadIdx.x behind an empty asm, for the STAGES of a solve kernel (a rollout, a linearization, a backward pass): what a stage
-// derives from its lane index is loop-invariant for the solve loop around the stages, the compiler hoists it out of that loop,
-// and the hoisted values - dozens of lane-dependent addresses per stage - then live across every other stage and get spilled in
-// whichever inner loop is tightest.  Opaque per call, they are formed at the top of the stage and die with it (measured on the
-// workgroup-per-problem kernels, round 5: backward pass of the arm 6.2 k -> 5.5 k cycles per step, of the coupled arm 7.4 k -> 5.5 k;
-// on the wave-per-problem kernels of this file it changes nothing - C2 43.19 M it/s either way - and they keep threadIdx.x).
-__device__ __forceinline__ int stage_lane() {
-  int t = threadIdx.x;
-  asm volatile("" : "+v"(t));
-  return t;
-}
-
-__device__ __forceinline__ double bcast_lane0(double v) {
-  union { double d; int i[2]; } u;
-  u.d = v;
-  u.i[0] = __builtin_amdgcn_readfirstlane(u.i[0]);
-  u.i[1] = __builtin_amdgcn_readfirstlane(u.i[1]);
-  return u.d;
-}
-
-// One wavefront owns a problem's LDS outside the linearization: ordering its own LDS traffic needs
-// no s_barrier (LDS executes a wave's operations in order), only that the compiler keeps the order
-// and waits for completion.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// Rendezvous of the main wave with its helper waves (LDS traffic only).
-__device__ __forceinline__ void team_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-// ---------------------------------------------------------------------------
-// LDS layout: array-of-records, ONE record per time step, so that everything a
-// sequential step touches is reachable from a single per-step pointer with
-// compile-time (immediate) offsets — no per-access address arithmetic in the
-// latency-critical loops, and adjacent fields fuse into ds_read2/ds_read_b128.
-//   G_t  nominal trajectory + gains : x_bar[n] | K[m][n] | u_bar[m] | kappa[m], dV
-//   T_t  trial trajectory           : x[n] | u[m]
-//   J_t  dynamics partials          : fx[n][n] | fu[n][m]
-// (HBM keeps the reference's time-last layout; the staging copy transposes.)
-// Each array has one pad record before index 0 and after the last index so the
-// one-step-ahead software prefetch never needs a clamp.
-// ---------------------------------------------------------------------------
-template <int n, int m>
-struct Lay {
-  static constexpr int even(int v) { return (v + 1) & ~1; }
-  static constexpr int XB = 0;
-  static constexpr int KK = even(n);
-  static constexpr int UB = KK + even(m * n);
-  static constexpr int KAP = UB + even(m);
-  static constexpr int DV = KAP + m;
-  // n = 2 (the passes over time are lane-chunked there: Riccati scan, Newton rollout): record strides
-  // are ODD numbers of doubles, so lanes reading consecutive records hit 32 different bank pairs and
-  // lanes owning chunks of 2..4 consecutive records conflict at most 4-way instead of 32-way.  Larger
-  // n keeps 16-byte aligned records (b128 loads in the wave-uniform sweeps matter more there).
-  static constexpr int pad(int v) { return n <= 2 ? (v | 1) : even(v); }
-  static constexpr int GS = pad(DV + 1);
-  static constexpr int XN = 0, UN = even(n), TS = pad(UN + m);
-  static constexpr int FX = 0, FU = even(n * n), JS = pad(FU + n * m);
-  static constexpr int DUMP_DOUBLES = 64 * 2 + (GS > JS ? GS : JS);   // 16 B per lane + one record of slack
-  // copy of the cost constants (Consts<M>) for code that runs outside the kernel function (outlined passes)
-  static constexpr int CST_DOUBLES = (n >= 3) ? even(2 * n * n + m * m + 3 * n) : 0;
-};
-
-struct WS {
-  double *G, *T, *J;       // point at record index 0 (pad record lives at index -1)
-  double* dump;            // per-lane sink for predicated-off stores (lane*16 B)
-  double* cst;             // Consts<M> image (n >= 3)
-  int *kp, *aux, *need, *binA, *binB;
-  int N;
-  int n_store, t_stride;   // T holds n_store trajectories, t_stride doubles apart
-};
-
-template <int n, int m>
-__host__ __device__ constexpr size_t ws_bytes(int N, int n_store = 1) {
-  using L = Lay<n, m>;
-  return ((size_t)(N + 2) * L::GS + (size_t)n_store * (N + 2) * L::TS + (size_t)(N + 2) * L::JS + L::DUMP_DOUBLES + L::CST_DOUBLES) * 8 +
-         (size_t)7 * N * 4 + 16;
-}
-
-template <int n, int m>
-__device__ inline WS carve(char* base, int N, int n_store) {
-  using L = Lay<n, m>;
-  WS w;
-  w.N = N;
-  double* p = reinterpret_cast<double*>(base);
-  w.G = p + L::GS; p += (size_t)(N + 2) * L::GS;
-  w.T = p + L::TS; p += (size_t)n_store * (N + 2) * L::TS;
-  w.n_store = n_store; w.t_stride = (N + 2) * L::TS;
-  w.J = p + L::JS; p += (size_t)(N + 2) * L::JS;
-  w.dump = p; p += L::DUMP_DOUBLES;
-  w.cst = p; p += L::CST_DOUBLES;
-  int* q = reinterpret_cast<int*>(p);
-  w.kp = q; q += N;
-  w.aux = q; q += N;
-  w.need = q; q += N;
-  w.binA = q; q += 2 * N;
-  w.binB = q;
-  return w;
-}
-
-// Result write-back store that goes THROUGH the L2 (device-scope relaxed store = sc1): most waves of a launch
-// finish long before its slowest problem, and lines they leave dirty would all be written back by the
-// end-of-kernel release, i.e. inside the gap before the next dispatch.
-__device__ __forceinline__ void wt_store(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // HBM (rows,len) time-last  ->  LDS records rec[t*RS + off + row]   (and back)
 __device__ inline void stage_in(double* recs, int RS, int off, const double* src, int rows, int len, bool zero) {
@@ -303,94 +67,6 @@ __device__ inline void stage_out(double* dst, const double* recs, int RS, int of
   }
 }
 
-// The bounds of one problem, in registers for the whole launch (Limited<M> kernels; empty otherwise).
-template <class M, bool = UsesLimits<M>::value>
-struct LimitRegs {};
-template <class M>
-struct LimitRegs<M, true> {
-  double umin[M::m], umax[M::m];
-  __device__ inline void load_limits(const double* p) {      // p: this problem's (2, m) record
-#pragma unroll
-    for (int k = 0; k < M::m; ++k) { umin[k] = p[k]; umax[k] = p[M::m + k]; }
-  }
-  // clip(v, u_min, u_max) by comparisons: a NaN stays NaN (its trial is rejected as without limits)
-  __device__ __forceinline__ double clamp(int k, double v) const {
-    v = v < umin[k] ? umin[k] : v;
-    return v > umax[k] ? umax[k] : v;
-  }
-};
-
-template <class M>
-struct Consts : LimitRegs<M> {
-  static constexpr int n = M::n, m = M::m;
-  double Q[n][n], R[m][m], Qf[n][n], xnom[n];
-  double qn[n];    // 2*x_nom^T Q    (ilqr.py:180)
-  double qfn[n];   // 2*x_nom^T Qf   (ilqr.py:203)
-  __device__ inline void load(const double* cm) { load(cm, cm + 2 * n * n + m * m); }
-  // xn: this problem's target (x_nom_of); qn / qfn come from the same loop whichever array it is
-  __device__ inline void load(const double* cm, const double* xn) {
-    load_from([cm](int e) __attribute__((always_inline)) { return cm[e]; }, xn);
-  }
-  // at(e): entry e of Q | R | Qf wherever the matrices live (dense: cm[e]; the lane-per-problem kernels' per-problem matrices:
-  // KArgs::cost_cols, batch-minor) - ONE loop builds the constants whichever array they came from
-  template <class At>
-  __device__ inline void load_from(At at, const double* xn) {
-#pragma unroll
-    for (int i = 0; i < n; ++i)
-#pragma unroll
-      for (int j = 0; j < n; ++j) { Q[i][j] = at(i * n + j); Qf[i][j] = at(n * n + m * m + i * n + j); }
-#pragma unroll
-    for (int i = 0; i < m; ++i)
-#pragma unroll
-      for (int j = 0; j < m; ++j) R[i][j] = at(n * n + i * m + j);
-#pragma unroll
-    for (int i = 0; i < n; ++i) xnom[i] = xn[i];
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      double s = 0.0, sf = 0.0;
-#pragma unroll
-      for (int i = 0; i < n; ++i) { s += (2.0 * xnom[i]) * Q[i][j]; sf += (2.0 * xnom[i]) * Qf[i][j]; }
-      qn[j] = s; qfn[j] = sf;
-    }
-  }
-  // Qf alone, read again (the lane-per-problem kernels' per-problem matrices: Qf is used twice per iteration, and re-reading it
-  // there keeps n^2 values per lane out of the registers in between)
-  template <class At>
-  __device__ __forceinline__ void reload_Qf(At at) {
-#pragma unroll
-    for (int i = 0; i < n; ++i)
-#pragma unroll
-      for (int j = 0; j < n; ++j) Qf[i][j] = at(n * n + m * m + i * n + j);
-  }
-  // LDS image: Q | Qf | R | xnom | qn | qfn
-  __device__ inline void to_lds(double* d) const {
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-      for (int i = 0; i < n; ++i)
-#pragma unroll
-        for (int j = 0; j < n; ++j) { d[i * n + j] = Q[i][j]; d[n * n + i * n + j] = Qf[i][j]; }
-#pragma unroll
-      for (int i = 0; i < m; ++i)
-#pragma unroll
-        for (int j = 0; j < m; ++j) d[2 * n * n + i * m + j] = R[i][j];
-#pragma unroll
-      for (int i = 0; i < n; ++i) { d[2 * n * n + m * m + i] = xnom[i]; d[2 * n * n + m * m + n + i] = qn[i]; d[2 * n * n + m * m + 2 * n + i] = qfn[i]; }
-    }
-  }
-  __device__ inline void from_lds(const double* d) {
-#pragma unroll
-    for (int i = 0; i < n; ++i)
-#pragma unroll
-      for (int j = 0; j < n; ++j) { Q[i][j] = d[i * n + j]; Qf[i][j] = d[n * n + i * n + j]; }
-#pragma unroll
-    for (int i = 0; i < m; ++i)
-#pragma unroll
-      for (int j = 0; j < m; ++j) R[i][j] = d[2 * n * n + i * m + j];
-#pragma unroll
-    for (int i = 0; i < n; ++i) { xnom[i] = d[2 * n * n + m * m + i]; qn[i] = d[2 * n * n + m * m + n + i]; qfn[i] = d[2 * n * n + m * m + 2 * n + i]; }
-  }
-};
-
 // ---------------------------------------------------------------------------
 // One line-search trial (ilqr.py:306-327) for this lane's eps.  G records are
 // read at wave-uniform addresses (LDS broadcast), one step ahead of use, into
@@ -398,53 +74,6 @@ struct Consts : LimitRegs<M> {
 // Lane 0 stores its trajectory into the T records; the other lanes' stores go
 // to a per-lane dump slot so the loop carries no exec-mask branches.
 // ---------------------------------------------------------------------------
-// The full row sums, also where Q is diagonal.  A wave-uniform branch that leaves out the products with Q's zeros (on a flag the
-// host set for such a Q) gives the same bits and saves 12 of the 146 instructions of a cart-pole + wall rollout step, but MEASURED
-// in the fused kernel (round 6, profiles/r06_c4_ab.txt) the line search got 26 % LONGER (178.6 k -> 224.9 k cycles per iteration):
-// the second arm of the branch lives in the same loop, and its registers push the loop's values into the accumulation file.  The
-// flag and its detection in mi_ilqr_set_cost left the sources with this finding.
-template <class M>
-__device__ __forceinline__ double stage_cost(const Consts<M>& c, const double (&x)[M::n], const double (&u)[M::m]) {
-  constexpr int n = M::n, m = M::m;
-  double dx[n];
-#pragma unroll
-  for (int i = 0; i < n; ++i) dx[i] = x[i] - c.xnom[i];
-  double q = 0.0;
-#pragma unroll
-  for (int i = 0; i < n; ++i) {
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < n; ++j) s += c.Q[i][j] * dx[j];
-    q += dx[i] * s;
-  }
-  double ru = 0.0;
-#pragma unroll
-  for (int i = 0; i < m; ++i) {
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < m; ++j) s += c.R[i][j] * u[j];
-    ru += u[i] * s;
-  }
-  return q + ru;
-}
-
-template <class M>
-__device__ __forceinline__ double terminal_cost(const Consts<M>& c, const double (&x)[M::n]) {
-  constexpr int n = M::n;
-  double dx[n];
-#pragma unroll
-  for (int i = 0; i < n; ++i) dx[i] = x[i] - c.xnom[i];
-  double q = 0.0;
-#pragma unroll
-  for (int i = 0; i < n; ++i) {
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < n; ++j) s += c.Qf[i][j] * dx[j];
-    q += dx[i] * s;
-  }
-  return q;
-}
-
 template <class M>
 struct GRegs {
   double xb[M::n], K[M::m][M::n], ub[M::m], kap[M::m], dv;
@@ -557,32 +186,6 @@ __device__ inline void rollout(const WS& w, const Consts<M>& c, const KArgs& a, 
   else exp_out = expd;
 }
 
-// Sum over each 16-lane row, result in every lane of the row: four DPP row rotations (8, 4, 2, 1)
-// instead of four ds_bpermute round trips through the LDS crossbar.
-template <int ROT>
-__device__ __forceinline__ double row_ror_f64(double v) {
-  union { double d; int i[2]; } u, r;
-  u.d = v;
-  r.i[0] = __builtin_amdgcn_mov_dpp(u.i[0], 0x120 + ROT, 0xF, 0xF, true);
-  r.i[1] = __builtin_amdgcn_mov_dpp(u.i[1], 0x120 + ROT, 0xF, 0xF, true);
-  return r.d;
-}
-__device__ __forceinline__ double row16_sum(double p) {
-  p += row_ror_f64<8>(p);
-  p += row_ror_f64<4>(p);
-  p += row_ror_f64<2>(p);
-  p += row_ror_f64<1>(p);
-  return p;
-}
-
-// Sum over the wave, result in every lane, fixed order: DPP row sums, then the four row totals
-// through v_readlane (SGPRs) - no ds_bpermute round trips.
-__device__ __forceinline__ double readlane_f64(double v, int srclane);
-__device__ __forceinline__ double wave_sum(double v) {
-  v = row16_sum(v);
-  return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
-}
-
 // Total cost (ilqr.py:325,327) and expected improvement (:326) of the trajectory stored in
 // the T records, evaluated time-parallel (one time step per lane, fixed-order wave reduction).
 template <class M>
@@ -627,7 +230,6 @@ __device__ inline void traj_cost(const WS& w, const Consts<M>& c, double eps, do
 // posteriori.  Not converged within the cap (cold starts, the first iteration of hard problems), or the check
 // fails -> the caller falls back to the sequential rollout.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double lane_read_f64(double v, int src);
 
 // One column of [fx | fu] at (x, u): central differences (the build's stand-in for AutoDiff,
 // ilqr.py:233-272) or one forward-mode dual evaluation.
@@ -685,19 +287,6 @@ __device__ __forceinline__ void aff2_compose_dev(Aff2& o, const Aff2& l, const A
 #pragma unroll
     for (int j = 0; j < 2; ++j) o.G[i][j] = fma(l.G[i][0], e.G[0][j], fma(l.G[i][1], e.G[1][j], l.G[i][j] + e.G[i][j]));
   }
-}
-template <int CTRL, int ROWS>
-__device__ __forceinline__ double dpp_f64_or_zero(double v) {
-  union { double d; int i[2]; } u, r;
-  u.d = v;
-  if constexpr (ROWS == 0xF) {                                              // no source lane: 0 (bound_ctrl)
-    r.i[0] = __builtin_amdgcn_mov_dpp(u.i[0], CTRL, 0xF, 0xF, true);
-    r.i[1] = __builtin_amdgcn_mov_dpp(u.i[1], CTRL, 0xF, 0xF, true);
-  } else {                                                                  // row not selected: 0 (old value)
-    r.i[0] = __builtin_amdgcn_update_dpp(0, u.i[0], CTRL, ROWS, 0xF, true);
-    r.i[1] = __builtin_amdgcn_update_dpp(0, u.i[1], CTRL, ROWS, 0xF, true);
-  }
-  return r.d;
 }
 template <int CTRL, int ROWS>
 __device__ __forceinline__ void aff2_prefix_level(Aff2& P) {
@@ -1290,18 +879,6 @@ __device__ inline int linearize(const WS& w, const KArgs& a, const ModelParams<M
                            [&](const int* list, int count) __attribute__((always_inline)) { jac_at<M, JAC>(w, a, par, list, count); });
 }
 
-template <int m>
-__device__ __forceinline__ void invert_small(const double (&A)[m][m], double (&Ai)[m][m]) {
-  static_assert(m >= 1 && m <= 2, "wave-per-problem path covers m <= 2");
-  if constexpr (m == 1) {
-    Ai[0][0] = fast_rcp(A[0][0]);
-  } else {
-    const double id = fast_rcp(A[0][0] * A[1][1] - A[0][1] * A[1][0]);
-    Ai[0][0] = A[1][1] * id; Ai[0][1] = -A[0][1] * id;
-    Ai[1][0] = -A[1][0] * id; Ai[1][1] = A[0][0] * id;
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Backward Riccati pass (ilqr.py:623-667) with the quadratic cost expansion
 // (:161-206) fused in.  Wave-uniform: every lane carries the same Vx/Vxx in
@@ -1537,175 +1114,6 @@ __device__ inline void backward_scalar(const WS& w, const Consts<M>& c) {
   if (t == 0) backward_step<M>(A, c, Q2, R2, Vx, Vxx, gw);
 }
 
-// ---------------------------------------------------------------------------
-// Backward step with box control limits (Limited<M> kernels, m <= 2): given the expansion Qx, Qu, Qxx, Quu, Qux of
-// step t (ilqr.py:651-656), solve  du* = argmin 1/2 du^T Quu du + Qu^T du  subject to  lo <= du <= hi
-// (lo = u_min - u_bar_t, hi = u_max - u_bar_t) and set kappa = -du*.
-//   m = 1: the clamp of -Qu / Quu.
-//   m = 2: the unconstrained minimiser when it lies in the box; otherwise the best of the four edges u0 = lo0, u0 = hi0,
-//          u1 = lo1, u1 = hi1 (infinite edges skipped), each with the free component's clamped 1-D minimiser (the row of
-//          Quu du + Qu = 0 it solves); the smallest objective wins, a tie goes to the earlier edge.
-// The clamped components are those the chosen candidate put on a bound - decided by that construction, never by
-// comparing floats afterwards.  Their rows of K are 0; the free rows are Quu_ff^-1 Qux_f.  With nothing clamped every
-// output is the reference's arithmetic (backward_step); otherwise dV = kappa^T Qu and the value update takes its general
-// form Vx = Qx - K^T Qu - Qux^T kappa + K^T Quu kappa, Vxx = Qxx - K^T Qux - Qux^T K + K^T Quu K.
-// s2 accumulates kappa^T Quu kappa.  Returns false when Quu is not positive definite (no minimiser; the problem stops
-// with MI_STATUS_NOT_PD).  Shared by the wave- and lane-per-problem kernels.
-// ---------------------------------------------------------------------------
-template <int n, int m>
-__device__ __forceinline__ bool box_qp_step(const double (&Qx)[n], const double (&Qu)[m], const double (&Qxx)[n][n],
-                                            const double (&Quu)[m][m], const double (&Qux)[m][n], const double (&lo)[m],
-                                            const double (&hi)[m], double (&kap)[m], double (&Kg)[m][n], double& dv,
-                                            double& s2, double (&Vx)[n], double (&Vxx)[n][n]) {
-  static_assert(m >= 1 && m <= 2, "box QP of the m <= 2 kernels");
-  bool pd;
-  if constexpr (m == 1) pd = Quu[0][0] > 0.0 && __builtin_isfinite(Quu[0][0]);
-  else {
-    const double det = Quu[0][0] * Quu[1][1] - Quu[0][1] * Quu[1][0];
-    pd = Quu[0][0] > 0.0 && det > 0.0 && __builtin_isfinite(det) && __builtin_isfinite(Quu[0][0]) && __builtin_isfinite(Quu[1][1]) &&
-         __builtin_isfinite(Quu[0][1]) && __builtin_isfinite(Quu[1][0]);
-  }
-  double Qi[m][m];
-  invert_small<m>(Quu, Qi);
-  double d[m];                                              // du*, the minimiser
-  bool cl[m];                                               // component on a bound
-#pragma unroll
-  for (int a_ = 0; a_ < m; ++a_) {
-    double s = 0.0;
-#pragma unroll
-    for (int b_ = 0; b_ < m; ++b_) s += Qi[a_][b_] * Qu[b_];
-    d[a_] = -s;
-    cl[a_] = false;
-  }
-  if constexpr (m == 1) {
-    if (d[0] < lo[0]) { d[0] = lo[0]; cl[0] = true; }
-    else if (d[0] > hi[0]) { d[0] = hi[0]; cl[0] = true; }
-  } else {
-    const bool inside = !(d[0] < lo[0]) && !(d[0] > hi[0]) && !(d[1] < lo[1]) && !(d[1] > hi[1]);
-    if (!inside) {
-      double best = __builtin_inf();
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int fx_ = e >> 1, fr = 1 - fx_;                // the component on the edge, the free one
-        const double v = (e & 1) ? hi[fx_] : lo[fx_];
-        if (!__builtin_isfinite(v)) continue;
-        double f = -(Qu[fr] + Quu[fr][fx_] * v) / Quu[fr][fr];
-        bool cf = false;
-        if (f < lo[fr]) { f = lo[fr]; cf = true; }
-        else if (f > hi[fr]) { f = hi[fr]; cf = true; }
-        double c2[2];
-        c2[fx_] = v; c2[fr] = f;
-        const double obj = 0.5 * (c2[0] * (Quu[0][0] * c2[0] + Quu[0][1] * c2[1]) + c2[1] * (Quu[1][0] * c2[0] + Quu[1][1] * c2[1])) +
-                           (Qu[0] * c2[0] + Qu[1] * c2[1]);
-        if (obj < best) {
-          best = obj;
-          d[0] = c2[0]; d[1] = c2[1];
-          cl[fx_] = true; cl[fr] = cf;
-        }
-      }
-    }
-  }
-  bool any = false;
-#pragma unroll
-  for (int a_ = 0; a_ < m; ++a_) { kap[a_] = -d[a_]; any = any || cl[a_]; }
-  double Qk[m];                                             // Quu kappa
-#pragma unroll
-  for (int a_ = 0; a_ < m; ++a_) {
-    double s = 0.0;
-#pragma unroll
-    for (int b_ = 0; b_ < m; ++b_) s += Quu[a_][b_] * kap[b_];
-    Qk[a_] = s;
-  }
-  double kqk = 0.0;
-#pragma unroll
-  for (int a_ = 0; a_ < m; ++a_) kqk += kap[a_] * Qk[a_];
-  s2 += kqk;
-  if (!any) {
-    // the reference's step (ilqr.py:659-667; backward_step)
-    double QuQi[m];
-#pragma unroll
-    for (int a_ = 0; a_ < m; ++a_) {
-      double s = 0.0, q = 0.0;
-#pragma unroll
-      for (int b_ = 0; b_ < m; ++b_) { s += Qi[a_][b_] * Qu[b_]; q += Qu[b_] * Qi[b_][a_]; }
-      kap[a_] = s;
-      QuQi[a_] = q;
-#pragma unroll
-      for (int j = 0; j < n; ++j) {
-        double g = 0.0;
-#pragma unroll
-        for (int b_ = 0; b_ < m; ++b_) g += Qi[a_][b_] * Qux[b_][j];
-        Kg[a_][j] = g;
-      }
-    }
-    dv = 0.0;
-#pragma unroll
-    for (int a_ = 0; a_ < m; ++a_) dv += QuQi[a_] * Qu[a_];
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      double s = Qx[j];
-#pragma unroll
-      for (int a_ = 0; a_ < m; ++a_) s -= QuQi[a_] * Qux[a_][j];
-      Vx[j] = s;
-    }
-    double QuxTQi[n][m];
-#pragma unroll
-    for (int i = 0; i < n; ++i)
-#pragma unroll
-      for (int b_ = 0; b_ < m; ++b_) {
-        double s = 0.0;
-#pragma unroll
-        for (int a_ = 0; a_ < m; ++a_) s += Qux[a_][i] * Qi[a_][b_];
-        QuxTQi[i][b_] = s;
-      }
-#pragma unroll
-    for (int i = 0; i < n; ++i)
-#pragma unroll
-      for (int j = 0; j < n; ++j) {
-        double s = Qxx[i][j];
-#pragma unroll
-        for (int b_ = 0; b_ < m; ++b_) s -= QuxTQi[i][b_] * Qux[b_][j];
-        Vxx[i][j] = s;
-      }
-    return pd;
-  }
-  // K: clamped rows 0, free rows Quu_ff^-1 Qux_f (at most one free component here)
-#pragma unroll
-  for (int a_ = 0; a_ < m; ++a_)
-#pragma unroll
-    for (int j = 0; j < n; ++j) Kg[a_][j] = cl[a_] ? 0.0 : Qux[a_][j] / Quu[a_][a_];
-  dv = 0.0;
-#pragma unroll
-  for (int a_ = 0; a_ < m; ++a_) dv += kap[a_] * Qu[a_];
-  double QK[m][n];                                          // Quu K
-#pragma unroll
-  for (int a_ = 0; a_ < m; ++a_)
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      double s = 0.0;
-#pragma unroll
-      for (int b_ = 0; b_ < m; ++b_) s += Quu[a_][b_] * Kg[b_][j];
-      QK[a_][j] = s;
-    }
-#pragma unroll
-  for (int j = 0; j < n; ++j) {
-    double s = Qx[j];
-#pragma unroll
-    for (int a_ = 0; a_ < m; ++a_) s += -Kg[a_][j] * Qu[a_] - Qux[a_][j] * kap[a_] + Kg[a_][j] * Qk[a_];
-    Vx[j] = s;
-  }
-#pragma unroll
-  for (int i = 0; i < n; ++i)
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      double s = Qxx[i][j];
-#pragma unroll
-      for (int a_ = 0; a_ < m; ++a_) s += -Kg[a_][i] * Qux[a_][j] - Qux[a_][i] * Kg[a_][j] + Kg[a_][i] * QK[a_][j];
-      Vxx[i][j] = s;
-    }
-  return pd;
-}
-
 // Cost-to-go expansion of one step (ilqr.py:651-656; backward_step's arithmetic) from the cost gradients lx, lu.
 template <int n, int m>
 __device__ __forceinline__ void q_expansion(const double (&lx)[n], const double (&lu)[m], const double (&fx)[n][n],
@@ -1866,21 +1274,6 @@ __device__ inline bool backward_limited(const WS& w, const Consts<M>& c) {
 }
 
 typedef double d4s_t __attribute__((ext_vector_type(4)));
-
-// value of lane LANE of this lane's 16-lane row, for a double: one v_mov_b64_dpp row_newbcast
-// (gfx90a+ DPP64).  bound_ctrl with full row/bank masks: every lane is written.
-template <int LANE>
-__device__ __forceinline__ double row_share(double v) {
-  return __builtin_amdgcn_update_dpp(v, v, 0x150 + LANE, 0xF, 0xF, true);
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int srclane) {
-  union { double d; int i[2]; } u;
-  u.d = v;
-  u.i[0] = __builtin_amdgcn_readlane(u.i[0], srclane);
-  u.i[1] = __builtin_amdgcn_readlane(u.i[1], srclane);
-  return u.d;
-}
 
 // ---------------------------------------------------------------------------
 // Backward Riccati pass on the fp64 matrix core, for 3 <= n <= 4, m = 1.
@@ -2143,15 +1536,6 @@ __device__ __forceinline__ void ric_combine(RicElem<n>& o, const RicElem<n>& ei,
       }
     }
   }
-}
-
-// value of `v` in lane `src` (any lane; out-of-range callers mask the result)
-__device__ __forceinline__ double lane_read_f64(double v, int src) {
-  union { double d; int i[2]; } u, r;
-  u.d = v;
-  r.i[0] = __builtin_amdgcn_ds_bpermute(src << 2, u.i[0]);
-  r.i[1] = __builtin_amdgcn_ds_bpermute(src << 2, u.i[1]);
-  return r.d;
 }
 
 // One Kogge-Stone level of the scan over the lanes, operands moved with DPP: `dst` = the element of

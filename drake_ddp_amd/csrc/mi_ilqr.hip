@@ -23,15 +23,12 @@
 #include <vector>
 
 #include "../../include/mi_ilqr.h"
-#include "ilqr_batch.hpp"
-#include "ilqr_large.hpp"
-#include "ilqr_small.hpp"
+#include "host.hpp"          // the handle and the launch templates (instantiated in the k_*.hip units)
+#include "kernel_args.hpp"   // KArgs, DevStats
+#include "lds_layout.hpp"    // ws_bytes, large_lds_bytes, large_lds_bytes_hbm, kLargeThreads
+#include "models.hpp"
 
 using namespace mi;
-
-
-#include "host.hpp"
-
 using namespace mi_host;
 
 namespace {
@@ -925,7 +922,7 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   }
   bool lxu_hbm = false;
   if (!batch_minor && lds > kMaxLds && large) {
-    // the horizon's cost gradients do not fit beside the fixed block: keep them in HBM (ilqr_large.hpp: large_lds_bytes_hbm)
+    // the horizon's cost gradients do not fit beside the fixed block: keep them in HBM (lds_layout.hpp: large_lds_bytes_hbm)
     const size_t l = model.lds_bytes(desc->N, -1);
     if (l != 0 && l <= kMaxLds) { lds = l; lxu_hbm = true; }
   }

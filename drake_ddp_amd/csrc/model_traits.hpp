@@ -84,8 +84,8 @@ struct ExactCost : M { static constexpr bool kExactBackward = true; };
 template <class M>
 struct Limited : M { static constexpr bool kLimited = true; };
 
-// Constants derived from the traits alone.  (kSpecRollout - which models get mid_rollout4 - also reads LLay<n, m>::kMid and stays
-// beside that layout in ilqr_large.hpp.)  kLxFromRollout: the rollout leaves lx_t, lu_t of the accepted trial in the backward pass's
+// Constants derived from the traits alone.  (kSpecRollout - which models get mid_rollout4 - also reads LLay<n, m>::kMid
+// (lds_layout.hpp) and stays in ilqr_large.hpp.)  kLxFromRollout: the rollout leaves lx_t, lu_t of the accepted trial in the backward pass's
 // cost-gradient area (not chain models: their linearization uses that area as a cache).  kEarlyLin: early linearization is possible.
 template <class M>
 constexpr bool kLxFromRollout = !IsChainModel<M>::value;

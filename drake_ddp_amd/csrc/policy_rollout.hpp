@@ -19,7 +19,10 @@
 // the steps it completed and a cost of +inf, and fills the rest of its trajectories with NaN.  All of this is per-lane selects:
 // the kernel has no wave-level operation and no early return, so one failing sample changes nothing for its neighbours.
 #pragma once
-#include "host.hpp"
+#include "fastmath.hpp"
+#include "host.hpp"           // mi_ilqr, PolicyArgs, HIPCHK
+#include "model_traits.hpp"   // CanFail
+#include "models.hpp"
 
 namespace mi {
 

@@ -590,7 +590,7 @@ def test_shortest_horizons_vs_c_oracle(N):
             s.SetInitialState(x0); s.SetInitialGuess(ug)
             s.Solve()                                    # (the batched class reports a line search that ran out of step sizes on a tie
             assert s.stats.n_internal == 0               #  per problem; it RAISES for an aborted kernel - which round 6 found this test
-            rel = np.abs(s.cost - r["cost"]) / np.abs(r["cost"])   #  had been swallowing: clustered launches at N = 3, ilqr_large.hpp: kIntRowMin)
+            rel = np.abs(s.cost - r["cost"]) / np.abs(r["cost"])   #  had been swallowing: clustered launches at N = 3, lds_layout.hpp: kIntRowMin)
             xe = np.abs(s.x_bar - r["x_bar"]).max()
             print(f"N = {N} {name} ({mode}): cost {rel.max():.1e}, x {xe:.1e}")
             assert np.isfinite(s.x_bar).all() and rel.max() < 1e-11 and xe < 2e-5

@@ -1,0 +1,75 @@
+"""The layering of the native headers (drake_ddp_amd/csrc/*.hpp; DESIGN.md, "Source layout"): every header compiles as the only
+include of a translation unit, and the `#include "..."` lines keep the kernel families apart - no family header includes
+another, the host (host.hpp, mi_ilqr.hip) includes none of them, policy_rollout.hpp names what it uses.  Compile-only
+(-fsyntax-only) and text checks: needs hipcc, no GPU."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from drake_ddp_amd import build  # noqa: E402
+
+FAMILY = {"ilqr_small.hpp", "ilqr_large.hpp", "ilqr_batch.hpp", "policy_rollout.hpp"}
+HEADERS = sorted(f for f in os.listdir(build.CSRC) if f.endswith(".hpp"))
+
+
+def includes(name):
+    """The quoted includes of csrc/<name>, as written."""
+    with open(os.path.join(build.CSRC, name)) as f:
+        return re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)
+
+
+def test_the_headers_the_rules_speak_of_exist():
+    assert FAMILY <= set(HEADERS)
+    assert {"host.hpp", "kernel_args.hpp", "lds_layout.hpp", "wave_ops.hpp", "cost_terms.hpp", "model_traits.hpp", "models.hpp",
+            "fastmath.hpp", "launch_small.hpp", "launch_large.hpp", "launch_batch.hpp"} <= set(HEADERS)
+
+
+@pytest.mark.parametrize("header", HEADERS)
+def test_header_compiles_as_the_only_include(header, tmp_path):
+    src = tmp_path / ("only_" + header[:-4] + ".hip")
+    src.write_text('#include "%s"\n' % os.path.join(build.CSRC, header))
+    r = subprocess.run([build.HIPCC, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", str(src)],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout[-4000:]
+
+
+@pytest.mark.parametrize("header", sorted(FAMILY))
+def test_no_family_header_includes_another(header):
+    assert not (set(includes(header)) & FAMILY), includes(header)
+
+
+def test_the_shared_headers_include_no_family_header_and_no_launch_templates():
+    for name in ("kernel_args.hpp", "lds_layout.hpp", "wave_ops.hpp", "cost_terms.hpp", "host.hpp"):
+        inc = set(includes(name))
+        assert not (inc & FAMILY) and not any(i.startswith("launch_") for i in inc), (name, sorted(inc))
+
+
+def test_kernel_args_knows_no_model_and_no_keypoint_code():
+    assert includes("kernel_args.hpp") == ["../../include/mi_ilqr.h"]
+    with open(os.path.join(build.CSRC, "kernel_args.hpp")) as f:
+        assert sorted(re.findall(r"^\s*#\s*include\s+<([^>]+)>", f.read(), re.M)) == ["hip/hip_runtime.h", "stdint.h"]
+
+
+def test_host_takes_the_kernel_arguments_from_their_own_header():
+    assert "kernel_args.hpp" in includes("host.hpp")
+
+
+def test_policy_rollout_names_what_it_uses():
+    assert {"host.hpp", "fastmath.hpp", "model_traits.hpp", "models.hpp"} <= set(includes("policy_rollout.hpp"))
+
+
+def test_the_abi_unit_includes_the_interface_and_no_kernel_templates():
+    inc = set(includes("mi_ilqr.hip"))
+    assert {"host.hpp", "kernel_args.hpp", "lds_layout.hpp", "models.hpp"} <= inc
+    assert not (inc & FAMILY) and not any(i.startswith("launch_") for i in inc), sorted(inc)
+
+
+def test_each_launch_header_serves_one_family():
+    for launch, family in (("launch_small.hpp", "ilqr_small.hpp"), ("launch_large.hpp", "ilqr_large.hpp"), ("launch_batch.hpp", "ilqr_batch.hpp")):
+        assert set(includes(launch)) & FAMILY == {family}, (launch, includes(launch))
