@@ -29,6 +29,8 @@ F_X_NOM, F_TARGET_STEP = 14, 15   # (B, n) per-problem targets and MPC target st
 F_MODEL_PARAMS = 16               # (B, n_params) per-problem model parameters (mi_ilqr.h: "Per-problem model parameters")
 F_COST_MATRICES = 17              # (B, 2n^2+m^2) per-problem cost matrices, row b = Q_b | R_b | Qf_b (mi_ilqr.h: "Per-problem cost matrices")
 F_POLICY_KERNEL_MS = 18           # (1,) ms of the rollout kernel of the last mi_ilqr_policy_rollout
+F_POLICY_NOISE = 19               # (B, n+m) sigma_x | sigma_u of the policy rollouts' disturbances
+F_POLICY_STREAM = 20              # (3,) seed | first_sample | common of their random stream
 I_ITERS, I_STATUS, I_LS_TRIALS, I_KP_COUNT, I_KP_LIST = 100, 101, 102, 103, 104
 I64_STAGE_CYCLES = 200
 I64_CLUSTER_WORDS = 201

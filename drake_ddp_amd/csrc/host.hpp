@@ -17,7 +17,8 @@
 // library-internal: hidden from the dynamic symbol table (the C ABI is mi_ilqr.h)
 #define MI_INTERNAL __attribute__((visibility("hidden")))
 
-// One per-problem (B, width) array of a handle (mi_ilqr_set MI_F_X_NOM / MI_F_TARGET_STEP / MI_F_MODEL_PARAMS / MI_F_COST_MATRICES;
+// One per-problem (B, width) array of a handle (mi_ilqr_set MI_F_X_NOM / MI_F_TARGET_STEP / MI_F_MODEL_PARAMS / MI_F_COST_MATRICES /
+// MI_F_POLICY_NOISE;
 // mi_ilqr.hip: store_upload / store_drop / store_read).  The host mirror is the truth: what mi_ilqr_get returns without touching the
 // stream and what mi_ilqr_mpc_run advances; the device copies follow it on the handle's stream.  `synced` - they equal it - is the
 // array's per-problem mode: only then do the kernels get the pointers, a failed copy leaves the mode, and rows the caller repeats
@@ -123,6 +124,12 @@ struct mi_ilqr {
   // so that the solves' events and statistics stay what they were
   hipEvent_t policy_ev0 = nullptr, policy_ev1 = nullptr;
   bool policy_ran = false;         // the events hold a launch (a policy rollout has run on this handle)
+  // the rollouts' disturbances: MI_F_POLICY_NOISE, (B, n + m) rows sigma_x | sigma_u - `synced` selects the noisy kernels - and
+  // MI_F_POLICY_STREAM.  Read by mi_ilqr_policy_rollout only; problem data, mi_ilqr_reset keeps them.
+  RowStore policy_noise;
+  unsigned long long policy_seed = 0;
+  uint32_t policy_first_sample = 0;
+  bool policy_common = false;
 };
 
 // Run-time switches for A/B runs (README): the environment is read once per process.
@@ -258,6 +265,7 @@ struct PolicyArgs {
   const double* cost;         // Q | R | Qf of problem b at b * cost_stride
   const double* x_nom;        // (n,) of problem b at b * x_nom_stride
   const double* ulim;         // (B, 2, m) u_min | u_max, or nullptr: no clamp
+  const double* noise;        // (B, n + m) sigma_x | sigma_u of problem b (MI_F_POLICY_NOISE), or nullptr: the noise-free kernels
   double* cost_out;           // (B, S)
   double* x_final;            // (B, n, S) sample-minor
   int32_t* steps;             // (B, S)
@@ -266,8 +274,12 @@ struct PolicyArgs {
   size_t param_stride, cost_stride, x_nom_stride;
   double dt;
   int32_t N, S, B, m_user;    // m_user: controls m_user .. m-1 are padding and stay exact zeros
+  unsigned long long seed;    // MI_F_POLICY_STREAM: the Philox key, the number of the call's sample 0, one stream for all problems
+  uint32_t first_sample;
+  int32_t common;
 };
-template <class M> MI_INTERNAL int launch_policy_rollout(mi_ilqr* h, const PolicyArgs& a);          // policy_rollout.hpp
+template <class M> MI_INTERNAL int launch_policy_rollout(mi_ilqr* h, const PolicyArgs& a);          // policy_rollout.hpp; k_policy.hip
+template <class M> MI_INTERNAL int launch_policy_rollout_noise(mi_ilqr* h, const PolicyArgs& a);    // ... k_policy_noise.hip
 
 // The launch entry of a model's record (mi_ilqr_model_plugin::launch), built-in or plugin: the handle picks the kernel set - the
 // lane-per-problem kernels (h->batch_minor), the Limited<M> ones (h->limited), else the regular ones.  A set the model lacks is
@@ -286,7 +298,10 @@ int launch_entry(mi_ilqr* h, int mode, const void* kargs) {
 // ... and the same for model M with the policy rollout (kModePolicyRollout), which is one kernel per model whatever the handle's family
 template <class M, Launcher REGULAR, Launcher LIMITED = nullptr, Launcher BATCH = nullptr, Launcher BATCH_LIMITED = nullptr>
 int model_entry(mi_ilqr* h, int mode, const void* kargs) {
-  if (mode == kModePolicyRollout) return launch_policy_rollout<M>(h, *static_cast<const PolicyArgs*>(kargs));
+  if (mode == kModePolicyRollout) {
+    const PolicyArgs& a = *static_cast<const PolicyArgs*>(kargs);
+    return a.noise ? launch_policy_rollout_noise<M>(h, a) : launch_policy_rollout<M>(h, a);
+  }
   return launch_entry<REGULAR, LIMITED, BATCH, BATCH_LIMITED>(h, mode, kargs);
 }
 }  // namespace mi_host

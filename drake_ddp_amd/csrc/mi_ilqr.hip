@@ -65,7 +65,7 @@ Model builtin(int family, size_t (*lds)(int32_t, int32_t), int (*launch)(mi_ilqr
   return r;
 }
 // wave-per-problem kernels (k_<model>.hip, k_<model>_lim.hip) and the lane-per-problem ones (k_batch.hip, k_batch_lim.hip); every
-// model's policy-rollout kernels are in k_policy.hip
+// model's policy-rollout kernels are in k_policy.hip and, with noise, k_policy_noise.hip
 template <class M>
 Model wave_model(std::initializer_list<double> defaults) {
   return builtin<M>(0, wave_lds<M::n, M::m>,
@@ -635,6 +635,7 @@ RowField row_field(mi_ilqr* h, int which) {
     case MI_F_TARGET_STEP: return {&h->target_steps, nullptr};
     case MI_F_MODEL_PARAMS: return {&h->params, h->d.model_params};
     case MI_F_COST_MATRICES: return {&h->costs, h->h_costmat.data()};
+    case MI_F_POLICY_NOISE: return {&h->policy_noise, nullptr};        // (not set: no noise, zeros)
   }
   return {nullptr, nullptr};
 }
@@ -952,6 +953,7 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   h->targets.width = h->target_steps.width = h->lane_targets.width = h->n;
   h->params.width = model.n_params;
   h->costs.width = cost_len(h);
+  h->policy_noise.width = h->n + h->m;
   h->params.batch_minor_copy = h->costs.batch_minor_copy = batch_minor;   // (what the lane kernels read batch-minor: KArgs::param_cols, cost_cols)
   const int rc = create_resources(h, lxu_hbm);
   if (rc != MI_ILQR_OK) { mi_ilqr_destroy(h); return rc; }
@@ -1051,6 +1053,37 @@ static int set_model_params(mi_ilqr* h, const double* src, size_t bytes) {
   if (!src) return MI_ILQR_E_BAD_ARG;
   for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(src[i])) return MI_ILQR_E_BAD_ARG;
   return store_upload(h, h->params, src);
+}
+
+// The disturbances of mi_ilqr_policy_rollout.  MI_F_POLICY_NOISE: (B, n + m) rows sigma_x | sigma_u, standard deviations - finite
+// and non-negative, zero on the padding controls; src == NULL with bytes == 0: no noise, the noise-free kernels again.
+// MI_F_POLICY_STREAM: seed | first_sample | common as doubles holding integers.  A refused call changes nothing.
+static int set_policy_noise(mi_ilqr* h, const double* src, size_t bytes) {
+  const size_t w = h->policy_noise.width, cnt = (size_t)h->B * w;
+  if (!src && bytes == 0) { store_drop(h->policy_noise); return MI_ILQR_OK; }
+  if (bytes != cnt * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  const int m_user = model_of(h->d.model_id)->p.m_user;
+  const size_t first_pad = (size_t)h->n + (m_user > 0 ? (size_t)m_user : (size_t)h->m);
+  for (size_t i = 0; i < cnt; ++i) {
+    if (!std::isfinite(src[i]) || src[i] < 0.0) return MI_ILQR_E_BAD_ARG;
+    if (i % w >= first_pad && src[i] != 0.0) return MI_ILQR_E_BAD_ARG;
+  }
+  return store_upload(h, h->policy_noise, src);
+}
+
+static int set_policy_stream(mi_ilqr* h, const double* src, size_t bytes) {
+  if (bytes != 3 * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  const double seed = src[0], first = src[1], common = src[2];
+  // (the comparisons are false for a NaN; an integer below 2^53 is exact in a double)
+  if (!(seed >= 0.0 && seed < 0x1p53 && seed == std::floor(seed))) return MI_ILQR_E_BAD_ARG;
+  if (!(first >= 0.0 && first < 0x1p32 && first == std::floor(first))) return MI_ILQR_E_BAD_ARG;
+  if (!(common == 0.0 || common == 1.0)) return MI_ILQR_E_BAD_ARG;
+  h->policy_seed = (unsigned long long)seed;
+  h->policy_first_sample = (uint32_t)first;
+  h->policy_common = common == 1.0;
+  return MI_ILQR_OK;
 }
 
 // The cost class of one set of matrices, cm = Q | R | Qf (mi_ilqr_set_cost and every row of MI_F_COST_MATRICES decide it here):
@@ -1485,6 +1518,8 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
   const size_t B = h->B, n = h->n, m = h->m, N = h->N, np = model->p.n_params, Sz = (size_t)S, W = n + m + m * n;
   if (params && np == 0) return MI_ILQR_E_UNSUPPORTED;
   if (params) for (size_t i = 0; i < B * Sz * np; ++i) if (!std::isfinite(params[i])) return MI_ILQR_E_BAD_ARG;
+  const bool noisy = h->policy_noise.synced;
+  if (noisy && (unsigned long long)h->policy_first_sample + (unsigned long long)S > 0x100000000ull) return MI_ILQR_E_BAD_ARG;   // (the sample counter is 32 bits)
   HIPCHK(hipSetDevice(h->d.device_id));
   // one block of the handle's grow-only scratch, in doubles: the policy's time-major copy | inputs as they arrive and sample-minor |
   // outputs sample-minor and in the boundary's layout
@@ -1532,6 +1567,8 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
   a.cost = rows_or(h->costs, h->costmat, &a.cost_stride);
   a.x_nom = rows_or(h->targets, h->costmat + cost_len(h), &a.x_nom_stride);
   a.ulim = h->limited ? h->ulim : nullptr;
+  a.noise = noisy ? h->policy_noise.rows : nullptr;
+  a.seed = h->policy_seed; a.first_sample = h->policy_first_sample; a.common = h->policy_common ? 1 : 0;
   a.cost_out = sc + o_cost; a.x_final = sc + o_xf; a.steps = reinterpret_cast<int32_t*>(sc + o_steps);
   a.X = X ? sc + o_X : nullptr; a.U = U ? sc + o_U : nullptr;
   a.dt = h->d.dt; a.N = (int32_t)N; a.S = S; a.B = (int32_t)B; a.m_user = model->p.m_user > 0 ? model->p.m_user : (int32_t)m;
@@ -1680,6 +1717,11 @@ int mi_ilqr_get_mpc_log(mi_ilqr_t* h, double* dst, size_t bytes) {
 int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
   if (const RowField r = row_field(h, which); r.store) return store_read(h, *r.store, r.shared_row, dst, bytes);   // (host mirrors)
+  if (which == MI_F_POLICY_STREAM) {
+    if (bytes != 3 * 8) return MI_ILQR_E_BAD_SHAPE;
+    dst[0] = (double)h->policy_seed; dst[1] = (double)h->policy_first_sample; dst[2] = h->policy_common ? 1.0 : 0.0;
+    return MI_ILQR_OK;
+  }
   if (which == MI_F_POLICY_KERNEL_MS) {        // the rollout kernel of the last mi_ilqr_policy_rollout, from its own events
     if (bytes != 8) return MI_ILQR_E_BAD_SHAPE;
     if (!h->policy_ran) return MI_ILQR_E_BAD_ARG;
@@ -1759,6 +1801,8 @@ int mi_ilqr_get_int(mi_ilqr_t* h, int which, int32_t* dst, size_t bytes) {
 int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
   if (h && which == MI_F_MODEL_PARAMS) return set_model_params(h, src, bytes);   // (src == NULL, bytes == 0: back to shared mode)
   if (h && which == MI_F_COST_MATRICES) return set_cost_rows(h, src, bytes);     // (the same)
+  if (h && which == MI_F_POLICY_NOISE) return set_policy_noise(h, src, bytes);   // (src == NULL, bytes == 0: no noise)
+  if (h && which == MI_F_POLICY_STREAM) return set_policy_stream(h, src, bytes);
   if (!h || !src) return MI_ILQR_E_BAD_ARG;
   if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return set_target_field(h, which, src, bytes);
   Field f = field_of(h, which);

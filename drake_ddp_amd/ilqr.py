@@ -90,6 +90,54 @@ def check_rollout_args(x0, params, B, n, n_params):
     return np.ascontiguousarray(x0), params
 
 
+def check_noise_args(state_noise, control_noise, seed, first_sample, common_noise, B, n, m, m_dev=None, S=None):
+    """RolloutPolicy's disturbance arguments -> (rows, stream): rows is None when both sigmas are None (no noise), else the
+    contiguous (B, n + m_dev) float64 array sigma_x | sigma_u with zeros on the padding controls (m_dev: the device's number of
+    controls, default m); stream is the float64 triple seed | first_sample | common.  state_noise: scalar, (n,) or (B, n);
+    control_noise: scalar, (m,) or (B, m); one of them None: zeros.  ValueError - decided here, before anything reaches the device -
+    for any other shape, a negative, NaN or infinite sigma, a seed that is no integer in [0, 2^53), a first_sample that is no integer
+    in [0, 2^32) or - S given - with first_sample + S > 2^32."""
+    m_dev = m if m_dev is None else int(m_dev)
+
+    def integer(v, name, bound, what):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer, float, np.floating)):
+            raise ValueError(f"RolloutPolicy: {name} must be an integer in [0, {what}); got {v!r}")
+        if isinstance(v, (float, np.floating)) and not (np.isfinite(v) and v == np.floor(v)):
+            raise ValueError(f"RolloutPolicy: {name} must be an integer in [0, {what}); got {v!r}")
+        v = int(v)
+        if not 0 <= v < bound:
+            raise ValueError(f"RolloutPolicy: {name} must be an integer in [0, {what}); got {v}")
+        return v
+
+    seed = integer(seed, "seed", 1 << 53, "2^53")
+    first_sample = integer(first_sample, "first_sample", 1 << 32, "2^32")
+    if S is not None and first_sample + int(S) > (1 << 32):
+        raise ValueError(f"RolloutPolicy: first_sample + S must not exceed 2^32; got {first_sample} + {int(S)}")
+    stream = np.array([seed, first_sample, 1.0 if common_noise else 0.0], dtype=np.float64)
+    if state_noise is None and control_noise is None:
+        return None, stream
+
+    def sigma(v, k, name):
+        if v is None:
+            return np.zeros((B, k))
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"RolloutPolicy: {name} is not an array of numbers ({e})") from None
+        if a.shape not in ((), (k,), (B, k)):
+            raise ValueError(f"RolloutPolicy: {name} must be a scalar, ({k},) or ({B}, {k}); got {a.shape}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"RolloutPolicy: NaN or infinity in {name}")
+        if (a < 0.0).any():
+            raise ValueError(f"RolloutPolicy: negative entry in {name} (standard deviations)")
+        return np.broadcast_to(a, (B, k))
+
+    rows = np.zeros((B, n + m_dev))
+    rows[:, :n] = sigma(state_noise, n, "state_noise")
+    rows[:, n:n + m] = sigma(control_noise, m, "control_noise")
+    return rows, stream
+
+
 class PolicyRollout:
     """What RolloutPolicy returns: cost, x_final, steps and - asked for - the trajectories X, U (else None)."""
     __slots__ = ("cost", "x_final", "steps", "X", "U")
@@ -659,16 +707,32 @@ class BatchedIterativeLQR:
         _capi.check(self._lib.mi_ilqr_backward(self._h), "mi_ilqr_backward")
 
     # ------------------------------------------------------------- Monte-Carlo rollouts of the policy
-    def RolloutPolicy(self, x0, params=None, trajectories=False):
+    def RolloutPolicy(self, x0, params=None, trajectories=False, *, state_noise=None, control_noise=None, seed=0, first_sample=0,
+                      common_noise=False):
         """Roll out S samples per problem under the policy the solver holds - u = u_bar - K (x - x_bar), the reason SaveSolution
         stores K (ilqr.py:712-733) - one GPU lane per sample, in one call (include/mi_ilqr.h: mi_ilqr_policy_rollout).
         x0: (B, S, n), or (S, n) for every problem.  params: None - each problem's own plant - or (B, S, n_params) / (S, n_params),
         a plant per sample.  Costs, targets and control limits are the solver's, per-problem where set.  Returns a PolicyRollout:
         cost (B, S) - +inf for a sample that ended at an infeasible or non-finite step -, x_final (B, S, n), steps (B, S) and, with
         trajectories=True, X (B, S, n, N) and U (B, S, m, N-1) with NaN in the columns a sample did not reach.  Changes nothing in
-        the solver: a Solve() after the call is the Solve() without it."""
+        the solver: a Solve() after the call is the Solve() without it.
+        state_noise (scalar, (n,) or (B, n)) and control_noise (scalar, (m,) or (B, m)): standard deviations of a disturbance at every
+        step, x_{t+1} = f(x_t, u_t + sigma_u xi) + sigma_x xi' with independent standard normals generated on the device - U and the
+        cost keep the commanded u_t, X holds the noisy states.  A normal depends on (seed, problem, first_sample + sample, step,
+        component) only: the same seed gives the same rollouts, S samples from first_sample = k are samples k .. k + S - 1 of one
+        long call, common_noise=True gives every problem the same disturbances.  Both None: no noise, today's kernel."""
         x0, params = check_rollout_args(x0, params, self.B, self.n, int(self.system.params.size))
+        noisy = state_noise is not None or control_noise is not None
+        rows, stream = check_noise_args(state_noise, control_noise, seed, first_sample, common_noise, self.B, self.n, self.m,
+                                        self._md if noisy else None, x0.shape[1] if noisy else None)
         self._push_costs()
+        if rows is not None:
+            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_STREAM, _capi.ptr(stream), stream.nbytes), "mi_ilqr_set")
+            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_NOISE, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
+            self._policy_noise_set = True
+        elif getattr(self, "_policy_noise_set", False):
+            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_NOISE, None, 0), "mi_ilqr_set")
+            self._policy_noise_set = False
         B, S = self.B, x0.shape[1]
         cost, x_final, steps = np.empty((B, S)), np.empty((B, S, self.n)), np.empty((B, S), dtype=np.int32)
         X = np.empty((B, S, self.n, self.N)) if trajectories else None
@@ -819,11 +883,14 @@ class IterativeLinearQuadraticRegulator(BatchedIterativeLQR):
             return res[0].reshape(self.n, self.N), res[1][0], total_time, float(res[2][0])
         return self.x_bar, self.u_bar, total_time, float(self.cost[0])
 
-    def RolloutPolicy(self, x0, params=None, trajectories=False):
-        """x0 (S, n), params None or (S, n_params): cost (S,), x_final (S, n), steps (S,)[, X (S, n, N), U (S, m, N-1)]."""
+    def RolloutPolicy(self, x0, params=None, trajectories=False, *, state_noise=None, control_noise=None, seed=0, first_sample=0,
+                      common_noise=False):
+        """x0 (S, n), params None or (S, n_params): cost (S,), x_final (S, n), steps (S,)[, X (S, n, N), U (S, m, N-1)].
+        state_noise scalar or (n,), control_noise scalar or (m,), seed, first_sample, common_noise: BatchedIterativeLQR.RolloutPolicy."""
         if np.ndim(x0) != 2:
             raise ValueError(f"RolloutPolicy: x0 must be (S, {self.n}); got {np.shape(x0)}")
-        return super().RolloutPolicy(x0, params, trajectories)._without_batch_axis()
+        return super().RolloutPolicy(x0, params, trajectories, state_noise=state_noise, control_noise=control_noise, seed=seed,
+                                     first_sample=first_sample, common_noise=common_noise)._without_batch_axis()
 
     def SaveSolution(self, fname):
         """ilqr.py:712-733: npz with t, x_bar (last step dropped), u_bar, K."""

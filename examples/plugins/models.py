@@ -11,6 +11,8 @@
   chainx   any (n, m)     nq coupled pendula with the last m actuated + ne first-order "filter" states (n = 2 nq + ne): the
                          mid-size workgroup-per-problem family (n <= 32, any m <= 16) at whatever shape a test asks for -
                          (12, 4) a quadrotor's, (14, 7) a 7-joint arm's, (27, 7) kinova_gen3.py's arm + free body
+  noiseprobe n = 40, m = 16 a plant that forgets its state and passes its inputs through: under RolloutPolicy's state_noise /
+                         control_noise the trajectory IS the random stream (tests/test_gpu_policy_noise.py reads the generator so)
 """
 import os
 import sys
@@ -133,6 +135,13 @@ PADDED_SHAPES = [(18, 7, 0), (16, 3, 5)]
 LARGE_SHAPES = [(18, 4, 0), (18, 8, 0), (20, 4, 0), (20, 8, 0), (17, 4, 1), (19, 8, 0), (19, 12, 1), (16, 16, 1), (18, 16, 0), (20, 16, 0)]
 
 
+# x_{t+1}[i] = 0 x_t[i] + u_t[i] (i < 16): with a zero policy, a rollout with control noise shows the control stream in the first 16
+# states, one with state noise the state stream in all 40 - ten Philox blocks per step, the widest a model of the library can ask for.
+NOISEPROBE_BODY = """    for (int i = 0; i < 40; ++i) xn[i] = 0.0 * x[i];
+    for (int i = 0; i < 16; ++i) xn[i] = xn[i] + u[i];"""
+NOISEPROBE_SPEC = ("noiseprobe", 40, 16, NOISEPROBE_BODY, [], "large")
+
+
 def chain_spec(nq):
     return ("chain%d" % nq, 2 * nq, 12, chain_body(nq), CHAIN_DEFAULTS, "large")
 
@@ -148,7 +157,7 @@ def build_all(verbose=False):
     specs = [("vdp", 2, 1, VDP_BODY, VDP_DEFAULTS, "small"), ("kink2", 2, 1, KINK2_BODY, KINK2_DEFAULTS, "small"),
              ("chain3", 6, 2, CHAIN3_BODY, CHAIN3_DEFAULTS, "small"),
              ("synth36p", 36, 12, SYNTH36P_BODY, SYNTH36P_DEFAULTS, "large"), chain_spec(17), chain_spec(20)]
-    specs += [chainx_spec(*sh) for sh in CHAINX_SHAPES + PADDED_SHAPES + LARGE_SHAPES + FAST_STEP_SHAPES]
+    specs += [chainx_spec(*sh) for sh in CHAINX_SHAPES + PADDED_SHAPES + LARGE_SHAPES + FAST_STEP_SHAPES] + [NOISEPROBE_SPEC]
     return plugin.build_models(specs, verbose=verbose)
 
 

@@ -125,6 +125,8 @@ enum {
   MI_F_MODEL_PARAMS = 16,/* (B,n_params) per-problem model parameters: problem b's plant ("Per-problem model parameters" below) */
   MI_F_COST_MATRICES = 17,/* (B,2*n*n+m*m) per-problem cost matrices, row b = Q_b | R_b | Qf_b ("Per-problem cost matrices" below) */
   MI_F_POLICY_KERNEL_MS = 18,/* (1,) read-only: milliseconds of the rollout kernel of the last policy rollout, from its own HIP events (mi_ilqr_policy_rollout) */
+  MI_F_POLICY_NOISE = 19,    /* (B,n+m) per-problem standard deviations sigma_x | sigma_u of the policy rollouts' disturbances ("Process and actuation noise" below) */
+  MI_F_POLICY_STREAM = 20,   /* (3,) seed | first_sample | common of the disturbances' random stream, integers held in doubles (the same) */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
@@ -509,6 +511,33 @@ size_t mi_ilqr_lds_bytes(const mi_ilqr_desc* desc);
  * MI_ILQR_E_UNSUPPORTED; a NaN or an infinity in params MI_ILQR_E_BAD_ARG.  Every model and kernel family (additive in ABI 10). */
 int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const double* params, double* cost, double* x_final,
                            int32_t* steps, double* X, double* U);
+
+/* Process and actuation noise of the policy rollouts (additive in ABI 10: two selectors of mi_ilqr_set / mi_ilqr_get, no new entry
+ * point).  On a handle that holds a MI_F_POLICY_NOISE array every step of mi_ilqr_policy_rollout is disturbed:
+ *     u_t     = u_bar_t - K_t (x_t - x_bar_t)                       clamped on a limited handle, as above: the COMMANDED control
+ *     x_{t+1} = f(x_t, u_t + sigma_u o xi^u_t) + sigma_x o xi^x_t    xi: independent standard normals, o: component by component
+ *     L      += (x_t - x_nom)' Q (x_t - x_nom) + u_t' R u_t          with the commanded u_t
+ * U holds the commanded controls, X the noisy states.  The disturbance on u is added after the clamp and is not clamped again (an
+ * external disturbance, not a command).  The finite and infeasible checks look at the noisy x_{t+1}; ended samples, steps, x_final
+ * and the NaN columns are as above.  x0 gets no noise; padding controls get none and stay exact zeros.
+ *   mi_ilqr_set(MI_F_POLICY_NOISE, rows, B*(n+m)*8)  row b = sigma_x (n) | sigma_u (m, the DEVICE's number of controls) of problem b:
+ *                                            standard deviations, zero where a component is to get no noise.  Survives mi_ilqr_reset.
+ *   mi_ilqr_set(MI_F_POLICY_NOISE, NULL, 0)  clears it: the next rollout runs the noise-free kernel again, bitwise as before it was set.
+ *   mi_ilqr_set(MI_F_POLICY_STREAM, v, 24)   v = seed | first_sample | common, each an integer value: seed in [0, 2^53), first_sample
+ *                                            in [0, 2^32), common 0 or 1.  Default 0 | 0 | 0.
+ *   mi_ilqr_get reads both back; MI_F_POLICY_NOISE reads as zeros while it is not set.
+ * Errors: a negative, NaN or infinite sigma, a non-zero sigma on a padding control, a stream value that is not such an integer:
+ * MI_ILQR_E_BAD_ARG; wrong `bytes`: MI_ILQR_E_BAD_SHAPE; a refused call changes nothing.  A rollout with noise set and
+ * first_sample + S > 2^32: MI_ILQR_E_BAD_ARG.
+ * The generator is counter-based: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) with
+ *     key     = (seed mod 2^32, seed div 2^32)
+ *     counter = (first_sample + s, t, common ? 0 : b, j)     j = i / 4 for state component i, j = 256 + k / 4 for control component k
+ * and the normal of a component is made from word (i mod 4) of block j by Box-Muller: words (w0, w1) give u_a = (w0 + 1/2) 2^-32,
+ * u_b = (w1 + 1/2) 2^-32, z0 = r cos(2 pi u_b), z1 = r sin(2 pi u_b) with r = sqrt(-2 ln u_a); words (w2, w3) give z2, z3 the same
+ * way (|z| <= 6.77).  So a normal depends on (seed, b, s, t, component) only - not on S, not on the model, not on how the samples
+ * are spread over calls: S samples from first_sample = k are samples k .. k + S - 1 of one long call, and common = 1 gives every
+ * problem the same disturbances (common random numbers).  The handle stays read-only for solves: a solve after a noisy rollout is
+ * bitwise the solve without it. */
 
 #ifdef __cplusplus
 }

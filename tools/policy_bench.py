@@ -2,7 +2,7 @@
 only equivalent the library offered before it: a (B S)-problem handle with the policy replicated by set_state and one
 stage_rollout(0.0).
 
-    python tools/policy_bench.py [--reps R] [--warmup W] [--configs pendulum,quad3d] [--samples 64,1024] [--emulate-up-to P]
+    python tools/policy_bench.py [--reps R] [--warmup W] [--configs pendulum,quad3d] [--samples 64,1024] [--emulate-up-to P] [--noise]
 
 Shapes: pendulum B = 1024, N = 200; Quad3D B = 64, N = 40; each at S = 64 and S = 1024 samples per problem.  The policy is what a
 capped solve leaves on the handle; the samples are the problems' own x0 plus seeded perturbations (all rollouts run to the end).
@@ -10,7 +10,9 @@ Both paths are timed with HIP events around their ONE kernel (policy_kernel_ms /
 median and the min .. max spread; sample-steps/s = B S (N - 1) / kernel time.  The emulation's handle holds the whole solver state
 of B S problems (fx alone is B S n^2 (N-1) doubles: 27 GB for Quad3D at S = 1024, which still runs), so it runs where B S <=
 --emulate-up-to (default 65536: everything but the pendulum at S = 1024, a 1 M-problem handle) - the rates are per sample-step and
-compare across S.  Prints one JSON line."""
+compare across S.  --noise: the same rollouts again with process and actuation noise (state_noise / control_noise: the noisy
+kernels of csrc/policy_rollout.hpp, a Philox block and its Box-Muller normals per four components and step) and the ratio of the
+two kernel times.  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -30,6 +32,15 @@ def problem(config):
         return p, B, W.quad3d_batch_x0(B), W.quad3d_u_guess(40), 1e-3
     p, B = W.pendulum_problem(), 1024
     return p, B, W.pendulum_batch_x0(B), np.zeros((1, p["N"] - 1)), 0.05
+
+
+def noise(config, n):
+    """sigma_x (n,), sigma_u: about 1e-3 of the state scale and 1e-2 of the control scale; the quadruped's attitude quaternion gets none"""
+    if config == "quad3d":
+        sx = np.full(n, 1e-3)
+        sx[:4] = 0.0
+        return sx, 5e-2
+    return np.full(n, 3e-3), 1e-2
 
 
 def solver(p, B, **kw):
@@ -54,6 +65,7 @@ def main():
     ap.add_argument("--configs", default="pendulum,quad3d")
     ap.add_argument("--samples", default="64,1024")
     ap.add_argument("--emulate-up-to", type=int, default=65536)
+    ap.add_argument("--noise", action="store_true")
     a = ap.parse_args()
     out = {}
     for config in a.configs.split(","):
@@ -75,6 +87,15 @@ def main():
                 if i >= a.warmup:
                     ms.append(s.policy_kernel_ms())
             res = dict(B=B, S=S, N=N, full_rollouts=int((r.steps == N - 1).sum()), policy_rollout=summary(ms, work))
+            if a.noise:
+                sx, su = noise(config, n)
+                ms_n = []
+                for i in range(a.warmup + a.reps):
+                    rn = s.RolloutPolicy(x0, state_noise=sx, control_noise=su, seed=S)
+                    if i >= a.warmup:
+                        ms_n.append(s.policy_kernel_ms())
+                res["policy_rollout_noise"] = dict(summary(ms_n, work), full_rollouts=int((rn.steps == N - 1).sum()))
+                res["noise_slowdown"] = res["policy_rollout_noise"]["kernel_ms"] / res["policy_rollout"]["kernel_ms"]
             if B * S <= a.emulate_up_to:
                 e = solver(p, B * S)
                 e.set_state(**{k: np.repeat(v, S, axis=0) for k, v in pol.items()})
