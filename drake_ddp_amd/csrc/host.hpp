@@ -18,7 +18,7 @@
 #define MI_INTERNAL __attribute__((visibility("hidden")))
 
 // One per-problem (B, width) array of a handle (mi_ilqr_set MI_F_X_NOM / MI_F_TARGET_STEP / MI_F_MODEL_PARAMS / MI_F_COST_MATRICES /
-// MI_F_POLICY_NOISE;
+// MI_F_POLICY_NOISE / MI_F_PLANT_STATE / MI_F_PLANT_PARAMS / MI_F_PLANT_NOISE;
 // mi_ilqr.hip: store_upload / store_drop / store_read).  The host mirror is the truth: what mi_ilqr_get returns without touching the
 // stream and what mi_ilqr_mpc_run advances; the device copies follow it on the handle's stream.  `synced` - they equal it - is the
 // array's per-problem mode: only then do the kernels get the pointers, a failed copy leaves the mode, and rows the caller repeats
@@ -130,6 +130,19 @@ struct mi_ilqr {
   unsigned long long policy_seed = 0;
   uint32_t policy_first_sample = 0;
   bool policy_common = false;
+  // the plant of the closed receding-horizon loop (mi_ilqr_mpc_run; plant_advance.hpp).  plant_state: (B, n), `synced` = the handle
+  // holds a plant - its device rows ARE the plant (the kernel advances them in place, mi_ilqr_mpc_run brings the mirror up to date);
+  // plant_params: (B, n_params), not synced = every plant runs on its problem's model row; plant_noise: (B, n + m) sigma_x | sigma_u,
+  // `synced` selects the noisy kernels.  Problem data like the policy's: mi_ilqr_reset keeps them.
+  RowStore plant_state, plant_params, plant_noise;
+  unsigned long long plant_seed = 0, plant_clock = 0;   // MI_F_PLANT_STREAM: seed | clock | common | feedback
+  bool plant_common = false, plant_feedback = true;
+  double* plant_dead = nullptr;    // (B,): 1.0 = the plant has ended (until MI_F_PLANT_STATE is set again)
+  double* plant_log = nullptr;     // (rows, n + m + 1, B) problem-minor: x_k | u_k | l_k of the last closed-loop run (grow-only)
+  size_t plant_log_cap = 0;        // ... its capacity in doubles
+  int plant_log_rows = 0;          // ... and the rows that run wrote (0: no such run yet)
+  hipEvent_t plant_ev0 = nullptr, plant_ev1 = nullptr;   // the plant kernel's own event pair (MI_F_PLANT_KERNEL_MS)
+  double plant_ms = 0.0;           // summed over the plant kernels of the last closed-loop run
 };
 
 // Run-time switches for A/B runs (README): the environment is read once per process.
@@ -193,6 +206,9 @@ constexpr int kModeProbeLimits = 0x4c494d;
 // mi_ilqr_policy_rollout: the launch entry takes a PolicyArgs (below), not a KArgs, and launches policy_rollout_kernel<M>
 // (policy_rollout.hpp) whatever kernel family serves the handle's solves.
 constexpr int kModePolicyRollout = 0x504f4c;
+// mi_ilqr_mpc_run on a handle that holds a plant: the launch entry takes a PlantArgs (below) and launches plant_advance_kernel<M>
+// (plant_advance.hpp), again whatever the handle's kernel family.
+constexpr int kModePlantAdvance = 0x504c54;
 constexpr int kMaxBatchPluginN = 6;      // family-0 models up to this n also get the lane-per-problem kernels
 
 // The dynamic-LDS ceiling of a kernel is raised once per (kernel, device), to the hardware maximum - not
@@ -281,6 +297,26 @@ struct PolicyArgs {
 template <class M> MI_INTERNAL int launch_policy_rollout(mi_ilqr* h, const PolicyArgs& a);          // policy_rollout.hpp; k_policy.hip
 template <class M> MI_INTERNAL int launch_policy_rollout_noise(mi_ilqr* h, const PolicyArgs& a);    // ... k_policy_noise.hip
 
+// Arguments of plant_advance_kernel<M> (plant_advance.hpp), all device pointers.  "Problem-minor": element e of problem b at e * B + b.
+struct PlantArgs {
+  const double* policy;       // (steps, n + m + m n, B) problem-minor: row j = x_bar_j | u_bar_j | K_j (m x n, row-major), the first `steps` columns
+  const double* params;       // (n_params, B) problem-minor: the plants' parameters
+  const double* cost;         // (n n + m m, B) problem-minor: Q_b | R_b
+  const double* x_nom;        // (n, B) problem-minor
+  const double* ulim;         // (2 m, B) problem-minor u_min | u_max, or nullptr: no clamp
+  const double* noise;        // (n + m, B) problem-minor sigma_x | sigma_u (MI_F_PLANT_NOISE), or nullptr: the noise-free kernels
+  double* x;                  // (B, n): the plants' states, advanced in place
+  double* dead;               // (B,): 1.0 = the plant has ended; read and written
+  double* mpc_dead;           // (B,): the MPC log's flags (mpc_log_fill_kernel), set for a plant that has ended
+  double* log;                // (steps, n + m + 1, B) problem-minor: this launch's rows x_k | u_k | l_k
+  double dt;
+  unsigned long long seed;    // MI_F_PLANT_STREAM: the Philox key
+  uint32_t clock;             // ... and the plant clock of this launch's first step
+  int32_t B, steps, m_user, feedback, common;   // m_user: controls m_user .. m-1 are padding and stay exact zeros
+};
+template <class M> MI_INTERNAL int launch_plant_advance(mi_ilqr* h, const PlantArgs& a);            // plant_advance.hpp; k_plant.hip
+template <class M> MI_INTERNAL int launch_plant_advance_noise(mi_ilqr* h, const PlantArgs& a);      // ... k_plant_noise.hip
+
 // The launch entry of a model's record (mi_ilqr_model_plugin::launch), built-in or plugin: the handle picks the kernel set - the
 // lane-per-problem kernels (h->batch_minor), the Limited<M> ones (h->limited), else the regular ones.  A set the model lacks is
 // nullptr; the probe (kModeProbeLimits) answers whether it has Limited<M> kernels, launching nothing.
@@ -295,12 +331,17 @@ int launch_entry(mi_ilqr* h, int mode, const void* kargs) {
   if constexpr (LIMITED != nullptr) if (h->limited) return LIMITED(h, mode, a);
   return REGULAR(h, mode, a);
 }
-// ... and the same for model M with the policy rollout (kModePolicyRollout), which is one kernel per model whatever the handle's family
+// ... and the same for model M with the policy rollout (kModePolicyRollout) and the plant of the closed MPC loop (kModePlantAdvance),
+// each one kernel per model whatever the handle's family
 template <class M, Launcher REGULAR, Launcher LIMITED = nullptr, Launcher BATCH = nullptr, Launcher BATCH_LIMITED = nullptr>
 int model_entry(mi_ilqr* h, int mode, const void* kargs) {
   if (mode == kModePolicyRollout) {
     const PolicyArgs& a = *static_cast<const PolicyArgs*>(kargs);
     return a.noise ? launch_policy_rollout_noise<M>(h, a) : launch_policy_rollout<M>(h, a);
+  }
+  if (mode == kModePlantAdvance) {
+    const PlantArgs& a = *static_cast<const PlantArgs*>(kargs);
+    return a.noise ? launch_plant_advance_noise<M>(h, a) : launch_plant_advance<M>(h, a);
   }
   return launch_entry<REGULAR, LIMITED, BATCH, BATCH_LIMITED>(h, mode, kargs);
 }

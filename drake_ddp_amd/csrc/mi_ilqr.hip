@@ -429,6 +429,44 @@ __global__ void __launch_bounds__(256) policy_pack_kernel(const double* __restri
   }
 }
 
+// The closed MPC loop's plant (plant_advance.hpp: a lane is a problem) reads everything PROBLEM-MINOR, element e of problem b at
+// e * B + b.  plant_pack_kernel: the first `steps` columns of the policy, (steps, W, B) with row j = x_bar_j | u_bar_j | K_j, gathered
+// from the handle's kernel layout like policy_pack_kernel does (a source that is nullptr reads as zeros); the writes are coalesced.
+__global__ void __launch_bounds__(256) plant_pack_kernel(const double* __restrict__ x_bar, const double* __restrict__ u_bar,
+                                                           const double* __restrict__ K, double* __restrict__ dst,
+                                                           int B, int n, int m, int N, int steps, int layout) {
+  const int W = n + m + m * n, M1 = N - 1;
+  const size_t total = (size_t)steps * W * B;
+  auto at = [&](const double* f, int rows, int len, int b, int r, int t) -> double {
+    if (!f) return 0.0;
+    if (layout == LAYOUT_TL) return f[((size_t)b * rows + r) * len + t];
+    if (layout == LAYOUT_TM) return f[((size_t)b * len + t) * rows + r];
+    return f[((size_t)t * rows + r) * B + b];
+  };
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const int b = (int)(e % B);
+    const size_t jw = e / B;
+    const int w = (int)(jw % W), t = (int)(jw / W);
+    dst[e] = w < n ? at(x_bar, n, N, b, w, t) : (w < n + m ? at(u_bar, m, M1, b, w - n, t) : at(K, m * n, M1, b, w - n - m, t));
+  }
+}
+
+// ... and rows_to_cols_kernel: a per-problem array, `width` doubles of problem b at src + b * stride (stride 0: one row for every
+// problem), as (width, B)
+__global__ void __launch_bounds__(256) rows_to_cols_kernel(const double* __restrict__ src, size_t stride, double* __restrict__ dst,
+                                                             int width, int B) {
+  const size_t total = (size_t)width * B;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const size_t k = e / B, b = e - k * B;
+    dst[e] = src[b * stride + k];
+  }
+}
+
+// x0 <- the plants' states, on the device (dst may be the mapped host block of a tiny batch: host.hpp, host_inputs)
+__global__ void __launch_bounds__(256) copy_doubles_kernel(const double* __restrict__ src, double* __restrict__ dst, size_t count) {
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < count; e += (size_t)gridDim.x * 256) dst[e] = src[e];
+}
+
 // Batched (R x C) -> (C x R) transposes with pitches, 32 x 32 tiles through LDS so that reads and writes are both coalesced: matrix
 // z = (o, i), i < inner; element (r, c) is read at src[o src_outer + i src_inner + r src_r + c], written at dst[o dst_outer +
 // i dst_inner + c dst_c + r].  The sample-minor <-> boundary conversions of mi_ilqr_policy_rollout.  grid = (ceil(C/32), ceil(R/32), <= Z).
@@ -636,6 +674,9 @@ RowField row_field(mi_ilqr* h, int which) {
     case MI_F_MODEL_PARAMS: return {&h->params, h->d.model_params};
     case MI_F_COST_MATRICES: return {&h->costs, h->h_costmat.data()};
     case MI_F_POLICY_NOISE: return {&h->policy_noise, nullptr};        // (not set: no noise, zeros)
+    case MI_F_PLANT_STATE: return {&h->plant_state, nullptr};          // (mi_ilqr_get refuses it while the handle holds no plant)
+    case MI_F_PLANT_PARAMS: return {&h->plant_params, h->d.model_params};   // (not set: the problem's model row, get_plant_field)
+    case MI_F_PLANT_NOISE: return {&h->plant_noise, nullptr};
   }
   return {nullptr, nullptr};
 }
@@ -953,7 +994,9 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   h->targets.width = h->target_steps.width = h->lane_targets.width = h->n;
   h->params.width = model.n_params;
   h->costs.width = cost_len(h);
-  h->policy_noise.width = h->n + h->m;
+  h->policy_noise.width = h->plant_noise.width = h->n + h->m;
+  h->plant_state.width = h->n;
+  h->plant_params.width = model.n_params;
   h->params.batch_minor_copy = h->costs.batch_minor_copy = batch_minor;   // (what the lane kernels read batch-minor: KArgs::param_cols, cost_cols)
   const int rc = create_resources(h, lxu_hbm);
   if (rc != MI_ILQR_OK) { mi_ilqr_destroy(h); return rc; }
@@ -976,6 +1019,8 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
   if (h->pin_ev) (void)hipEventDestroy(h->pin_ev);
   if (h->policy_ev0) (void)hipEventDestroy(h->policy_ev0);
   if (h->policy_ev1) (void)hipEventDestroy(h->policy_ev1);
+  if (h->plant_ev0) (void)hipEventDestroy(h->plant_ev0);
+  if (h->plant_ev1) (void)hipEventDestroy(h->plant_ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1058,9 +1103,10 @@ static int set_model_params(mi_ilqr* h, const double* src, size_t bytes) {
 // The disturbances of mi_ilqr_policy_rollout.  MI_F_POLICY_NOISE: (B, n + m) rows sigma_x | sigma_u, standard deviations - finite
 // and non-negative, zero on the padding controls; src == NULL with bytes == 0: no noise, the noise-free kernels again.
 // MI_F_POLICY_STREAM: seed | first_sample | common as doubles holding integers.  A refused call changes nothing.
-static int set_policy_noise(mi_ilqr* h, const double* src, size_t bytes) {
-  const size_t w = h->policy_noise.width, cnt = (size_t)h->B * w;
-  if (!src && bytes == 0) { store_drop(h->policy_noise); return MI_ILQR_OK; }
+// (the same rows and rules serve the plant of the closed MPC loop: MI_F_PLANT_NOISE, a store of its own)
+static int set_noise_rows(mi_ilqr* h, RowStore& store, const double* src, size_t bytes) {
+  const size_t w = store.width, cnt = (size_t)h->B * w;
+  if (!src && bytes == 0) { store_drop(store); return MI_ILQR_OK; }
   if (bytes != cnt * 8) return MI_ILQR_E_BAD_SHAPE;
   if (!src) return MI_ILQR_E_BAD_ARG;
   const int m_user = model_of(h->d.model_id)->p.m_user;
@@ -1069,7 +1115,48 @@ static int set_policy_noise(mi_ilqr* h, const double* src, size_t bytes) {
     if (!std::isfinite(src[i]) || src[i] < 0.0) return MI_ILQR_E_BAD_ARG;
     if (i % w >= first_pad && src[i] != 0.0) return MI_ILQR_E_BAD_ARG;
   }
-  return store_upload(h, h->policy_noise, src);
+  return store_upload(h, store, src);
+}
+
+// The plant of the closed MPC loop (mi_ilqr_mpc_run; plant_advance.hpp).  MI_F_PLANT_STATE: (B, n) finite states - the handle holds
+// a plant from now on, and every plant is running again; src == NULL with bytes == 0: no plant, mi_ilqr_mpc_run is the open loop.
+// MI_F_PLANT_PARAMS: set_model_params' rules on the plants' own rows.  MI_F_PLANT_STREAM: seed | clock | common | feedback.
+// A refused call changes nothing.
+static int set_plant_state(mi_ilqr* h, const double* src, size_t bytes) {
+  const size_t cnt = (size_t)h->B * h->n;
+  if (!src && bytes == 0) { store_drop(h->plant_state); return MI_ILQR_OK; }
+  if (bytes != cnt * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(src[i])) return MI_ILQR_E_BAD_ARG;
+  HIPCHK(hipSetDevice(h->d.device_id));
+  int rc = h->plant_dead ? MI_ILQR_OK : dev_alloc(h, h->plant_dead, (size_t)h->B);
+  if (rc != MI_ILQR_OK) return rc;
+  HIPCHK(hipMemsetAsync(h->plant_dead, 0, (size_t)h->B * 8, h->stream));
+  return store_upload(h, h->plant_state, src);
+}
+
+static int set_plant_params(mi_ilqr* h, const double* src, size_t bytes) {
+  const size_t cnt = (size_t)h->B * h->plant_params.width;
+  if (cnt == 0) return MI_ILQR_E_UNSUPPORTED;
+  if (!src && bytes == 0) { store_drop(h->plant_params); return MI_ILQR_OK; }
+  if (bytes != cnt * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(src[i])) return MI_ILQR_E_BAD_ARG;
+  return store_upload(h, h->plant_params, src);
+}
+
+static int set_plant_stream(mi_ilqr* h, const double* src, size_t bytes) {
+  if (bytes != 4 * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  const double seed = src[0], clock = src[1], common = src[2], feedback = src[3];
+  if (!(seed >= 0.0 && seed < 0x1p53 && seed == std::floor(seed))) return MI_ILQR_E_BAD_ARG;
+  if (!(clock >= 0.0 && clock < 0x1p32 && clock == std::floor(clock))) return MI_ILQR_E_BAD_ARG;
+  if (!(common == 0.0 || common == 1.0) || !(feedback == 0.0 || feedback == 1.0)) return MI_ILQR_E_BAD_ARG;
+  h->plant_seed = (unsigned long long)seed;
+  h->plant_clock = (unsigned long long)clock;
+  h->plant_common = common == 1.0;
+  h->plant_feedback = feedback == 1.0;
+  return MI_ILQR_OK;
 }
 
 static int set_policy_stream(mi_ilqr* h, const double* src, size_t bytes) {
@@ -1631,10 +1718,90 @@ __global__ void __launch_bounds__(256) mpc_log_fill_kernel(const double* __restr
   if ((status[b] & ~MI_STATUS_FLAG_INDEFINITE) >= MI_STATUS_LINESEARCH_FAILED) dead[b] = 1.0;
 }
 
+// The closed loop's plant (a handle that holds MI_F_PLANT_STATE), the part of a mi_ilqr_mpc_run that does not change from one
+// re-solve to the next, staged problem-minor in the handle's scratch: the plants' parameters, Q | R, the bounds, the sigmas.
+// Offsets in doubles; `pol` and `x_nom` are filled before every launch (plant_advance).
+struct PlantStage { size_t pol, prm, prow, cost, x_nom, ulim, noise; };
+
+static int rows_to_cols(mi_ilqr* h, const double* src, size_t stride, double* dst, size_t width) {
+  const size_t total = width * (size_t)h->B;
+  if (total == 0) return MI_ILQR_OK;
+  hipLaunchKernelGGL(rows_to_cols_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, h->stream, src, stride, dst,
+                     (int)width, h->B);
+  HIPCHK(hipGetLastError());
+  return MI_ILQR_OK;
+}
+
+static int plant_prepare(mi_ilqr* h, int32_t num_resolves, int32_t replan_steps, PlantStage* st) {
+  const Model* model = model_of(h->d.model_id);
+  const size_t B = h->B, n = h->n, m = h->m, np = model->p.n_params, W = n + m + m * n, C = n + m + 1;
+  size_t off = 0;
+  auto take = [&](size_t count) { const size_t o = off; off += (count + 31) & ~(size_t)31; return o; };
+  st->pol = take((size_t)replan_steps * W * B); st->prm = take(np * B); st->prow = take(np); st->cost = take((n * n + m * m) * B);
+  st->x_nom = take(n * B); st->ulim = take(2 * m * B); st->noise = take((n + m) * B);
+  int rc = ensure_scratch(h, off * 8);
+  if (rc != MI_ILQR_OK) return rc;
+  const size_t need = (size_t)num_resolves * replan_steps * C * B;
+  if (h->plant_log_cap < need) {                 // grow-only
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->plant_log_cap = 0;
+    if ((rc = dev_free(h, h->plant_log)) != MI_ILQR_OK) return rc;
+    if ((rc = dev_alloc(h, h->plant_log, need)) != MI_ILQR_OK) return rc;
+    h->plant_log_cap = need;
+  }
+  if (!h->plant_ev0) {
+    HIPCHK(hipEventCreate(&h->plant_ev0));
+    HIPCHK(hipEventCreate(&h->plant_ev1));
+  }
+  double* const sc = h->scratch;
+  // the plants' parameters: their own rows, else the problems' model rows, else the descriptor's row for every problem
+  if (np) {
+    const RowStore& own = h->plant_params.synced ? h->plant_params : h->params;
+    if (own.synced) rc = rows_to_cols(h, own.rows, np, sc + st->prm, np);
+    else if ((rc = stage_h2d(h, sc + st->prow, h->d.model_params, np * 8)) == MI_ILQR_OK) rc = rows_to_cols(h, sc + st->prow, 0, sc + st->prm, np);
+    if (rc != MI_ILQR_OK) return rc;
+  }
+  if ((rc = rows_to_cols(h, h->costs.synced ? h->costs.rows : h->costmat, h->costs.synced ? h->costs.width : 0, sc + st->cost, n * n + m * m)) != MI_ILQR_OK) return rc;
+  if (h->limited && (rc = rows_to_cols(h, h->ulim, 2 * m, sc + st->ulim, 2 * m)) != MI_ILQR_OK) return rc;
+  if (h->plant_noise.synced && (rc = rows_to_cols(h, h->plant_noise.rows, n + m, sc + st->noise, n + m)) != MI_ILQR_OK) return rc;
+  return MI_ILQR_OK;
+}
+
+// Step 1 of a closed-loop round: the plants advance `replan_steps` steps under the policy the handle holds now (a cold handle's x_bar
+// and K read as zeros, a reset one's u_bar too, a pending guess is read from where it waits), with the target the plan was solved for.
+static int plant_advance(mi_ilqr* h, const PlantStage& st, int32_t round, int32_t replan_steps, double* mpc_dead) {
+  const Model* model = model_of(h->d.model_id);
+  const size_t B = h->B, n = h->n, m = h->m, W = n + m + m * n, C = n + m + 1;
+  double* const sc = h->scratch;
+  const double* u_src = h->u_pending ? h->u_guess : (h->u_zero ? nullptr : h->u_bar);
+  {
+    const size_t total = (size_t)replan_steps * W * B;
+    hipLaunchKernelGGL(plant_pack_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, h->stream,
+                       h->cold ? nullptr : h->x_bar, u_src, h->cold ? nullptr : h->K, sc + st.pol, (int)B, (int)n, (int)m, h->N, (int)replan_steps,
+                       layout_of(h));
+    HIPCHK(hipGetLastError());
+  }
+  int rc = rows_to_cols(h, h->targets.synced ? h->targets.rows : h->costmat + cost_len(h), h->targets.synced ? n : 0, sc + st.x_nom, n);
+  if (rc != MI_ILQR_OK) return rc;
+  PlantArgs a{};
+  a.policy = sc + st.pol; a.params = sc + st.prm; a.cost = sc + st.cost; a.x_nom = sc + st.x_nom;
+  a.ulim = h->limited ? sc + st.ulim : nullptr;
+  a.noise = h->plant_noise.synced ? sc + st.noise : nullptr;
+  a.x = h->plant_state.rows; a.dead = h->plant_dead; a.mpc_dead = mpc_dead;
+  a.log = h->plant_log + (size_t)round * replan_steps * C * B;
+  a.dt = h->d.dt; a.seed = h->plant_seed;
+  a.clock = (uint32_t)(h->plant_clock + (unsigned long long)round * (unsigned long long)replan_steps);
+  a.B = (int32_t)B; a.steps = replan_steps; a.m_user = model->p.m_user > 0 ? model->p.m_user : (int32_t)m;
+  a.feedback = h->plant_feedback ? 1 : 0; a.common = h->plant_common ? 1 : 0;
+  return model->p.launch(h, kModePlantAdvance, &a);
+}
+
 int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, const double* target_step, mi_ilqr_stats* stats) {
   if (!h) return MI_ILQR_E_BAD_ARG;
   if (num_resolves < 1 || replan_steps < 1 || replan_steps >= h->N - 1) return MI_ILQR_E_BAD_ARG;
   if (h->targets.synced && target_step) return MI_ILQR_E_BAD_ARG;   // the steps are the field MI_F_TARGET_STEP then
+  const bool plant = h->plant_state.synced;      // the closed loop: always the host-loop form, the plant kernel between its launches
+  if (plant && h->plant_clock + (unsigned long long)num_resolves * (unsigned long long)replan_steps > 0x100000000ull) return MI_ILQR_E_BAD_ARG;   // (the step counter is 32 bits)
   HIPCHK(hipSetDevice(h->d.device_id));
   int rc;
   if (h->mpc_log_resolves < num_resolves) {
@@ -1649,15 +1816,27 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
   HIPCHK(hipMemsetAsync(h->mpc_log, 0, ((size_t)h->B * h->mpc_log_resolves * (h->n + 2) + h->B) * 8, h->stream));
   h->mpc_resolves = num_resolves; h->mpc_replan = replan_steps;     // (up front: a failing re-solve must not leave the log's shape stale)
   const bool large_on_device = h->large && (size_t)h->m * (h->N - 1) <= 8 * (size_t)kLargeThreads;
-  if ((h->large && !large_on_device) || h->batch_minor || (!h->large && (h->N > 512 || h->n > 8))) {
+  if (plant || (h->large && !large_on_device) || h->batch_minor || (!h->large && (h->N > 512 || h->n > 8))) {
     // lane-per-problem path (and horizons the in-kernel shift does not cover): loop shift + solve on the host
+    PlantStage stage{};
+    if (plant) {
+      if ((rc = plant_prepare(h, num_resolves, replan_steps, &stage)) != MI_ILQR_OK) return rc;
+      h->plant_log_rows = 0; h->plant_ms = 0.0;
+    }
     std::vector<double> xn(h->n);
     // x_nom from the host mirror: mi_ilqr_set_cost uploads asynchronously on the handle's stream, so a blocking
     // null-stream read of the device copy could still see the previous target
     if (target_step) std::memcpy(xn.data(), shared_x_nom(h), h->n * 8);
     mi_ilqr_stats acc; std::memset(&acc, 0, sizeof(acc)); acc.best_cost = INFINITY; acc.best_index = -1;
     for (int r = 0; r < num_resolves; ++r) {
+      if (plant && (rc = plant_advance(h, stage, r, replan_steps, mpc_dead)) != MI_ILQR_OK) return rc;
       if ((rc = mi_ilqr_mpc_shift(h, replan_steps)) != MI_ILQR_OK) return rc;
+      if (plant) {                               // x0 <- the plant's state (a plant that has ended: the last state it held)
+        const size_t cnt = (size_t)h->B * h->n;
+        hipLaunchKernelGGL(copy_doubles_kernel, dim3((unsigned)std::min<size_t>((cnt + 255) / 256, 1024)), dim3(256), 0, h->stream,
+                           h->plant_state.rows, h->x0, cnt);
+        HIPCHK(hipGetLastError());
+      }
       if (target_step) {
         for (int i = 0; i < h->n; ++i) xn[i] += target_step[i];
         if ((rc = mi_ilqr_set_cost(h, nullptr, nullptr, nullptr, xn.data())) != MI_ILQR_OK) return rc;
@@ -1668,6 +1847,11 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
       hipLaunchKernelGGL(mpc_log_fill_kernel, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, h->x0, h->cost, h->iters, h->status, h->mpc_log,
                          mpc_dead, h->B, h->n, num_resolves, r);
       HIPCHK(hipGetLastError());
+      if (plant) {                               // (mi_ilqr_solve has synchronized: the plant kernel's events are complete)
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, h->plant_ev0, h->plant_ev1));
+        h->plant_ms += (double)ms;
+      }
       acc.total_iters += st.total_iters; acc.total_ls_trials += st.total_ls_trials; acc.kernel_ms += st.kernel_ms;
       acc.algorithmic_bytes += st.algorithmic_bytes;
       acc.n_converged = st.n_converged; acc.n_max_iters = st.n_max_iters; acc.n_ls_failed = st.n_ls_failed; acc.n_internal = st.n_internal; acc.n_not_pd = st.n_not_pd;
@@ -1675,6 +1859,12 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
       acc.best_cost = st.best_cost; acc.best_index = st.best_index;
     }
     h->mpc_resolves = num_resolves; h->mpc_replan = replan_steps;
+    if (plant) {                                 // the clock and the host mirror of the states follow the plants
+      HIPCHK(hipMemcpyAsync(h->plant_state.mirror.data(), h->plant_state.rows, (size_t)h->B * h->n * 8, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+      h->plant_clock += (unsigned long long)num_resolves * (unsigned long long)replan_steps;
+      h->plant_log_rows = num_resolves * replan_steps;
+    }
     if (stats) *stats = acc;
     return MI_ILQR_OK;
   }
@@ -1714,8 +1904,47 @@ int mi_ilqr_get_mpc_log(mi_ilqr_t* h, double* dst, size_t bytes) {
   return MI_ILQR_OK;
 }
 
+// mi_ilqr_get of the plant's selectors that are not plain mirrors; kNotPlantField for every other selector
+constexpr int kNotPlantField = 1;
+static int get_plant_field(mi_ilqr* h, int which, double* dst, size_t bytes) {
+  const size_t B = h->B;
+  switch (which) {
+    case MI_F_PLANT_STATE:                     // the mirror: mi_ilqr_mpc_run brings it up to date
+      if (bytes != B * h->n * 8) return MI_ILQR_E_BAD_SHAPE;
+      if (!h->plant_state.synced) return MI_ILQR_E_BAD_ARG;
+      return store_read(h, h->plant_state, nullptr, dst, bytes);
+    case MI_F_PLANT_PARAMS:                    // not set: problem b's model row
+      if (!h->plant_params.synced && h->params.synced) return store_read(h, h->params, nullptr, dst, bytes);
+      return store_read(h, h->plant_params, h->d.model_params, dst, bytes);
+    case MI_F_PLANT_STREAM:
+      if (bytes != 4 * 8) return MI_ILQR_E_BAD_SHAPE;
+      dst[0] = (double)h->plant_seed; dst[1] = (double)h->plant_clock; dst[2] = h->plant_common ? 1.0 : 0.0; dst[3] = h->plant_feedback ? 1.0 : 0.0;
+      return MI_ILQR_OK;
+    case MI_F_PLANT_KERNEL_MS:
+      if (bytes != 8) return MI_ILQR_E_BAD_SHAPE;
+      if (h->plant_log_rows == 0) return MI_ILQR_E_BAD_ARG;
+      *dst = h->plant_ms;
+      return MI_ILQR_OK;
+    case MI_F_PLANT_LOG: {                     // (rows, n + m + 1, B) on the device -> (B, rows, n + m + 1): one transpose, one copy
+      const size_t cw = (size_t)h->plant_log_rows * (h->n + h->m + 1);
+      if (h->plant_log_rows == 0) return MI_ILQR_E_BAD_ARG;
+      if (bytes != B * cw * 8) return MI_ILQR_E_BAD_SHAPE;
+      if (cw > 0x7fffffffull) return MI_ILQR_E_UNSUPPORTED;
+      HIPCHK(hipSetDevice(h->d.device_id));
+      int rc = ensure_scratch(h, bytes);
+      if (rc != MI_ILQR_OK) return rc;
+      if ((rc = transpose_tiles(h, h->plant_log, h->scratch, (int)cw, (int)B, 1, 1, 0, 0, B, 0, 0, cw)) != MI_ILQR_OK) return rc;
+      HIPCHK(hipStreamSynchronize(h->stream));
+      HIPCHK(hipMemcpy(dst, h->scratch, bytes, hipMemcpyDeviceToHost));
+      return MI_ILQR_OK;
+    }
+  }
+  return kNotPlantField;
+}
+
 int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
+  if (const int rc = get_plant_field(h, which, dst, bytes); rc != kNotPlantField) return rc;
   if (const RowField r = row_field(h, which); r.store) return store_read(h, *r.store, r.shared_row, dst, bytes);   // (host mirrors)
   if (which == MI_F_POLICY_STREAM) {
     if (bytes != 3 * 8) return MI_ILQR_E_BAD_SHAPE;
@@ -1755,6 +1984,7 @@ int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
 
 int mi_ilqr_get_async(mi_ilqr_t* h, int which, void* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
+  if (const int rc = get_plant_field(h, which, static_cast<double*>(dst), bytes); rc != kNotPlantField) return rc;   // (done when the call returns)
   if (const RowField r = row_field(h, which); r.store) {       // (host mirrors: the copy is done when the call returns)
     if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) {
       HIPCHK(hipSetDevice(h->d.device_id));
@@ -1801,8 +2031,12 @@ int mi_ilqr_get_int(mi_ilqr_t* h, int which, int32_t* dst, size_t bytes) {
 int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
   if (h && which == MI_F_MODEL_PARAMS) return set_model_params(h, src, bytes);   // (src == NULL, bytes == 0: back to shared mode)
   if (h && which == MI_F_COST_MATRICES) return set_cost_rows(h, src, bytes);     // (the same)
-  if (h && which == MI_F_POLICY_NOISE) return set_policy_noise(h, src, bytes);   // (src == NULL, bytes == 0: no noise)
+  if (h && which == MI_F_POLICY_NOISE) return set_noise_rows(h, h->policy_noise, src, bytes);   // (src == NULL, bytes == 0: no noise)
   if (h && which == MI_F_POLICY_STREAM) return set_policy_stream(h, src, bytes);
+  if (h && which == MI_F_PLANT_STATE) return set_plant_state(h, src, bytes);     // (src == NULL, bytes == 0: no plant)
+  if (h && which == MI_F_PLANT_PARAMS) return set_plant_params(h, src, bytes);   // (the same: the problems' model rows)
+  if (h && which == MI_F_PLANT_NOISE) return set_noise_rows(h, h->plant_noise, src, bytes);
+  if (h && which == MI_F_PLANT_STREAM) return set_plant_stream(h, src, bytes);
   if (!h || !src) return MI_ILQR_E_BAD_ARG;
   if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return set_target_field(h, which, src, bytes);
   Field f = field_of(h, which);

@@ -138,6 +138,61 @@ def check_noise_args(state_noise, control_noise, seed, first_sample, common_nois
     return rows, stream
 
 
+def check_plant_args(x, params, state_noise, control_noise, seed, common_noise, feedback, clock, B, n, m, n_params, m_dev=None):
+    """SetPlant's arguments -> (x, params, noise, stream): x the contiguous (B, n) float64 states ((n,) is broadcast to rows); params
+    None or the contiguous (B, n_params) rows ((n_params,) broadcast); noise None when both sigmas are None, else the (B, n + m_dev)
+    rows sigma_x | sigma_u of check_noise_args (the same forms: scalar, (n,) / (m,), (B, n) / (B, m)); stream the float64 quadruple
+    seed | clock | common | feedback.  ValueError - decided here, before anything reaches the device - for any other shape, NaN or
+    infinity in x or params, params for a model without parameters, a negative, NaN or infinite sigma, a seed that is no integer in
+    [0, 2^53), a clock that is no integer in [0, 2^32), common_noise or feedback that is no bool (or 0 / 1)."""
+    def array(v, name):
+        try:
+            return np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"SetPlant: {name} is not an array of numbers ({e})") from None
+
+    def rows(v, k, name):
+        a = array(v, name)
+        if a.shape == (k,):
+            a = np.broadcast_to(a, (B, k))
+        elif a.shape != (B, k):
+            raise ValueError(f"SetPlant: {name} must be ({B}, {k}) or ({k},); got {a.shape}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"SetPlant: NaN or infinity in {name}")
+        return np.ascontiguousarray(a)
+
+    def flag(v, name):
+        if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and v in (0, 1)):
+            return 1.0 if v else 0.0
+        raise ValueError(f"SetPlant: {name} must be True or False; got {v!r}")
+
+    x = rows(x, n, "x")
+    if params is not None:
+        if n_params == 0:
+            raise ValueError("SetPlant: this model has no parameters")
+        params = rows(params, n_params, "params")
+    try:
+        noise, st = check_noise_args(state_noise, control_noise, seed, clock, False, B, n, m, m_dev)
+    except ValueError as e:       # (the same rules; the messages speak of this call and of the clock)
+        raise ValueError(str(e).replace("RolloutPolicy", "SetPlant").replace("first_sample", "clock")) from None
+    stream = np.array([st[0], st[1], flag(common_noise, "common_noise"), flag(feedback, "feedback")], dtype=np.float64)
+    return x, params, noise, stream
+
+
+class PlantLog:
+    """The closed loop's record (plant_log), K = num_resolves * replan_steps steps of the last MPCRun on a solver that holds a plant:
+    X (B, n, K+1) - the state at every step, the plant's current state last -, U (B, m, K) the commanded controls, stage_cost (B, K)
+    the l_k and steps (B,) the steps each plant completed in that run; NaN where a plant that ended did not get to (its X keeps
+    the state it stopped in, in column `steps` and - the current state - in the last one)."""
+    __slots__ = ("X", "U", "stage_cost", "steps")
+
+    def __init__(self, X, U, stage_cost, steps):
+        self.X, self.U, self.stage_cost, self.steps = X, U, stage_cost, steps
+
+    def _without_batch_axis(self):
+        return PlantLog(*(a[0] for a in (self.X, self.U, self.stage_cost, self.steps)))
+
+
 class PolicyRollout:
     """What RolloutPolicy returns: cost, x_final, steps and - asked for - the trajectories X, U (else None)."""
     __slots__ = ("cost", "x_final", "steps", "X", "U")
@@ -643,7 +698,10 @@ class BatchedIterativeLQR:
         """The receding-horizon loop (acrobot.py:145-155, mini_cheetah.py:190-201) kept on the device:
         num_resolves x { shift warm start; x_nom += target_step; Solve }.  One launch for the
         wave-per-problem and workgroup-per-problem models (the lane-per-problem "throughput" kernels loop on
-        the host).  Returns the aggregate stats; `mpc_log` has the per-re-solve record."""
+        the host).  Returns the aggregate stats; `mpc_log` has the per-re-solve record.
+        On a solver that holds a plant (SetPlant) this is the CLOSED loop: before every re-solve the plant advances replan_steps
+        steps under the policy of the previous solve, and the re-solve starts from the plant's state instead of the prediction
+        x_bar[:, replan_steps] (include/mi_ilqr.h: "Closed-loop MPC"); `plant_log` has the plant's record."""
         ts = None
         steps = None if target_step is None else np.asarray(target_step, dtype=np.float64)
         per_problem = self._per_problem_targets() or (steps is not None and steps.shape == (self.B, self.n) and steps.size != self.n)
@@ -663,6 +721,7 @@ class BatchedIterativeLQR:
             self.x_nom = out
         self.stats = stats
         self._mpc_resolves = int(num_resolves)
+        self._mpc_replan = int(replan_steps)
         self._check_internal(stats)
         return stats
 
@@ -742,6 +801,58 @@ class BatchedIterativeLQR:
         if U is not None and self._md != self.m:
             U = np.ascontiguousarray(U[:, :, :self.m, :])
         return PolicyRollout(cost, x_final, steps, X, U)
+
+    # ------------------------------------------------------------- the plant of the closed MPC loop
+    def SetPlant(self, x, params=None, *, state_noise=None, control_noise=None, seed=0, common_noise=False, feedback=True, clock=0):
+        """Give every problem a plant of its own: from now on MPCRun is the closed loop (include/mi_ilqr.h: "Closed-loop MPC").
+        x: (B, n) states, or (n,) for every problem.  params: None - problem b's own model parameters - or (B, n_params) / (n_params,),
+        the TRUE plants the controller's model differs from.  state_noise (scalar, (n,) or (B, n)) and control_noise (scalar, (m,) or
+        (B, m)): standard deviations of a disturbance at every plant step, x+ = f(x, u + sigma_u xi) + sigma_x xi'; a normal depends
+        on (seed, problem, plant clock, component) only - it is the one sample 0 of RolloutPolicy gets at that step -, common_noise=True
+        gives every problem the same disturbances.  feedback=False: the plant gets u_bar alone.  clock: the plant's step counter, which
+        MPCRun advances (plant_clock).  Survives Reset(); ClearPlant() returns to the open loop."""
+        x, params, noise, stream = check_plant_args(x, params, state_noise, control_noise, seed, common_noise, feedback, clock, self.B, self.n,
+                                                    self.m, int(self.system.params.size), self._md)
+        st = lambda which, a: _capi.check(self._lib.mi_ilqr_set(self._h, which, _capi.ptr(a), 0 if a is None else a.nbytes), "mi_ilqr_set")   # noqa: E731
+        if int(self.system.params.size):
+            st(_capi.F_PLANT_PARAMS, params)
+        st(_capi.F_PLANT_NOISE, noise)
+        st(_capi.F_PLANT_STREAM, stream)
+        st(_capi.F_PLANT_STATE, x)
+
+    def ClearPlant(self):
+        """No plant: MPCRun is the open loop again, bitwise what it is on a solver that never had one."""
+        for which in (_capi.F_PLANT_STATE, _capi.F_PLANT_NOISE) + ((_capi.F_PLANT_PARAMS,) if int(self.system.params.size) else ()):
+            _capi.check(self._lib.mi_ilqr_set(self._h, which, None, 0), "mi_ilqr_set")
+
+    def _plant_get(self, which, shape):
+        out = np.empty(shape)
+        _capi.check(self._lib.mi_ilqr_get(self._h, which, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+        return out
+
+    @property
+    def plant_state(self):
+        """(B, n): the plants' current states."""
+        return self._plant_get(_capi.F_PLANT_STATE, (self.B, self.n))
+
+    @property
+    def plant_clock(self):
+        """Plant steps taken so far (SetPlant's clock, advanced by every closed-loop MPCRun)."""
+        return int(self._plant_get(_capi.F_PLANT_STREAM, (4,))[1])
+
+    @property
+    def plant_log(self):
+        """The record of the last closed-loop MPCRun: a PlantLog."""
+        K, n, md = self._mpc_resolves * self._mpc_replan, self.n, self._md
+        rows = self._plant_get(_capi.F_PLANT_LOG, (self.B, K, n + md + 1))
+        X = np.concatenate([np.moveaxis(rows[:, :, :n], 1, 2), self._plant_get(_capi.F_PLANT_STATE, (self.B, n))[:, :, None]], axis=2)
+        U = np.ascontiguousarray(np.moveaxis(rows[:, :, n:n + self.m], 1, 2))
+        steps = (~np.isnan(rows[:, :, n:n + self.m]).any(axis=2)).sum(axis=1).astype(np.int32)
+        return PlantLog(X, U, np.ascontiguousarray(rows[:, :, n + md]), steps)
+
+    def plant_kernel_ms(self):
+        """Milliseconds of the plant kernels of the last closed-loop MPCRun, summed (HIP events of their own)."""
+        return float(self._plant_get(_capi.F_PLANT_KERNEL_MS, (1,))[0])
 
     def policy_kernel_ms(self):
         """Milliseconds of the rollout kernel of the last RolloutPolicy call (HIP events of its own)."""
@@ -891,6 +1002,17 @@ class IterativeLinearQuadraticRegulator(BatchedIterativeLQR):
             raise ValueError(f"RolloutPolicy: x0 must be (S, {self.n}); got {np.shape(x0)}")
         return super().RolloutPolicy(x0, params, trajectories, state_noise=state_noise, control_noise=control_noise, seed=seed,
                                      first_sample=first_sample, common_noise=common_noise)._without_batch_axis()
+
+    def SetPlant(self, x, params=None, **kw):
+        """x (n,), params None or (n_params,), sigmas scalar or (n,) / (m,): BatchedIterativeLQR.SetPlant."""
+        if np.ndim(x) != 1:
+            raise ValueError(f"SetPlant: x must be ({self.n},); got {np.shape(x)}")
+        if params is not None and np.ndim(params) != 1:
+            raise ValueError(f"SetPlant: params must be ({int(self.system.params.size)},); got {np.shape(params)}")
+        super().SetPlant(x, params, **kw)
+
+    plant_state = property(lambda s: BatchedIterativeLQR.plant_state.fget(s)[0])
+    plant_log = property(lambda s: BatchedIterativeLQR.plant_log.fget(s)._without_batch_axis())
 
     def SaveSolution(self, fname):
         """ilqr.py:712-733: npz with t, x_bar (last step dropped), u_bar, K."""

@@ -127,6 +127,12 @@ enum {
   MI_F_POLICY_KERNEL_MS = 18,/* (1,) read-only: milliseconds of the rollout kernel of the last policy rollout, from its own HIP events (mi_ilqr_policy_rollout) */
   MI_F_POLICY_NOISE = 19,    /* (B,n+m) per-problem standard deviations sigma_x | sigma_u of the policy rollouts' disturbances ("Process and actuation noise" below) */
   MI_F_POLICY_STREAM = 20,   /* (3,) seed | first_sample | common of the disturbances' random stream, integers held in doubles (the same) */
+  MI_F_PLANT_STATE = 21,     /* (B,n) the plants' states: set, the handle holds a plant and mi_ilqr_mpc_run is the CLOSED loop ("Closed-loop MPC" below) */
+  MI_F_PLANT_PARAMS = 22,    /* (B,n_params) the plants' own model parameters (default: problem b's model row) */
+  MI_F_PLANT_NOISE = 23,     /* (B,n+m) per-problem standard deviations sigma_x | sigma_u of the plants' disturbances */
+  MI_F_PLANT_STREAM = 24,    /* (4,) seed | clock | common | feedback of the plants, integers held in doubles */
+  MI_F_PLANT_LOG = 25,       /* (B,num_resolves*replan_steps,n+m+1) read-only: rows x_k | u_k | l_k of the last closed-loop mi_ilqr_mpc_run */
+  MI_F_PLANT_KERNEL_MS = 26, /* (1,) read-only: milliseconds of the plant kernels of the last closed-loop mi_ilqr_mpc_run, summed, from their own HIP events */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
@@ -538,6 +544,49 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
  * are spread over calls: S samples from first_sample = k are samples k .. k + S - 1 of one long call, and common = 1 gives every
  * problem the same disturbances (common random numbers).  The handle stays read-only for solves: a solve after a noisy rollout is
  * bitwise the solve without it. */
+
+/* Closed-loop MPC: a plant of its own inside mi_ilqr_mpc_run (additive in ABI 10: six selectors of mi_ilqr_set / mi_ilqr_get, no new
+ * entry point).  mi_ilqr_mpc_run starts every re-solve from its own prediction, x0 <- x_bar[:, replan_steps]: the controller never
+ * meets a plant that differs from its model.  A handle that HOLDS A PLANT - one state per problem, optionally parameters and
+ * disturbances of its own - runs each of the num_resolves rounds of mi_ilqr_mpc_run(h, num_resolves, replan_steps, ..) as
+ *   1. the plants advance replan_steps steps under the policy the handle holds from the previous solve; for j = 0 .. replan_steps-1,
+ *      k = the plant clock + j:
+ *          u_k     = u_bar[:, j] - K[:, :, j] (x_k - x_bar[:, j])        clamped to the problem's box on a handle with control limits;
+ *                                                                        u_bar[:, j] (clamped likewise) with feedback off
+ *          x_{k+1} = f(x_k, u_k + sigma_u o xi^u_k; plant parameters of b, dt) + sigma_x o xi^x_k
+ *          l_k     = (x_k - x_nom_b)' Q_b (x_k - x_nom_b) + u_k' R_b u_k   the matrices and the target the executed plan was solved for
+ *      padding controls stay exact zeros; the disturbance on u comes after the clamp and is not clamped again; the log keeps the
+ *      row x_k | u_k (commanded) | l_k;
+ *   2. mi_ilqr_mpc_shift(replan_steps) as ever - the warm start - and then x0 <- the plant's state, a copy on the device;
+ *   3. the targets move (target_step / MI_F_TARGET_STEP), the solve runs, row r of the MPC log is written (its x0 IS the plant's state);
+ *   4. the clock advances by replan_steps.
+ * Such a run always takes the host-loop form of mi_ilqr_mpc_run (shift + solve launches, every kernel family; the plant is a kernel
+ * of its own between them, one GPU lane per problem).  A plant whose step is infeasible (MI_MODEL_PLANAR_QUAD, MI_MODEL_QUAD3D) or
+ * not finite ENDS there - the rule of mi_ilqr_policy_rollout, applied to the noisy x_{k+1}; that is data, not an error: it keeps its
+ * last state, its log row of that step is x_k | NaN | NaN and its later rows are NaN, the MPC log has no row for it from that round
+ * on (they read as zeros, like the rows after a failed re-solve), and - the host loop cannot leave a problem out - it is solved on
+ * from that last state; no non-finite x0 ever reaches a solve and the other problems are untouched.  It runs again once
+ * MI_F_PLANT_STATE is set again.  Without a plant mi_ilqr_mpc_run takes exactly the paths it took before, bit for bit.
+ *   mi_ilqr_set(MI_F_PLANT_STATE, x, B*n*8)   the handle holds a plant from now on (every plant running); a NaN or an infinity:
+ *                                             MI_ILQR_E_BAD_ARG.  (NULL, 0) clears it.  mi_ilqr_get: the plants' current states
+ *                                             (MI_ILQR_E_BAD_ARG without a plant).  Survives mi_ilqr_reset, like the other five.
+ *   mi_ilqr_set(MI_F_PLANT_PARAMS, rows, B*n_params*8)   the plants' own parameters, the rules of MI_F_MODEL_PARAMS (MI_ILQR_E_UNSUPPORTED
+ *                                             for a model without parameters); (NULL, 0) or never set: problem b's model row
+ *                                             (MI_F_MODEL_PARAMS, else the descriptor's), which is also what mi_ilqr_get returns then.
+ *   mi_ilqr_set(MI_F_PLANT_NOISE, rows, B*(n+m)*8)   sigma_x | sigma_u with the rules and errors of MI_F_POLICY_NOISE; (NULL, 0) clears it
+ *                                             and the noise-free plant kernel runs again.  Independent of MI_F_POLICY_NOISE.
+ *   mi_ilqr_set(MI_F_PLANT_STREAM, v, 32)     v = seed | clock | common | feedback, integer values: seed in [0, 2^53), clock in [0, 2^32),
+ *                                             common and feedback 0 or 1.  Default 0 | 0 | 0 | 1.  mi_ilqr_mpc_run writes the advanced
+ *                                             clock back; a run whose clock would pass 2^32 (clock + num_resolves * replan_steps > 2^32)
+ *                                             returns MI_ILQR_E_BAD_ARG before anything is launched.
+ *   mi_ilqr_get(MI_F_PLANT_LOG, dst, B*num_resolves*replan_steps*(n+m+1)*8)   the rows of the last closed-loop run; wrong `bytes`
+ *                                             MI_ILQR_E_BAD_SHAPE, before any such run MI_ILQR_E_BAD_ARG (MI_F_PLANT_KERNEL_MS likewise).
+ * m is the DEVICE's number of controls throughout.  A refused call changes nothing.  The normals are those of the policy rollouts:
+ * Philox4x32-10 under the key (seed mod 2^32, seed div 2^32) with
+ *     counter = (0, k, common ? 0 : b, j)     j = i / 4 for state component i, j = 256 + c / 4 for control component c
+ * and the same Box-Muller - so the plant of problem b at clock k gets the normals that SAMPLE 0 of a policy rollout
+ * (first_sample = 0) gets at step t = k: from clock 0, with the same seed and sigmas, the first segment of a closed-loop run is the
+ * first replan_steps steps of that rollout. */
 
 #ifdef __cplusplus
 }
