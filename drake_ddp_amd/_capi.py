@@ -34,6 +34,8 @@ F_POLICY_STREAM = 20              # (3,) seed | first_sample | common of their r
 # the plant of the closed MPC loop (mi_ilqr.h: "Closed-loop MPC"): (B, n) states | (B, n_params) parameters | (B, n+m) sigma_x | sigma_u |
 # (4,) seed | clock | common | feedback | read-only (B, K, n+m+1) log | read-only (1,) ms of the plant kernels
 F_PLANT_STATE, F_PLANT_PARAMS, F_PLANT_NOISE, F_PLANT_STREAM, F_PLANT_LOG, F_PLANT_KERNEL_MS = 21, 22, 23, 24, 25, 26
+# reference trajectories (mi_ilqr.h: "Reference trajectories"): (B, T, n) time-varying targets | (1,) the row a solve's window starts at
+F_X_REF, F_REF_CLOCK = 27, 28
 I_ITERS, I_STATUS, I_LS_TRIALS, I_KP_COUNT, I_KP_LIST = 100, 101, 102, 103, 104
 I64_STAGE_CYCLES = 200
 I64_CLUSTER_WORDS = 201

@@ -119,7 +119,15 @@ struct mi_ilqr {
   // lane-per-problem kernels: their per-problem-cost instantiations always read target ROWS; a handle with one target gets the
   // shared x_nom broadcast into these (B, n) rows before a launch (refresh_lane_target_rows)
   RowStore lane_targets;
-  std::vector<void*> owned;        // every device allocation of the handle (dev_alloc): what mi_ilqr_destroy frees
+  // reference trajectories (MI_F_X_REF / MI_F_REF_CLOCK; workgroup-per-problem handles): (B, ref_T * n) rows, `synced` = the handle
+  // holds a reference; ref_clock: the row a solve's window starts at (mi_ilqr_mpc_run advances it); ref_qn: (B, N-1, n) kernel
+  // scratch (KArgs::ref_qn).  ref_cap: the doubles reference.rows was allocated for (a longer reference gets a new block).
+  RowStore reference;
+  int ref_T = 0;
+  long long ref_clock = 0;
+  size_t ref_cap = 0;
+  double* ref_qn = nullptr;
+  std::vector<void*> owned;       // every device allocation of the handle (dev_alloc): what mi_ilqr_destroy frees
   // mi_ilqr_policy_rollout: start / stop events of its rollout kernel (created on first use; MI_F_POLICY_KERNEL_MS) - its own pair,
   // so that the solves' events and statistics stay what they were
   hipEvent_t policy_ev0 = nullptr, policy_ev1 = nullptr;

@@ -46,7 +46,27 @@ struct LView {
   int pd_continue;  // a Quu that is not positive definite: 1 = invert it with partial pivoting and carry on like np.linalg.inv (ilqr.py:655)
   int asym;         // Q, R or Qf is not symmetric (mid-size kernels only): the reference's recursion without any use of symmetry
   const double* prow;   // this problem's row of the per-problem model parameters (KArgs::param_rows), or nullptr: the shared ones
+  // reference trajectory (KArgs::x_ref): this problem's (ref_T, n) rows, or nullptr: the constant target x_nom.  The window of the
+  // solve starts at row ref_clk and holds the last row past the end (ref_at).  qnG: 2 r_t^T Q of the window's steps, [N-1][n] in HBM
+  // (ilqr_large_kernel: ref_window) - what the backward passes subtract per step where oQn serves a constant target.
+  const double* ref;
+  double* qnG;
+  int ref_T, ref_clk;
 };
+
+// r_t of the window, component i (only where v.ref is not null)
+template <int n, class V>
+__device__ __forceinline__ double ref_at(const V& v, int t, int i) {
+  const int r = v.ref_clk + t < v.ref_T - 1 ? v.ref_clk + t : v.ref_T - 1;
+  return v.ref[(size_t)r * n + i];
+}
+// (2 x_nom^T Q)_i as step t's cost gradient sees it: the step's own row under a reference, else the LDS vector.  A value is selected,
+// never a pointer (lxu_load: the HBM side as a relaxed device-scope atomic keeps the two accesses apart).
+template <int n, class V>
+__device__ __forceinline__ double qn_at(const V& v, const double* qn, int t, int i) {
+  if (v.qnG) return __hip_atomic_load(v.qnG + (size_t)t * n + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return qn[i];
+}
 
 // lx_t | lu_t: LDS (the address space stays known to the compiler) or HBM, chosen per launch
 // (the HBM side as relaxed device-scope atomics: plain accesses let the compiler fold the two branches into ONE access through a
@@ -282,8 +302,10 @@ __device__ inline double large_rollout(const LView<M::n, M::m>& v, double* lds, 
   // Operands of the control law (K_t row slice, x_bar_t slice, u_bar_t, kappa_t) come from
   // L2/MALL: they are requested TWO steps ahead into two alternating register sets (a step is
   // ~1.5 k cycles of work; an Infinity-Cache hit costs about that much on its own).
-  struct Pf { double kr[JR], xbr[JR], ubk, kpk; };
+  // (and, under a reference trajectory, r_t for the lanes that form x_t - r_t: `rr`, x_nom itself otherwise)
+  struct Pf { double kr[JR], xbr[JR], ubk, kpk, rr; };
   Pf pfA, pfB;
+  pfA.rr = xnr; pfB.rr = xnr;
   auto prefetch = [&](Pf& f, int t) __attribute__((always_inline)) {
     if (urole) {
       const double* Kr = v.K + ((size_t)t * m + uk) * n;
@@ -297,6 +319,7 @@ __device__ inline double large_rollout(const LView<M::n, M::m>& v, double* lds, 
       f.ubk = 0.0; f.kpk = 0.0;
       if (ul == 0) { f.ubk = v.U[(size_t)t * m + uk]; f.kpk = v.kap[(size_t)t * m + uk]; }
     }
+    if (v.ref) { if (drole) f.rr = ref_at<n>(v, t, tid - 192); }
   };
   double* xc = xs;                     // current state
   double* xn_ = xs2;                   // next state
@@ -317,7 +340,7 @@ __device__ inline double large_rollout(const LView<M::n, M::m>& v, double* lds, 
     }
     if (drole) {
       const double xv_ = xc[tid - 192];
-      dxc[tid - 192] = xv_ - xnr;
+      dxc[tid - 192] = xv_ - f.rr;
       if (prog) {
         if (tid == 192 && t >= 1) {
           drain_stores();                                    // steps 0 .. t-1: every store this wave has issued is complete
@@ -600,8 +623,10 @@ __device__ inline void mid_rollout4(const LView<M::n, M::m>& v, double* xsp, dou
 #pragma unroll
   for (int i = 0; i < n; ++i) xr[i] = x0g[i];
   double acc[kSpec] = {0.0, 0.0, 0.0, 0.0};
-  struct Pf { double kr[JR], xbr[JR], ubk, kpk; };
+  // (and, under a reference trajectory, r_t for the lanes that form x_t - r_t: `rr`, x_nom itself otherwise)
+  struct Pf { double kr[JR], xbr[JR], ubk, kpk, rr; };
   Pf pfA, pfB;
+  pfA.rr = xnr; pfB.rr = xnr;
   auto prefetch = [&](Pf& f, int t) __attribute__((always_inline)) {
     if (urole) {
       const double* Kr = v.K + ((size_t)t * m + uk) * n;
@@ -615,6 +640,7 @@ __device__ inline void mid_rollout4(const LView<M::n, M::m>& v, double* xsp, dou
       f.ubk = 0.0; f.kpk = 0.0;
       if (ul == 0) { f.ubk = v.U[(size_t)t * m + uk]; f.kpk = v.kap[(size_t)t * m + uk]; }
     }
+    if (v.ref) { if (drole) f.rr = ref_at<n>(v, t, tid - 192); }
   };
   auto one_step = [&](Pf& f, int t) __attribute__((always_inline)) {
     if (urole) {                                           // u_t = u_bar_t - eps kappa_t - K_t (x_t - x_bar_t)   (ilqr.py:313)
@@ -642,7 +668,7 @@ __device__ inline void mid_rollout4(const LView<M::n, M::m>& v, double* xsp, dou
 #pragma unroll
       for (int c = 0; c < kSpec; ++c) {
         const double xv_ = xc[c * XS + tid - 192];
-        dx4[c * 32 + tid - 192] = xv_ - xnr;
+        dx4[c * 32 + tid - 192] = xv_ - f.rr;
         Xo(c)[(size_t)t * n + (tid - 192)] = xv_;
       }
     }
@@ -1453,6 +1479,13 @@ __device__ inline void large_backward(const LView<M::n, M::m>& v, double* lds, l
         const int pp = 16 * c + lr;
         const double c0 = pp < n ? -qn[pp] : 0.0;
         d4_t acc = {c0, c0, c0, c0};
+        if (v.qnG) {                                         // reference trajectory: every step its own 2 r_t^T Q
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            const int tt = 16 * q + lk + 4 * reg;
+            acc[reg] = (tt < N - 1 && pp < n) ? -qn_at<n>(v, qn, tt, pp) : 0.0;
+          }
+        }
         acc = op.run(acc);
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
@@ -1474,7 +1507,7 @@ __device__ inline void large_backward(const LView<M::n, M::m>& v, double* lds, l
         double s_;
         if (pp < n) {
           const double* xg = v.X + (size_t)tt * n;
-          s_ = -qn[pp];
+          s_ = -qn_at<n>(v, qn, tt, pp);
           for (int j = 0; j < n; ++j) s_ += (2.0 * Q[pp * n + j]) * xg[j];
         } else {
           const double* ug = v.U + (size_t)tt * m;
@@ -2036,7 +2069,7 @@ __device__ inline void mid_backward(const LView<M::n, M::m>& v, double* lds, boo
         const double qnp = qn[pp];
         for (int tt = g0; tt < N - 1; tt += TG) {
           const double* xg = Xs_ + (size_t)tt * n;
-          double s_ = -qnp;
+          double s_ = v.qnG ? -qn_at<n>(v, qn, tt, pp) : -qnp;
 #pragma unroll
           for (int j = 0; j < n; ++j) s_ += q2[j] * xg[j];
           lxu_store(v, Lxu, tt * nm + pp, s_);
@@ -2404,7 +2437,7 @@ __device__ inline void large_backward_asym(const LView<M::n, M::m>& v, double* l
       }
       if (tid < n) {
         const double* xg = v.X + (size_t)t * n;
-        double s_ = -qn[tid];
+        double s_ = -qn_at<n>(v, qn, t, tid);
         for (int j = 0; j < n; ++j) s_ += (2.0 * Q[tid * n + j]) * xg[j];
         Gr[tid] = s_;
       } else if (tid < nm) {
@@ -2745,7 +2778,7 @@ __device__ inline void mid_backward_limited(const LView<M::n, M::m>& v, double* 
       }
       if (tid < n) {
         const double* xg = v.X + (size_t)t * n;
-        double s_ = -qn[tid];
+        double s_ = -qn_at<n>(v, qn, t, tid);
         for (int j = 0; j < n; ++j) s_ += (2.0 * Q[tid * n + j]) * xg[j];
         Gr[tid] = s_;
       } else if (tid < nm) {
@@ -2918,6 +2951,12 @@ __global__ void __launch_bounds__(kLargeThreads, 1) ilqr_large_kernel(const KArg
   v.pd_continue = a.pd_continue;
   v.asym = a.cost_asym;                     // (n >= 33: large_backward_asym, the PIV form of the kernel)
   v.prow = param_row_of<M>(a, b);
+  v.ref = a.x_ref ? a.x_ref + (size_t)b * a.ref_T * n : nullptr;   // (a helper: the rows of the problem it serves)
+  v.qnG = a.x_ref ? a.ref_qn + (size_t)b * (N - 1) * n : nullptr;
+  v.ref_T = a.ref_T;
+  v.ref_clk = a.ref_clock;
+  // (uniform values in scalar registers.  Forced into vector registers - fewer scalar spills, 334 / 335 against 350 / 381 in the
+  //  Synth36 kernels - they measured SLOWER)
   LargeAcc<n, m> acc;
   acc.X = v.X; acc.Fx = v.Fx; acc.Fu = v.Fu; acc.N = N;
   { const int Nr = int_row(N); acc.kp = ilds; acc.aux = ilds + Nr; acc.need = ilds + 2 * Nr; acc.binA = ilds + 3 * Nr; acc.binB = ilds + 5 * Nr; }
@@ -2928,7 +2967,9 @@ __global__ void __launch_bounds__(kLargeThreads, 1) ilqr_large_kernel(const KArg
     const double* cm = cost_of<n, m>(a, b);   // (a helper: the row of the problem it serves - its linearization and candidate rollouts)
     for (int e = tid; e < n * n; e += kLargeThreads) { lds[Ly::oQ + e] = cm[e]; lds[Ly::oQf + e] = cm[n * n + m * m + e]; }
     for (int e = tid; e < m * m; e += kLargeThreads) lds[Ly::oR + e] = cm[n * n + e];
-    if (tid < n) lds[Ly::oXnom + tid] = x_nom_of<n, m>(a, b)[tid];   // (a helper: the problem it serves)
+    // (a reference trajectory: the LDS target is the TERMINAL row r_{N-1} - the rollouts' terminal term and oQfn follow from it -
+    //  and the steps take their rows from HBM: the rollouts r_t itself, the backward passes 2 r_t^T Q out of ref_window's rows)
+    if (tid < n) lds[Ly::oXnom + tid] = v.ref ? ref_at<n>(v, N - 1, tid) : x_nom_of<n, m>(a, b)[tid];   // (a helper: the problem it serves)
     __syncthreads();
     if (tid < n) {
       double s = 0.0, sf = 0.0;
@@ -2939,6 +2980,21 @@ __global__ void __launch_bounds__(kLargeThreads, 1) ilqr_large_kernel(const KArg
       lds[Ly::oQn + tid] = s; lds[Ly::oQfn + tid] = sf;
     }
   }
+  // Reference trajectory: 2 r_t^T Q of the window's steps -> v.qnG, the loop of oQn above once per step (a one-row reference: its
+  // bits).  The solving workgroup only (helpers linearize; candidate groups are off on such handles, mi_ilqr.hip: make_args).
+  // Agent-scope stores, drained: the backward passes read them back with agent-scope loads (qn_at) behind the next barrier.
+  auto ref_window = [&]() __attribute__((always_inline)) {
+    if (v.ref && role == 0) {
+      for (int idx = tid; idx < (N - 1) * n; idx += kLargeThreads) {
+        const int tt = idx / n, pp = idx - tt * n;
+        double s = 0.0;
+        for (int i = 0; i < n; ++i) s += (2.0 * ref_at<n>(v, tt, i)) * lds[Ly::oQ + i * n + pp];
+        st_shared<true>(v.qnG + idx, s);
+      }
+      drain_stores();
+    }
+  };
+  ref_window();
   if constexpr (UsesLimits<M>::value) {                     // this problem's bounds and the S2 of its last backward pass
     static_assert(Ly::kMid, "control limits: the mid-size family only");
     if (tid < 2 * m) lds[Ly::oRed + kLimSlot + tid] = a.ulim[(size_t)b * 2 * m + tid];
@@ -3303,6 +3359,7 @@ __global__ void __launch_bounds__(kLargeThreads, 1) ilqr_large_kernel(const KArg
     if (MODE == MODE_MPC) {
       // warm start (mini_cheetah.py:193-198): x0 <- x_bar[:, replan]; u_bar <- [u_bar[:, replan:], repeat(last)]
       const int r = a.mpc_replan;
+      if (v.ref) v.ref_clk = a.ref_clock + (rs + 1) * r;   // (below: the window at the new clock)
       double* x0w = const_cast<double*>(x0g);
       constexpr int UPT = 8;                               // (m*(N-1) + 255) / 256 <= 8 for every admissible N
       double ush[UPT];
@@ -3323,7 +3380,9 @@ __global__ void __launch_bounds__(kLargeThreads, 1) ilqr_large_kernel(const KArg
       if (tid < n) {
         x0w[tid] = x0n;
         // moving target (mini_cheetah.py:151-156) and the constants derived from it (ilqr.py:180,203)
-        lds[Ly::oXnom + tid] += target_step_of<n>(a, b, tid);
+        // (a reference trajectory: it is the window that moves - re-solve rs + 1 starts at row ref_clock + (rs + 1) replan)
+        if (v.ref) lds[Ly::oXnom + tid] = ref_at<n>(v, N - 1, tid);
+        else lds[Ly::oXnom + tid] += target_step_of<n>(a, b, tid);
       }
       __syncthreads();
       if (tid < n) {
@@ -3334,6 +3393,7 @@ __global__ void __launch_bounds__(kLargeThreads, 1) ilqr_large_kernel(const KArg
         }
         lds[Ly::oQn + tid] = s_; lds[Ly::oQfn + tid] = sf_;
       }
+      ref_window();
       __syncthreads();
       L = __builtin_inf();
       status = MI_STATUS_CONVERGED;                          // per re-solve, as a host loop of Solve() calls would leave it

@@ -96,6 +96,14 @@ struct KArgs {
   // class of the most general row.  Neither array is written while a kernel runs.
   const double* cost_rows;
   const double* cost_cols;
+  // reference trajectories (mi_ilqr_set MI_F_X_REF / MI_F_REF_CLOCK; workgroup-per-problem kernels only): (B, ref_T, n) rows.  While
+  // x_ref is not null, every place a solve uses x_nom at time index t uses row min(ref_clock + t, ref_T - 1) of problem b instead
+  // (ilqr_large.hpp: ref_at); MODE_MPC moves the clock by mpc_replan before every re-solve.  ref_qn: (B, N-1, n) scratch the kernel fills with
+  // 2 r_t^T Q of the window it solves on - what the backward passes subtract per step where oQn serves a constant target.
+  // Null: x_nom.  x_ref is not written while a kernel runs.
+  const double* x_ref;
+  double* ref_qn;
+  int32_t ref_T, ref_clock;
 };
 
 // Where problem b's target lives: row b of the per-problem targets, else the shared one in the costmat (Q | R | Qf | x_nom).

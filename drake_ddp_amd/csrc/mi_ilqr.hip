@@ -194,6 +194,8 @@ KArgs make_args(const mi_ilqr* h) {
   if (a.cost_cols && !a.x_nom_rows) a.x_nom_rows = device_rows(h->lane_targets);
   a.param_rows = device_rows(h->params);
   a.param_cols = device_cols(h->params);
+  a.x_ref = device_rows(h->reference);
+  a.ref_qn = h->ref_qn; a.ref_T = h->ref_T; a.ref_clock = (int32_t)h->ref_clock;
   a.spec_policy = h->x_spec ? sw.spec : 0;
   a.cluster = 1;
   a.cluster_sync = h->cluster_sync;
@@ -215,6 +217,7 @@ KArgs make_args(const mi_ilqr* h) {
     bool still = true;
     for (int i = 0; i < h->n; ++i) still = still && h->mpc_target_step[i] == 0.0;
     if (h->target_steps_moving) still = false;
+    if (h->reference.synced) still = false;     // (a reference trajectory: the window moves with the clock, and only the leader follows it)
     const bool lsg = sw.ls_groups && still && h->spec_slots >= 4 * g - 1 && g > 1;
     a.cluster = g | ((sw.cluster_order & 3) << 8) | ((sw.early ? 1 : 0) << 10) | ((lsg ? 1 : 0) << 11);
   }
@@ -1088,6 +1091,47 @@ static int advance_per_problem_targets(mi_ilqr* h, int32_t times) {
   return upload_target_rows(h, h->targets, rows.data());
 }
 
+// Reference trajectories (MI_F_X_REF / MI_F_REF_CLOCK): (B, T, n) rows, T from the byte count; src == NULL with bytes == 0: no
+// reference, clock 0 - the kernels get a null x_ref, as on a handle that never held one.  Workgroup-per-problem handles only; not
+// beside a plant (the plant kernels know constant targets only).  A refused call changes nothing.
+constexpr double kRefClockEnd = 0x1p30;       // clocks and reference lengths stay below: row indices are 32-bit in the kernels
+static int set_reference(mi_ilqr* h, const double* src, size_t bytes) {
+  if (!src && bytes == 0) { store_drop(h->reference); h->ref_T = 0; h->ref_clock = 0; return MI_ILQR_OK; }
+  if (!h->large || h->plant_state.synced) return MI_ILQR_E_UNSUPPORTED;
+  const size_t per_row = (size_t)h->B * h->n;
+  if (bytes == 0 || bytes % (per_row * 8) != 0) return MI_ILQR_E_BAD_SHAPE;
+  const size_t T = bytes / (per_row * 8), cnt = per_row * T;
+  if ((double)T >= kRefClockEnd) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(src[i])) return MI_ILQR_E_BAD_ARG;
+  HIPCHK(hipSetDevice(h->d.device_id));
+  int rc = MI_ILQR_OK;
+  if (!h->ref_qn && (rc = dev_alloc(h, h->ref_qn, (size_t)h->B * (h->N - 1) * h->n)) != MI_ILQR_OK) return rc;
+  RowStore& s = h->reference;
+  if (s.width != T * (size_t)h->n) store_drop(s);           // (another length: nothing of the old rows can be kept)
+  if (cnt > h->ref_cap) {                                  // a longer reference: a block of its own size (kernels in flight read the old one)
+    HIPCHK(hipStreamSynchronize(h->stream));
+    store_drop(s);
+    h->ref_T = 0; h->ref_cap = 0;
+    if ((rc = dev_free(h, s.rows)) != MI_ILQR_OK) return rc;
+  }
+  s.width = T * (size_t)h->n;
+  if ((rc = store_upload(h, s, src)) != MI_ILQR_OK) { h->ref_T = 0; return rc; }
+  if (cnt > h->ref_cap) h->ref_cap = cnt;
+  h->ref_T = (int)T;
+  return MI_ILQR_OK;
+}
+
+static int set_ref_clock(mi_ilqr* h, const double* src, size_t bytes) {
+  if (!h->large) return MI_ILQR_E_UNSUPPORTED;
+  if (bytes != 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  const double c = *src;
+  if (!(c >= 0.0 && c < kRefClockEnd && c == std::floor(c))) return MI_ILQR_E_BAD_ARG;
+  h->ref_clock = (long long)c;
+  return MI_ILQR_OK;
+}
+
 // Per-problem model parameters (MI_F_MODEL_PARAMS): (B, n_params) rows, problem b's plant in row b.  src == NULL with bytes == 0:
 // back to the descriptor's parameters - the kernels read KArgs::params, as on a handle that never left them.
 static int set_model_params(mi_ilqr* h, const double* src, size_t bytes) {
@@ -1125,6 +1169,7 @@ static int set_noise_rows(mi_ilqr* h, RowStore& store, const double* src, size_t
 static int set_plant_state(mi_ilqr* h, const double* src, size_t bytes) {
   const size_t cnt = (size_t)h->B * h->n;
   if (!src && bytes == 0) { store_drop(h->plant_state); return MI_ILQR_OK; }
+  if (h->reference.synced) return MI_ILQR_E_UNSUPPORTED;      // (the plant kernels know constant targets only)
   if (bytes != cnt * 8) return MI_ILQR_E_BAD_SHAPE;
   if (!src) return MI_ILQR_E_BAD_ARG;
   for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(src[i])) return MI_ILQR_E_BAD_ARG;
@@ -1601,6 +1646,7 @@ int mi_ilqr_backward(mi_ilqr_t* h) {
 int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const double* params, double* cost, double* x_final,
                            int32_t* steps, double* X, double* U) {
   if (!h || S < 1 || !x0 || !cost) return MI_ILQR_E_BAD_ARG;
+  if (h->reference.synced) return MI_ILQR_E_UNSUPPORTED;      // (the policy kernels cost a rollout against a constant target only)
   const Model* model = model_of(h->d.model_id);
   const size_t B = h->B, n = h->n, m = h->m, N = h->N, np = model->p.n_params, Sz = (size_t)S, W = n + m + m * n;
   if (params && np == 0) return MI_ILQR_E_UNSUPPORTED;
@@ -1800,6 +1846,9 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
   if (!h) return MI_ILQR_E_BAD_ARG;
   if (num_resolves < 1 || replan_steps < 1 || replan_steps >= h->N - 1) return MI_ILQR_E_BAD_ARG;
   if (h->targets.synced && target_step) return MI_ILQR_E_BAD_ARG;   // the steps are the field MI_F_TARGET_STEP then
+  const bool tracking = h->reference.synced;     // a reference trajectory: the window moves, replan_steps rows per re-solve
+  if (tracking && target_step) return MI_ILQR_E_BAD_ARG;
+  if (tracking && (double)h->ref_clock + (double)num_resolves * (double)replan_steps >= kRefClockEnd) return MI_ILQR_E_BAD_ARG;
   const bool plant = h->plant_state.synced;      // the closed loop: always the host-loop form, the plant kernel between its launches
   if (plant && h->plant_clock + (unsigned long long)num_resolves * (unsigned long long)replan_steps > 0x100000000ull) return MI_ILQR_E_BAD_ARG;   // (the step counter is 32 bits)
   HIPCHK(hipSetDevice(h->d.device_id));
@@ -1828,9 +1877,10 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
     // null-stream read of the device copy could still see the previous target
     if (target_step) std::memcpy(xn.data(), shared_x_nom(h), h->n * 8);
     mi_ilqr_stats acc; std::memset(&acc, 0, sizeof(acc)); acc.best_cost = INFINITY; acc.best_index = -1;
+    const long long clock0 = h->ref_clock;       // (a run that fails leaves the reference's clock where it was)
     for (int r = 0; r < num_resolves; ++r) {
       if (plant && (rc = plant_advance(h, stage, r, replan_steps, mpc_dead)) != MI_ILQR_OK) return rc;
-      if ((rc = mi_ilqr_mpc_shift(h, replan_steps)) != MI_ILQR_OK) return rc;
+      if ((rc = mi_ilqr_mpc_shift(h, replan_steps)) != MI_ILQR_OK) { h->ref_clock = clock0; return rc; }
       if (plant) {                               // x0 <- the plant's state (a plant that has ended: the last state it held)
         const size_t cnt = (size_t)h->B * h->n;
         hipLaunchKernelGGL(copy_doubles_kernel, dim3((unsigned)std::min<size_t>((cnt + 255) / 256, 1024)), dim3(256), 0, h->stream,
@@ -1841,9 +1891,11 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
         for (int i = 0; i < h->n; ++i) xn[i] += target_step[i];
         if ((rc = mi_ilqr_set_cost(h, nullptr, nullptr, nullptr, xn.data())) != MI_ILQR_OK) return rc;
       }
-      if (h->targets.synced && (rc = advance_per_problem_targets(h, 1)) != MI_ILQR_OK) return rc;   // one (B, n) upload
+      // (per-problem targets under a reference are kept but ignored: they do not move either)
+      if (h->targets.synced && !tracking && (rc = advance_per_problem_targets(h, 1)) != MI_ILQR_OK) return rc;   // one (B, n) upload
+      if (tracking) h->ref_clock += replan_steps;
       mi_ilqr_stats st;
-      if ((rc = mi_ilqr_solve(h, &st)) != MI_ILQR_OK) return rc;
+      if ((rc = mi_ilqr_solve(h, &st)) != MI_ILQR_OK) { h->ref_clock = clock0; return rc; }
       hipLaunchKernelGGL(mpc_log_fill_kernel, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, h->x0, h->cost, h->iters, h->status, h->mpc_log,
                          mpc_dead, h->B, h->n, num_resolves, r);
       HIPCHK(hipGetLastError());
@@ -1874,12 +1926,13 @@ int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, co
   for (int i = 0; i < kMaxStateDim; ++i) h->mpc_target_step[i] = (target_step && i < h->n) ? target_step[i] : 0.0;
   rc = launch(h, MODE_MPC);
   if (rc != MI_ILQR_OK) return rc;
+  if (tracking) h->ref_clock += (long long)num_resolves * replan_steps;   // (what the kernel's window moved by)
   if (!stats_in_kernel(h)) {
     hipLaunchKernelGGL(stats_kernel, dim3(1), dim3(256), 0, h->stream, h->iters_ring, h->status_ring, h->ls_ring, h->cost_ring,
                        h->B, h->d_ring, h->cur_slot, (int)mi_ilqr::kStatsRing);
     HIPCHK(hipGetLastError());
   }
-  if (h->targets.synced) {   // the rows the kernel moved, every problem's num_resolves times (a failed problem's included)
+  if (h->targets.synced && !tracking) {   // the rows the kernel moved, every problem's num_resolves times (a failed problem's included)
     HIPCHK(hipStreamSynchronize(h->stream));
     if ((rc = advance_per_problem_targets(h, num_resolves)) != MI_ILQR_OK) return rc;
   }
@@ -1904,7 +1957,8 @@ int mi_ilqr_get_mpc_log(mi_ilqr_t* h, double* dst, size_t bytes) {
   return MI_ILQR_OK;
 }
 
-// mi_ilqr_get of the plant's selectors that are not plain mirrors; kNotPlantField for every other selector
+// mi_ilqr_get of the plant's selectors that are not plain mirrors (and of the reference trajectory's two: a (B, T, n) mirror whose
+// length is its own, and the clock); kNotPlantField for every other selector
 constexpr int kNotPlantField = 1;
 static int get_plant_field(mi_ilqr* h, int which, double* dst, size_t bytes) {
   const size_t B = h->B;
@@ -1919,6 +1973,15 @@ static int get_plant_field(mi_ilqr* h, int which, double* dst, size_t bytes) {
     case MI_F_PLANT_STREAM:
       if (bytes != 4 * 8) return MI_ILQR_E_BAD_SHAPE;
       dst[0] = (double)h->plant_seed; dst[1] = (double)h->plant_clock; dst[2] = h->plant_common ? 1.0 : 0.0; dst[3] = h->plant_feedback ? 1.0 : 0.0;
+      return MI_ILQR_OK;
+    case MI_F_X_REF:                           // the mirror (B, T, n); no reference: nothing to read
+      if (!h->reference.synced) return MI_ILQR_E_BAD_ARG;
+      if (bytes != h->reference.mirror.size() * 8) return MI_ILQR_E_BAD_SHAPE;
+      std::memcpy(dst, h->reference.mirror.data(), bytes);
+      return MI_ILQR_OK;
+    case MI_F_REF_CLOCK:
+      if (bytes != 8) return MI_ILQR_E_BAD_SHAPE;
+      *dst = (double)h->ref_clock;
       return MI_ILQR_OK;
     case MI_F_PLANT_KERNEL_MS:
       if (bytes != 8) return MI_ILQR_E_BAD_SHAPE;
@@ -2037,6 +2100,8 @@ int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
   if (h && which == MI_F_PLANT_PARAMS) return set_plant_params(h, src, bytes);   // (the same: the problems' model rows)
   if (h && which == MI_F_PLANT_NOISE) return set_noise_rows(h, h->plant_noise, src, bytes);
   if (h && which == MI_F_PLANT_STREAM) return set_plant_stream(h, src, bytes);
+  if (h && which == MI_F_X_REF) return set_reference(h, src, bytes);             // (src == NULL, bytes == 0: no reference)
+  if (h && which == MI_F_REF_CLOCK) return set_ref_clock(h, src, bytes);
   if (!h || !src) return MI_ILQR_E_BAD_ARG;
   if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return set_target_field(h, which, src, bytes);
   Field f = field_of(h, which);

@@ -60,6 +60,34 @@ def check_model_params(params, B, n_params):
     return np.ascontiguousarray(a)
 
 
+def check_target_trajectory(x_ref, clock, B, n):
+    """SetTargetTrajectory's arguments as a contiguous (B, T, n) float64 array ((T, n) is broadcast to the batch; None for None) and
+    the clock as an int.  ValueError for any other shape, T = 0, NaN / infinity and a clock that is not an integer in [0, 2^30) -
+    decided here, before anything reaches the device."""
+    try:
+        c = int(clock)
+        ok = c == clock and 0 <= c < 2 ** 30
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"SetTargetTrajectory: clock must be an integer in [0, 2^30); got {clock!r}")
+    if x_ref is None:
+        return None, c
+    try:
+        a = np.asarray(x_ref, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"SetTargetTrajectory: not an array of numbers ({e})") from None
+    if a.ndim == 2 and a.shape[1] == n:
+        a = np.broadcast_to(a, (B,) + a.shape)
+    elif not (a.ndim == 3 and a.shape[0] == B and a.shape[2] == n):
+        raise ValueError(f"SetTargetTrajectory: the reference must be (T, {n}) or ({B}, T, {n}); got {a.shape}")
+    if a.shape[1] < 1:
+        raise ValueError("SetTargetTrajectory: the reference needs at least one row (T >= 1)")
+    if not np.isfinite(a).all():
+        raise ValueError("SetTargetTrajectory: NaN or infinity")
+    return np.ascontiguousarray(a), c
+
+
 def check_rollout_args(x0, params, B, n, n_params):
     """RolloutPolicy's arguments as contiguous (B, S, n) and (B, S, n_params) float64 arrays (None for params=None).
     ValueError for a wrong rank or size and for NaN / infinity in params - decided here, before anything reaches the device.
@@ -292,6 +320,7 @@ class BatchedIterativeLQR:
         self.stats = None
         self.time_getDerivs = self.time_backwardsPass = self.time_fp = 0.0
         self.solve_wall_s = 0.0
+        self._ref_T = 0                # rows of the reference this object last set (SetTargetTrajectory); the handle says whether it holds one
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -317,6 +346,56 @@ class BatchedIterativeLQR:
     def _set_field(self, which, a):
         a = _capi.as_f64(a, (self.B, self.n))
         _capi.check(self._lib.mi_ilqr_set(self._h, which, _capi.ptr(a), a.nbytes), "mi_ilqr_set")
+
+    def SetTargetTrajectory(self, x_ref, clock=0):
+        """A reference to TRACK: (B, T, n), every problem its own, or (T, n) for the whole batch (include/mi_ilqr.h: "Reference
+        trajectories").  While the solver holds one, time index t of a solve is pulled towards x_ref[b, min(clock + t, T - 1)] instead
+        of x_nom - the terminal term towards index N - 1's row; past its end the reference holds its last row.  MPCRun moves the
+        clock by replan_steps per re-solve (target_clock).  A one-row reference is the constant target SetTargetState gives, bit
+        for bit.  None clears it: the solver is back on x_nom, as if it had never held one.  Takes effect at once; survives
+        Reset().  Workgroup-per-problem models only; not together with SetPlant / RolloutPolicy."""
+        rows, c = check_target_trajectory(x_ref, clock, self.B, self.n)
+        rc = self._lib.mi_ilqr_set(self._h, _capi.F_X_REF, _capi.ptr(rows), 0 if rows is None else rows.nbytes)
+        if rc == _capi.E_UNSUPPORTED:
+            if self._holds_plant():
+                raise ValueError("SetTargetTrajectory: this solver holds a plant (SetPlant), and the plant kernels know constant "
+                                 "targets only; ClearPlant() first")
+            raise ValueError("SetTargetTrajectory: reference trajectories are served by the workgroup-per-problem kernel family "
+                             f"only; this model (n = {self.n}, m = {self.m}) runs on the wave-per-problem or the lane-per-problem "
+                             "family")
+        _capi.check(rc, "mi_ilqr_set")
+        if rows is not None:               # (clearing the reference has reset the clock)
+            cl = np.array([float(c)])
+            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_REF_CLOCK, _capi.ptr(cl), cl.nbytes), "mi_ilqr_set")
+        self._ref_T = 0 if rows is None else rows.shape[1]
+
+    def _holds_plant(self):
+        out = np.empty((self.B, self.n))
+        return self._lib.mi_ilqr_get(self._h, _capi.F_PLANT_STATE, _capi.ptr(out), out.nbytes) == _capi.OK
+
+    def _tracking(self):
+        """Whether the HANDLE holds a reference (it may have been set, or lost, through the C ABI): MI_F_X_REF answers
+        MI_ILQR_E_BAD_ARG without one, and with one MI_ILQR_OK or - a length other than the one this object last set - BAD_SHAPE."""
+        probe = np.empty((self.B, max(self._ref_T, 1), self.n))
+        return self._lib.mi_ilqr_get(self._h, _capi.F_X_REF, _capi.ptr(probe), probe.nbytes) != _capi.E_BAD_ARG
+
+    @property
+    def target_trajectory(self):
+        """(B, T, n): the reference the solver holds (SetTargetTrajectory), or None."""
+        if not self._tracking():
+            return None
+        out = np.empty((self.B, self._ref_T, self.n))
+        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_X_REF, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+        return out
+
+    @property
+    def target_clock(self):
+        """The row of the reference the next solve's window starts at (SetTargetTrajectory's clock, advanced by MPCRun); 0 without one."""
+        if not self._tracking():
+            return 0
+        out = np.empty(1)
+        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_REF_CLOCK, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+        return int(out[0])
 
     def SetModelParameters(self, params):
         """(B, n_params): every problem its own plant - the reference's one solver object per System, B of them in one handle
@@ -702,6 +781,9 @@ class BatchedIterativeLQR:
         On a solver that holds a plant (SetPlant) this is the CLOSED loop: before every re-solve the plant advances replan_steps
         steps under the policy of the previous solve, and the re-solve starts from the plant's state instead of the prediction
         x_bar[:, replan_steps] (include/mi_ilqr.h: "Closed-loop MPC"); `plant_log` has the plant's record."""
+        if self._tracking() and target_step is not None:
+            raise ValueError("MPCRun: this solver holds a reference trajectory (SetTargetTrajectory) - it is the reference that "
+                             "moves the target, replan_steps rows per re-solve; target_step must be None")
         ts = None
         steps = None if target_step is None else np.asarray(target_step, dtype=np.float64)
         per_problem = self._per_problem_targets() or (steps is not None and steps.shape == (self.B, self.n) and steps.size != self.n)
@@ -784,6 +866,9 @@ class BatchedIterativeLQR:
         noisy = state_noise is not None or control_noise is not None
         rows, stream = check_noise_args(state_noise, control_noise, seed, first_sample, common_noise, self.B, self.n, self.m,
                                         self._md if noisy else None, x0.shape[1] if noisy else None)
+        if self._tracking():
+            raise ValueError("RolloutPolicy: this solver holds a reference trajectory (SetTargetTrajectory), and the policy kernels "
+                             "cost a rollout against a constant target only; SetTargetTrajectory(None) first")
         self._push_costs()
         if rows is not None:
             _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_STREAM, _capi.ptr(stream), stream.nbytes), "mi_ilqr_set")
@@ -813,6 +898,9 @@ class BatchedIterativeLQR:
         MPCRun advances (plant_clock).  Survives Reset(); ClearPlant() returns to the open loop."""
         x, params, noise, stream = check_plant_args(x, params, state_noise, control_noise, seed, common_noise, feedback, clock, self.B, self.n,
                                                     self.m, int(self.system.params.size), self._md)
+        if self._tracking():
+            raise ValueError("SetPlant: this solver holds a reference trajectory (SetTargetTrajectory), and the plant kernels know "
+                             "constant targets only; SetTargetTrajectory(None) first")
         st = lambda which, a: _capi.check(self._lib.mi_ilqr_set(self._h, which, _capi.ptr(a), 0 if a is None else a.nbytes), "mi_ilqr_set")   # noqa: E731
         if int(self.system.params.size):
             st(_capi.F_PLANT_PARAMS, params)
@@ -1003,6 +1091,12 @@ class IterativeLinearQuadraticRegulator(BatchedIterativeLQR):
         return super().RolloutPolicy(x0, params, trajectories, state_noise=state_noise, control_noise=control_noise, seed=seed,
                                      first_sample=first_sample, common_noise=common_noise)._without_batch_axis()
 
+    def SetTargetTrajectory(self, x_ref, clock=0):
+        """x_ref (T, n) or None: BatchedIterativeLQR.SetTargetTrajectory."""
+        if x_ref is not None and np.ndim(x_ref) != 2:
+            raise ValueError(f"SetTargetTrajectory: the reference must be (T, {self.n}); got {np.shape(x_ref)}")
+        super().SetTargetTrajectory(x_ref, clock)
+
     def SetPlant(self, x, params=None, **kw):
         """x (n,), params None or (n_params,), sigmas scalar or (n,) / (m,): BatchedIterativeLQR.SetPlant."""
         if np.ndim(x) != 1:
@@ -1012,6 +1106,8 @@ class IterativeLinearQuadraticRegulator(BatchedIterativeLQR):
         super().SetPlant(x, params, **kw)
 
     plant_state = property(lambda s: BatchedIterativeLQR.plant_state.fget(s)[0])
+    target_trajectory = property(lambda s: (lambda r: None if r is None else r[0])(BatchedIterativeLQR.target_trajectory.fget(s)),
+                                 doc="(T, n): the reference the solver holds (SetTargetTrajectory), or None.")
     plant_log = property(lambda s: BatchedIterativeLQR.plant_log.fget(s)._without_batch_axis())
 
     def SaveSolution(self, fname):

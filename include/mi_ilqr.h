@@ -133,6 +133,8 @@ enum {
   MI_F_PLANT_STREAM = 24,    /* (4,) seed | clock | common | feedback of the plants, integers held in doubles */
   MI_F_PLANT_LOG = 25,       /* (B,num_resolves*replan_steps,n+m+1) read-only: rows x_k | u_k | l_k of the last closed-loop mi_ilqr_mpc_run */
   MI_F_PLANT_KERNEL_MS = 26, /* (1,) read-only: milliseconds of the plant kernels of the last closed-loop mi_ilqr_mpc_run, summed, from their own HIP events */
+  MI_F_X_REF = 27,           /* (B,T,n) reference trajectories: time-varying targets, T from the byte count ("Reference trajectories" below) */
+  MI_F_REF_CLOCK = 28,       /* (1,) the row of the reference a solve's window starts at, an integer held in a double */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
@@ -274,6 +276,30 @@ int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const doubl
  *   mi_ilqr_set_cost with a non-NULL x_nom returns the handle to shared mode and drops both fields: it is then bitwise a
  *   never-per-problem one.  Targets are problem data: they survive mi_ilqr_reset.  Wrong `bytes` is MI_ILQR_E_BAD_SHAPE, a NaN
  *   MI_ILQR_E_BAD_ARG (the handle keeps what it had).  Every kernel family, solve, mpc_run and the stage entries. */
+
+/* Reference trajectories (time-varying targets: a path to TRACK inside the horizon; no counterpart in the reference, whose target
+ * stands still).  A handle may hold a reference x_ref, (B,T,n) with T >= 1, and an integer clock c >= 0.  While it does, every place
+ * a solve uses x_nom at time index t = 0 .. N-1 (the terminal term included) uses r_t = x_ref[b, min(c + t, T-1), :] instead: past
+ * its end the reference holds its last row.  Q, R, Qf stay what they are (shared or per problem, symmetric or not); MI_F_X_NOM and
+ * the shared x_nom are kept but ignored while a reference is held.
+ *   mi_ilqr_set(MI_F_X_REF, rows, B*T*n*8)  sets the reference; T follows from `bytes` (not a whole multiple >= 1 of B*n*8:
+ *                                           MI_ILQR_E_BAD_SHAPE).  The clock stays what it was.  (NULL, 0) clears the reference and
+ *                                           sets the clock to 0: the handle is then bitwise one that never held a reference.
+ *   mi_ilqr_set(MI_F_REF_CLOCK, &c, 8)      the clock, an integer in [0, 2^30) held in a double (else MI_ILQR_E_BAD_ARG).
+ *   mi_ilqr_get reads both back (MI_F_X_REF: `bytes` = B*T*n*8, without a reference MI_ILQR_E_BAD_ARG).
+ *   mi_ilqr_solve, the resident and stage entries use the window at the current clock.  mi_ilqr_mpc_run: re-solve k = 1 .. num_resolves
+ *   uses the window at c + k replan_steps - the reference moves the target, so target_step must be NULL (else MI_ILQR_E_BAD_ARG) -
+ *   and leaves the clock at c + num_resolves replan_steps (a run that returns an error leaves the clock where it was); the
+ *   single-launch and host-loop forms agree.  A reference of ONE row is bitwise the constant target MI_F_X_NOM with that row.
+ *   mi_ilqr_mpc_run(R, r) is bitwise R calls of mi_ilqr_mpc_run(1, r) on the n = 33..40 kernels.  On the mid-size ones (n <= 32:
+ *   Arm27, Arm27C, family-1 plugins) it is NOT under the default candidate policy, with a reference as with a constant target: that
+ *   policy rolls four line-search candidates out once a problem has backtracked in the CURRENT launch, and which search ran decides
+ *   how the cost gradients are rounded.  The forms then agree to round-off (bitwise under MI_ILQR_SPEC=2, which knows no launch).
+ *   With the first reference the handle allocates a (B, N-1, n) device scratch the kernels fill with 2 r_t^T Q of the window.
+ * Workgroup-per-problem kernels only (n > 8 models): handles of the wave- and lane-per-problem families return MI_ILQR_E_UNSUPPORTED.
+ * A handle that holds a reference refuses MI_F_PLANT_STATE and mi_ilqr_policy_rollout, a handle that holds a plant refuses a
+ * reference (MI_ILQR_E_UNSUPPORTED both ways: the plant and policy kernels know constant targets only).  Problem data: survives
+ * mi_ilqr_reset.  A NaN or an infinity is MI_ILQR_E_BAD_ARG; a refused call changes nothing. */
 
 /* Per-problem model parameters (the reference builds one solver object per System: B objects may be B plants of one structure -
  * domain-randomised MPC, parameter sweeps, picking the plant whose plan matches a measurement).  The model, dt and the costs stay
