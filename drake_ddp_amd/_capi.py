@@ -36,7 +36,14 @@ F_POLICY_STREAM = 20              # (3,) seed | first_sample | common of their r
 F_PLANT_STATE, F_PLANT_PARAMS, F_PLANT_NOISE, F_PLANT_STREAM, F_PLANT_LOG, F_PLANT_KERNEL_MS = 21, 22, 23, 24, 25, 26
 # reference trajectories (mi_ilqr.h: "Reference trajectories"): (B, T, n) time-varying targets | (1,) the row a solve's window starts at
 F_X_REF, F_REF_CLOCK = 27, 28
+# Monte-Carlo on the device (mi_ilqr.h: "Monte-Carlo on the device"): (B, 3n+2n_params) sampler rows x0_mean | x0_spread | goal | p_mean |
+# p_spread | write-only command (5,) S | x0_dist | p_dist | sample_params | samples | read-only (B, 10) S | counted | success | mean | M2 |
+# min | max | argmin | argmax | steps_total | read-only (B, S, n+n_params+2) rows x0 | params | cost | steps
+F_POLICY_MC_DIST, F_POLICY_MC_RUN, F_POLICY_MC_STATS, F_POLICY_MC_SAMPLES = 29, 30, 31, 32
+MC_DIST_NORMAL, MC_DIST_UNIFORM = 0, 1
+MC_FIELDS = 10
 I_ITERS, I_STATUS, I_LS_TRIALS, I_KP_COUNT, I_KP_LIST = 100, 101, 102, 103, 104
+I_POLICY_MC_PASSES = 105    # (1,) passes over windows of sample groups of the last on-device Monte-Carlo run
 I64_STAGE_CYCLES = 200
 I64_CLUSTER_WORDS = 201
 CLUSTER_WORDS = 40          # MI_ILQR_CLUSTER_WORDS

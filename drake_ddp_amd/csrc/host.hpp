@@ -138,6 +138,19 @@ struct mi_ilqr {
   unsigned long long policy_seed = 0;
   uint32_t policy_first_sample = 0;
   bool policy_common = false;
+  // Monte-Carlo on the device (MI_F_POLICY_MC_DIST / _RUN / _STATS / _SAMPLES; policy_mc.hpp).  policy_mc_dist: (B, 3 n + 2 n_params)
+  // sampler rows x0_mean | x0_spread | goal | p_mean | p_spread, problem data like the noise rows.  mc_acc: the fold's running
+  // accumulator on the device, (10, B) problem-minor; mc_stats: the last run's (B, 10) result (empty: no run yet); mc_samples: its
+  // (B, S, n + n_params + 2) rows when it was asked for them (else empty), on the host - what the selectors return.  mc_events: the
+  // start / stop pairs of the passes over windows of groups (a fixed few, used in turn); mc_ms: the rollout kernels of the last run, summed - what
+  // MI_F_POLICY_KERNEL_MS reports while policy_last_mc says that the last policy launch was such a run.
+  RowStore policy_mc_dist;
+  double* mc_acc = nullptr;
+  std::vector<double> mc_stats, mc_samples;
+  std::vector<hipEvent_t> mc_events;
+  double mc_ms = 0.0;
+  int32_t mc_passes = 0;           // passes of the last run (MI_I_POLICY_MC_PASSES)
+  bool policy_last_mc = false;
   // the plant of the closed receding-horizon loop (mi_ilqr_mpc_run; plant_advance.hpp).  plant_state: (B, n), `synced` = the handle
   // holds a plant - its device rows ARE the plant (the kernel advances them in place, mi_ilqr_mpc_run brings the mirror up to date);
   // plant_params: (B, n_params), not synced = every plant runs on its problem's model row; plant_noise: (B, n + m) sigma_x | sigma_u,
@@ -164,6 +177,7 @@ struct Switches {
   int cluster_order;     // MI_ILQR_CLUSTER_ORDER: placement of a cluster's workgroups (default 2)
   int early;             // MI_ILQR_EARLY: early linearization by the helpers (default 1)
   int ls_groups;         // MI_ILQR_LS_GROUPS: candidate groups (default 1)
+  int mc_pass_groups;    // MI_ILQR_MC_PASS_GROUPS: groups of 64 samples per pass of the on-device Monte-Carlo, forced when > 0 (tests)
 };
 MI_INTERNAL inline const Switches& switches() {
   static const Switches s = [] {
@@ -173,7 +187,8 @@ MI_INTERNAL inline const Switches& switches() {
     const int spec = num("MI_ILQR_SPEC", 1);
     return Switches{on("MI_ILQR_NO_HELPER"), on("MI_ILQR_SEQ_BACKWARD"), on("MI_ILQR_SEQ_ROLLOUT"),
                     !stats ? -1 : (stats[0] == '1' ? 1 : 0), (spec >= 0 && spec <= 2) ? spec : 0, num("MI_ILQR_CLUSTER", 0),
-                    num("MI_ILQR_CLUSTER_ORDER", 2), num("MI_ILQR_EARLY", 1), num("MI_ILQR_LS_GROUPS", 1)};
+                    num("MI_ILQR_CLUSTER_ORDER", 2), num("MI_ILQR_EARLY", 1), num("MI_ILQR_LS_GROUPS", 1),
+                    num("MI_ILQR_MC_PASS_GROUPS", 0)};
   }();
   return s;
 }
@@ -217,6 +232,9 @@ constexpr int kModePolicyRollout = 0x504f4c;
 // mi_ilqr_mpc_run on a handle that holds a plant: the launch entry takes a PlantArgs (below) and launches plant_advance_kernel<M>
 // (plant_advance.hpp), again whatever the handle's kernel family.
 constexpr int kModePlantAdvance = 0x504c54;
+// mi_ilqr_set(MI_F_POLICY_MC_RUN): the launch entry takes a PolicyMcArgs (below) and launches policy_mc_kernel<M> and the fold behind
+// it (policy_mc.hpp) for one window of sample groups.
+constexpr int kModePolicyMC = 0x504d43;
 constexpr int kMaxBatchPluginN = 6;      // family-0 models up to this n also get the lane-per-problem kernels
 
 // The dynamic-LDS ceiling of a kernel is raised once per (kernel, device), to the hardware maximum - not
@@ -305,6 +323,29 @@ struct PolicyArgs {
 template <class M> MI_INTERNAL int launch_policy_rollout(mi_ilqr* h, const PolicyArgs& a);          // policy_rollout.hpp; k_policy.hip
 template <class M> MI_INTERNAL int launch_policy_rollout_noise(mi_ilqr* h, const PolicyArgs& a);    // ... k_policy_noise.hip
 
+// Arguments of one pass of the on-device Monte-Carlo (policy_mc.hpp: policy_mc_kernel<M> and policy_mc_fold_kernel), device pointers.
+// kMcFields: the doubles of a per-problem result and of a group's partial, S | counted | success | mean | M2 | min | max | argmin |
+// argmax | steps_total.
+constexpr int kMcFields = 10;
+struct PolicyMcArgs {
+  PolicyArgs r;               // the rollout's: policy, param_rows, cost, x_nom, ulim, noise, the strides, dt, N, B, m_user and the stream
+                              // (x0, params, S and the outputs are not used: the samples are drawn, S is below)
+  const double* dist;         // (B, 3 n + n_params 2) sampler rows x0_mean | x0_spread | goal | p_mean | p_spread
+  double* partials;           // (groups, 10, B) problem-minor: this window's group partials
+  double* acc;                // (10, B) problem-minor: the running accumulator
+  double* samples;            // (B, n + n_params + 2, win_samples) sample-minor rows x0 | params | cost | steps of this window, or nullptr
+  unsigned long long S;       // the call's samples per problem
+  size_t win_samples;         // ... and this window's
+  uint32_t group0;            // the window: groups group0 .. group0 + groups - 1 of every problem
+  int32_t groups;
+  int32_t x0_dist, p_dist;    // 0 normal, 1 uniform
+  int32_t sample_params;      // the plants' parameters are drawn too (models with parameters)
+  int32_t first_pass;         // the accumulator starts empty
+  hipEvent_t ev0, ev1;        // the rollout kernel's start / stop events of this pass
+};
+template <class M> MI_INTERNAL int launch_policy_mc(mi_ilqr* h, const PolicyMcArgs& a);             // policy_mc.hpp; k_policy_mc.hip
+template <class M> MI_INTERNAL int launch_policy_mc_noise(mi_ilqr* h, const PolicyMcArgs& a);       // ... k_policy_mc_noise.hip
+
 // Arguments of plant_advance_kernel<M> (plant_advance.hpp), all device pointers.  "Problem-minor": element e of problem b at e * B + b.
 struct PlantArgs {
   const double* policy;       // (steps, n + m + m n, B) problem-minor: row j = x_bar_j | u_bar_j | K_j (m x n, row-major), the first `steps` columns
@@ -346,6 +387,10 @@ int model_entry(mi_ilqr* h, int mode, const void* kargs) {
   if (mode == kModePolicyRollout) {
     const PolicyArgs& a = *static_cast<const PolicyArgs*>(kargs);
     return a.noise ? launch_policy_rollout_noise<M>(h, a) : launch_policy_rollout<M>(h, a);
+  }
+  if (mode == kModePolicyMC) {
+    const PolicyMcArgs& a = *static_cast<const PolicyMcArgs*>(kargs);
+    return a.r.noise ? launch_policy_mc_noise<M>(h, a) : launch_policy_mc<M>(h, a);
   }
   if (mode == kModePlantAdvance) {
     const PlantArgs& a = *static_cast<const PlantArgs*>(kargs);

@@ -680,6 +680,7 @@ RowField row_field(mi_ilqr* h, int which) {
     case MI_F_PLANT_STATE: return {&h->plant_state, nullptr};          // (mi_ilqr_get refuses it while the handle holds no plant)
     case MI_F_PLANT_PARAMS: return {&h->plant_params, h->d.model_params};   // (not set: the problem's model row, get_plant_field)
     case MI_F_PLANT_NOISE: return {&h->plant_noise, nullptr};
+    case MI_F_POLICY_MC_DIST: return {&h->policy_mc_dist, nullptr};    // (not set: zeros)
   }
   return {nullptr, nullptr};
 }
@@ -998,6 +999,7 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   h->params.width = model.n_params;
   h->costs.width = cost_len(h);
   h->policy_noise.width = h->plant_noise.width = h->n + h->m;
+  h->policy_mc_dist.width = 3 * (size_t)h->n + 2 * (size_t)model.n_params;
   h->plant_state.width = h->n;
   h->plant_params.width = model.n_params;
   h->params.batch_minor_copy = h->costs.batch_minor_copy = batch_minor;   // (what the lane kernels read batch-minor: KArgs::param_cols, cost_cols)
@@ -1022,6 +1024,7 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
   if (h->pin_ev) (void)hipEventDestroy(h->pin_ev);
   if (h->policy_ev0) (void)hipEventDestroy(h->policy_ev0);
   if (h->policy_ev1) (void)hipEventDestroy(h->policy_ev1);
+  for (hipEvent_t e : h->mc_events) (void)hipEventDestroy(e);
   if (h->plant_ev0) (void)hipEventDestroy(h->plant_ev0);
   if (h->plant_ev1) (void)hipEventDestroy(h->plant_ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1705,7 +1708,7 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
   a.cost_out = sc + o_cost; a.x_final = sc + o_xf; a.steps = reinterpret_cast<int32_t*>(sc + o_steps);
   a.X = X ? sc + o_X : nullptr; a.U = U ? sc + o_U : nullptr;
   a.dt = h->d.dt; a.N = (int32_t)N; a.S = S; a.B = (int32_t)B; a.m_user = model->p.m_user > 0 ? model->p.m_user : (int32_t)m;
-  h->policy_ran = false;
+  h->policy_ran = h->policy_last_mc = false;
   if ((rc = model->p.launch(h, kModePolicyRollout, &a)) != MI_ILQR_OK) return rc;
   h->policy_ran = true;
   // sample-minor -> the boundary's layouts: x_final (B,S,n), X (B,S,n,N), U (B,S,m,N-1)
@@ -1725,6 +1728,150 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
     HIPCHK(hipMemcpyAsync(U, sc + o_U_out, B * Sz * m * (N - 1) * 8, hipMemcpyDeviceToHost, h->stream));
   }
   HIPCHK(hipStreamSynchronize(h->stream));
+  return MI_ILQR_OK;
+}
+
+// Monte-Carlo on the device (include/mi_ilqr.h).  MI_F_POLICY_MC_DIST: (B, 3 n + 2 n_params) rows x0_mean | x0_spread | goal |
+// p_mean | p_spread - means and spreads finite, spreads and goals non-negative, a goal may be +inf; src == NULL with bytes == 0
+// clears the rows.  A refused call changes nothing.
+static int set_mc_dist(mi_ilqr* h, const double* src, size_t bytes) {
+  RowStore& s = h->policy_mc_dist;
+  const size_t n = h->n, w = s.width, np = (w - 3 * n) / 2, cnt = (size_t)h->B * w;
+  if (!src && bytes == 0) { store_drop(s); return MI_ILQR_OK; }
+  if (bytes != cnt * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  for (size_t i = 0; i < cnt; ++i) {
+    const size_t c = i % w;
+    const double v = src[i];
+    const bool goal = c >= 2 * n && c < 3 * n, spread = (c >= n && c < 2 * n) || c >= 3 * n + np;
+    if (std::isnan(v) || (!goal && !std::isfinite(v)) || ((goal || spread) && v < 0.0)) return MI_ILQR_E_BAD_ARG;
+  }
+  return store_upload(h, s, src);
+}
+
+// MI_F_POLICY_MC_RUN: v = S | x0_dist | p_dist | sample_params | samples.  Draws, rolls out and reduces S samples per problem on the
+// handle's stream - passes over windows of sample groups, each one rollout kernel and one fold (policy_mc.hpp) - and synchronizes
+// once.  Nothing of the handle's solver state is written; the staging memory is the grow-only scratch.
+constexpr size_t kMcWindowBytes = 64u << 20;      // what the partials and the optional sample buffers of one pass may take
+constexpr unsigned long long kMcEventPairs = 32;  // event pairs a handle keeps for the passes of a run
+static int run_policy_mc(mi_ilqr* h, const double* v, size_t bytes) {
+  if (bytes != 5 * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!v) return MI_ILQR_E_BAD_ARG;
+  if (!(v[0] >= 1.0 && v[0] <= 0x1p32 && v[0] == std::floor(v[0]))) return MI_ILQR_E_BAD_ARG;
+  for (int i = 1; i < 5; ++i) if (!(v[i] == 0.0 || v[i] == 1.0)) return MI_ILQR_E_BAD_ARG;
+  if (h->reference.synced) return MI_ILQR_E_UNSUPPORTED;      // (the policy kernels cost a rollout against a constant target only)
+  if (!h->policy_mc_dist.synced) return MI_ILQR_E_BAD_ARG;
+  const unsigned long long S = (unsigned long long)v[0];
+  if ((unsigned long long)h->policy_first_sample + S > 0x100000000ull) return MI_ILQR_E_BAD_ARG;   // (the sample counter is 32 bits)
+  const Model* model = model_of(h->d.model_id);
+  const size_t B = h->B, n = h->n, m = h->m, N = h->N, np = model->p.n_params, W = n + m + m * n, SW = n + np + 2;
+  const bool sample_params = v[3] == 1.0, want_samples = v[4] == 1.0;
+  if (sample_params && np == 0) return MI_ILQR_E_UNSUPPORTED;
+  HIPCHK(hipSetDevice(h->d.device_id));
+  // the window: as many groups of 64 samples per pass as the cap allows (MI_ILQR_MC_PASS_GROUPS forces it)
+  const unsigned long long G = (S + 63) / 64;
+  const size_t group_bytes = (size_t)kMcFields * B * 8 + (want_samples ? 2 * B * 64 * SW * 8 : 0);
+  unsigned long long k = std::max<unsigned long long>(1, kMcWindowBytes / group_bytes);
+  if (switches().mc_pass_groups > 0) k = (unsigned long long)switches().mc_pass_groups;
+  k = std::min(std::min(k, G), std::max<unsigned long long>(1, 0x7fffffffull / B));
+  const unsigned long long passes = (G + k - 1) / k;
+  std::vector<double> samples;
+  if (want_samples) {
+    if (S > (unsigned long long)(SIZE_MAX / 8) / (B * SW)) return MI_ILQR_E_UNSUPPORTED;
+    try { samples.resize(B * (size_t)S * SW); } catch (const std::bad_alloc&) { return MI_ILQR_E_UNSUPPORTED; }
+  }
+  size_t off = 0;
+  auto take = [&](size_t count) { const size_t o = off; off += (count + 31) & ~(size_t)31; return o; };
+  const size_t win_max = (size_t)k * 64;
+  const size_t o_pol = take(B * (N - 1) * W), o_prow = take(np ? np : 1), o_part = take((size_t)k * kMcFields * B);
+  const size_t o_smp = take(want_samples ? B * SW * win_max : 0), o_smp_out = take(want_samples ? B * win_max * SW : 0);
+  int rc = ensure_scratch(h, off * 8);
+  if (rc != MI_ILQR_OK) return rc;
+  double* const sc = h->scratch;
+  if (!h->mc_acc && (rc = dev_alloc(h, h->mc_acc, (size_t)kMcFields * B)) != MI_ILQR_OK) return rc;
+  // one start / stop pair per pass, at most kMcEventPairs of them: a run of more passes waits for the stream every kMcEventPairs
+  // passes, adds their times up and uses the pairs again
+  const size_t pairs = (size_t)std::min<unsigned long long>(passes, kMcEventPairs);
+  while (h->mc_events.size() < 2 * pairs) {
+    hipEvent_t e = nullptr;
+    HIPCHK(hipEventCreate(&e));
+    h->mc_events.push_back(e);
+  }
+  // the policy as the handle holds it now (mi_ilqr_policy_rollout's rules)
+  const double* u_src = h->u_pending ? h->u_guess : (h->u_zero ? nullptr : h->u_bar);
+  {
+    const size_t total = B * (N - 1) * W;
+    const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
+    hipLaunchKernelGGL(policy_pack_kernel, dim3(blocks), dim3(256), 0, h->stream, h->cold ? nullptr : h->x_bar, u_src,
+                       h->cold ? nullptr : h->K, sc + o_pol, (int)B, (int)n, (int)m, (int)N, layout_of(h));
+    HIPCHK(hipGetLastError());
+  }
+  if (np && !h->params.synced && (rc = stage_h2d(h, sc + o_prow, h->d.model_params, np * 8)) != MI_ILQR_OK) return rc;
+  PolicyMcArgs a{};
+  auto rows_or = [](const RowStore& s, const double* shared_row, size_t* stride) {
+    *stride = s.synced ? s.width : 0;
+    return s.synced ? s.rows : shared_row;
+  };
+  a.r.policy = sc + o_pol;
+  a.r.param_rows = rows_or(h->params, sc + o_prow, &a.r.param_stride);
+  a.r.cost = rows_or(h->costs, h->costmat, &a.r.cost_stride);
+  a.r.x_nom = rows_or(h->targets, h->costmat + cost_len(h), &a.r.x_nom_stride);
+  a.r.ulim = h->limited ? h->ulim : nullptr;
+  a.r.noise = h->policy_noise.synced ? h->policy_noise.rows : nullptr;
+  a.r.seed = h->policy_seed; a.r.first_sample = h->policy_first_sample; a.r.common = h->policy_common ? 1 : 0;
+  a.r.dt = h->d.dt; a.r.N = (int32_t)N; a.r.B = (int32_t)B; a.r.m_user = model->p.m_user > 0 ? model->p.m_user : (int32_t)m;
+  a.dist = h->policy_mc_dist.rows; a.partials = sc + o_part; a.acc = h->mc_acc; a.samples = want_samples ? sc + o_smp : nullptr;
+  a.S = S; a.x0_dist = (int32_t)v[1]; a.p_dist = (int32_t)v[2]; a.sample_params = sample_params ? 1 : 0;
+  // From here on copies into `samples` and `acc` may be queued on the stream: whatever fails, the stream is waited for before
+  // the two go out of scope.
+  std::vector<double> acc((size_t)kMcFields * B);
+  double ms_sum = 0.0;
+  auto timed = [&](unsigned long long used) -> int {          // the stream is idle: add the kernels of the pairs in use
+    for (unsigned long long q = 0; q < used; ++q) {
+      float ms = 0.0f;
+      HIPCHK(hipEventElapsedTime(&ms, h->mc_events[2 * q], h->mc_events[2 * q + 1]));
+      ms_sum += (double)ms;
+    }
+    return MI_ILQR_OK;
+  };
+  auto passes_and_copies = [&]() -> int {
+    unsigned long long pass = 0;
+    for (unsigned long long g0 = 0; g0 < G; g0 += k, ++pass) {
+      const unsigned long long kg = std::min(k, G - g0), s0 = g0 * 64, slot = pass % kMcEventPairs;
+      if (pass > 0 && slot == 0) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (const int rt = timed(kMcEventPairs); rt != MI_ILQR_OK) return rt;
+      }
+      const size_t win = (size_t)std::min<unsigned long long>(S - s0, kg * 64);
+      a.group0 = (uint32_t)g0; a.groups = (int32_t)kg; a.win_samples = win; a.first_pass = pass == 0 ? 1 : 0;
+      a.ev0 = h->mc_events[2 * slot]; a.ev1 = h->mc_events[2 * slot + 1];
+      if (const int rl = model->p.launch(h, kModePolicyMC, &a); rl != MI_ILQR_OK) return rl;
+      if (want_samples) {     // sample-minor (B, SW, win) -> (B, win, SW), then rows s0 .. s0 + win - 1 of every problem's block
+        if (const int rt = transpose_tiles(h, sc + o_smp, sc + o_smp_out, (int)SW, (int)win, B, 1, SW * win, 0, win, win * SW, 0, SW);
+            rt != MI_ILQR_OK) return rt;
+        HIPCHK(hipMemcpy2DAsync(samples.data() + (size_t)s0 * SW, (size_t)S * SW * 8, sc + o_smp_out, win * SW * 8, win * SW * 8, B,
+                                hipMemcpyDeviceToHost, h->stream));
+      }
+    }
+    HIPCHK(hipMemcpyAsync(acc.data(), h->mc_acc, acc.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return timed((passes - 1) % kMcEventPairs + 1);
+  };
+  if ((rc = passes_and_copies()) != MI_ILQR_OK) {
+    (void)hipStreamSynchronize(h->stream);
+    return rc;
+  }
+  // (10, B) -> (B, 10); a problem without a counted sample: mean = M2 = NaN (min = +inf, max = -inf, argmin = argmax = -1 as folded)
+  h->mc_stats.assign(B * kMcFields, 0.0);
+  for (size_t b = 0; b < B; ++b) {
+    double* row = h->mc_stats.data() + b * kMcFields;
+    for (int f = 0; f < kMcFields; ++f) row[f] = acc[(size_t)f * B + b];
+    if (row[1] == 0.0) row[3] = row[4] = std::nan("");
+  }
+  h->mc_samples.swap(samples);
+  h->mc_ms = ms_sum;
+  h->mc_passes = (int32_t)std::min<unsigned long long>(passes, 0x7fffffffull);
+  h->policy_last_mc = true;
   return MI_ILQR_OK;
 }
 
@@ -2014,8 +2161,16 @@ int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
     dst[0] = (double)h->policy_seed; dst[1] = (double)h->policy_first_sample; dst[2] = h->policy_common ? 1.0 : 0.0;
     return MI_ILQR_OK;
   }
+  if (which == MI_F_POLICY_MC_STATS || which == MI_F_POLICY_MC_SAMPLES) {      // the last run's results, host copies
+    const std::vector<double>& r = which == MI_F_POLICY_MC_STATS ? h->mc_stats : h->mc_samples;
+    if (r.empty()) return MI_ILQR_E_BAD_ARG;
+    if (bytes != r.size() * 8) return MI_ILQR_E_BAD_SHAPE;
+    std::memcpy(dst, r.data(), bytes);
+    return MI_ILQR_OK;
+  }
   if (which == MI_F_POLICY_KERNEL_MS) {        // the rollout kernel of the last mi_ilqr_policy_rollout, from its own events
     if (bytes != 8) return MI_ILQR_E_BAD_SHAPE;
+    if (h->policy_last_mc) { *dst = h->mc_ms; return MI_ILQR_OK; }      // (an on-device Monte-Carlo run: its rollout kernels, summed over the passes)
     if (!h->policy_ran) return MI_ILQR_E_BAD_ARG;
     float ms = 0.0f;
     HIPCHK(hipSetDevice(h->d.device_id));
@@ -2082,6 +2237,12 @@ int mi_ilqr_get_int(mi_ilqr_t* h, int which, int32_t* dst, size_t bytes) {
     std::memset(dst, 0, bytes);
     return MI_ILQR_OK;
   }
+  if (which == MI_I_POLICY_MC_PASSES) {          // the passes of the last on-device Monte-Carlo run (a host value)
+    if (h->mc_stats.empty()) return MI_ILQR_E_BAD_ARG;
+    if (bytes != 4) return MI_ILQR_E_BAD_SHAPE;
+    *dst = h->mc_passes;
+    return MI_ILQR_OK;
+  }
   Field f = field_of(h, which);
   if (!f.ptr || !f.is_int) return MI_ILQR_E_BAD_ARG;
   if (bytes != f.bytes) return MI_ILQR_E_BAD_SHAPE;
@@ -2096,6 +2257,8 @@ int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
   if (h && which == MI_F_COST_MATRICES) return set_cost_rows(h, src, bytes);     // (the same)
   if (h && which == MI_F_POLICY_NOISE) return set_noise_rows(h, h->policy_noise, src, bytes);   // (src == NULL, bytes == 0: no noise)
   if (h && which == MI_F_POLICY_STREAM) return set_policy_stream(h, src, bytes);
+  if (h && which == MI_F_POLICY_MC_DIST) return set_mc_dist(h, src, bytes);      // (src == NULL, bytes == 0: no sampler rows)
+  if (h && which == MI_F_POLICY_MC_RUN) return run_policy_mc(h, src, bytes);     // (a command: runs the evaluation)
   if (h && which == MI_F_PLANT_STATE) return set_plant_state(h, src, bytes);     // (src == NULL, bytes == 0: no plant)
   if (h && which == MI_F_PLANT_PARAMS) return set_plant_params(h, src, bytes);   // (the same: the problems' model rows)
   if (h && which == MI_F_PLANT_NOISE) return set_noise_rows(h, h->plant_noise, src, bytes);

@@ -65,6 +65,26 @@ __device__ __forceinline__ double row16_sum(double p) {
   return p;
 }
 
+// value of lane (this lane ^ D) of this lane's 16-lane row, D = 1, 2, 4, 8 - the partner of a butterfly level: quad permutations
+// for 1 and 2, the half-row mirror (^ 7) followed by the reversed quad (^ 3) for 4, the rotation by 8 for 8.  DPP moves only.
+template <int D>
+__device__ __forceinline__ int row_xor_i32(int v) {
+  static_assert(D == 1 || D == 2 || D == 4 || D == 8, "a lane distance inside a 16-lane row");
+  if constexpr (D == 1) return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);                    // quad_perm:[1,0,3,2]
+  else if constexpr (D == 2) return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);               // quad_perm:[2,3,0,1]
+  else if constexpr (D == 4)
+    return __builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true), 0x1B, 0xF, 0xF, true);   // row_half_mirror, quad_perm:[3,2,1,0]
+  else return __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, true);                                    // row_ror:8
+}
+template <int D>
+__device__ __forceinline__ double row_xor_f64(double v) {
+  union { double d; int i[2]; } u, r;
+  u.d = v;
+  r.i[0] = row_xor_i32<D>(u.i[0]);
+  r.i[1] = row_xor_i32<D>(u.i[1]);
+  return r.d;
+}
+
 // value of lane LANE of this lane's 16-lane row, for a double: one v_mov_b64_dpp row_newbcast
 // (gfx90a+ DPP64).  bound_ctrl with full row/bank masks: every lane is written.
 template <int LANE>

@@ -207,6 +207,115 @@ def check_plant_args(x, params, state_noise, control_noise, seed, common_noise, 
     return x, params, noise, stream
 
 
+MC_DISTS = {"normal": _capi.MC_DIST_NORMAL, "uniform": _capi.MC_DIST_UNIFORM}
+
+
+def check_mc_args(S, x0_mean, x0_spread, B, n, n_params, *, x0_dist="normal", params_mean=None, params_spread=None, params_dist="uniform",
+                  goal=None, samples=False, first_sample=0):
+    """RolloutPolicyStats' sampler arguments -> (rows, run): rows the contiguous (B, 3 n + 2 n_params) float64 array x0_mean | x0_spread |
+    goal | p_mean | p_spread (MI_F_POLICY_MC_DIST), run the float64 quintuple S | x0_dist | p_dist | sample_params | samples
+    (MI_F_POLICY_MC_RUN).  Means, spreads and goal: (k,) or (B, k); goal None: +inf everywhere (success = counted); params_mean None:
+    the parameters are not sampled (params_spread alone is refused; params_mean alone: spread zero).  ValueError - decided here, before
+    anything reaches the device - for any other shape, a NaN, a mean or spread that is not finite, a negative spread or goal, an S
+    that is no integer >= 1 or with first_sample + S > 2^32, an unknown distribution, parameters on a model without any."""
+    def rows_of(v, k, name, finite=True):
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"RolloutPolicyStats: {name} is not an array of numbers ({e})") from None
+        if a.shape == (k,):
+            a = np.broadcast_to(a, (B, k))
+        elif a.shape != (B, k):
+            raise ValueError(f"RolloutPolicyStats: {name} must be ({k},) or ({B}, {k}); got {a.shape}")
+        if np.isnan(a).any() or (finite and not np.isfinite(a).all()):
+            raise ValueError(f"RolloutPolicyStats: NaN{' or infinity' if finite else ''} in {name}")
+        return a
+
+    def nonneg(a, name):
+        if (a < 0.0).any():
+            raise ValueError(f"RolloutPolicyStats: negative entry in {name}")
+        return a
+
+    if isinstance(S, (bool, np.bool_)) or not isinstance(S, (int, np.integer)) or S < 1:
+        raise ValueError(f"RolloutPolicyStats: S must be an integer >= 1; got {S!r}")
+    if isinstance(first_sample, (bool, np.bool_)) or not isinstance(first_sample, (int, np.integer)) or not 0 <= first_sample < (1 << 32):
+        raise ValueError(f"RolloutPolicyStats: first_sample must be an integer in [0, 2^32); got {first_sample!r}")
+    if int(first_sample) + int(S) > (1 << 32):
+        raise ValueError(f"RolloutPolicyStats: first_sample + S must not exceed 2^32; got {int(first_sample)} + {int(S)}")
+    for name, d in (("x0_dist", x0_dist), ("params_dist", params_dist)):
+        if d not in MC_DISTS:
+            raise ValueError(f"RolloutPolicyStats: {name} must be 'normal' or 'uniform'; got {d!r}")
+    rows = np.zeros((B, 3 * n + 2 * n_params))
+    rows[:, :n] = rows_of(x0_mean, n, "x0_mean")
+    rows[:, n:2 * n] = nonneg(rows_of(x0_spread, n, "x0_spread"), "x0_spread")
+    rows[:, 2 * n:3 * n] = np.inf if goal is None else nonneg(rows_of(goal, n, "goal", finite=False), "goal")
+    sample_params = params_mean is not None
+    if params_spread is not None and not sample_params:
+        raise ValueError("RolloutPolicyStats: params_spread needs params_mean")
+    if sample_params:
+        if n_params == 0:
+            raise ValueError("RolloutPolicyStats: this model has no parameters")
+        rows[:, 3 * n:3 * n + n_params] = rows_of(params_mean, n_params, "params_mean")
+        if params_spread is not None:
+            rows[:, 3 * n + n_params:] = nonneg(rows_of(params_spread, n_params, "params_spread"), "params_spread")
+    run = np.array([int(S), MC_DISTS[x0_dist], MC_DISTS[params_dist], 1.0 if sample_params else 0.0, 1.0 if samples else 0.0], dtype=np.float64)
+    return rows, run
+
+
+class PolicySamples:
+    """The samples of a RolloutPolicyStats(..., samples=True) call: x0 (B, S, n), params (B, S, n_params) - None when the parameters
+    were not sampled -, cost (B, S) and steps (B, S) int32: what RolloutPolicy takes and returns for the same samples."""
+    __slots__ = ("x0", "params", "cost", "steps")
+
+    def __init__(self, x0, params, cost, steps):
+        self.x0, self.params, self.cost, self.steps = x0, params, cost, steps
+
+
+class PolicyStats:
+    """What RolloutPolicyStats returns, (B,) arrays: n samples, of which `counted` ran to the end with a finite cost and `success`
+    also ended within `goal` of the target; mean, m2 (the sum of squared deviations), min, max over the counted samples; argmin /
+    argmax the global sample numbers of min / max (-1 without a counted sample); steps_total the steps of all n samples.
+    samples: None or a PolicySamples."""
+    __slots__ = ("n", "counted", "success", "mean", "m2", "min", "max", "argmin", "argmax", "steps_total", "samples")
+
+    def __init__(self, n, counted, success, mean, m2, min, max, argmin, argmax, steps_total, samples=None):   # noqa: A002
+        self.n, self.counted, self.success, self.mean, self.m2 = n, counted, success, mean, m2
+        self.min, self.max, self.argmin, self.argmax, self.steps_total, self.samples = min, max, argmin, argmax, steps_total, samples
+
+    @classmethod
+    def from_rows(cls, rows, samples=None):
+        """rows: the (B, 10) array of MI_F_POLICY_MC_STATS."""
+        i = lambda k: rows[:, k].astype(np.int64)   # noqa: E731
+        return cls(i(0), i(1), i(2), rows[:, 3].copy(), rows[:, 4].copy(), rows[:, 5].copy(), rows[:, 6].copy(), i(7), i(8), i(9), samples)
+
+    @property
+    def var(self):
+        """The sample variance of the counted costs, m2 / (counted - 1); NaN with fewer than two."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.counted > 1, self.m2 / (self.counted - 1), np.nan)
+
+    @property
+    def success_rate(self):
+        return self.success / self.n
+
+    def merge(self, other):
+        """Chan's merge with the result of a DISJOINT, LATER window of samples (first_sample): how a sample set split over calls or
+        ranks is put together.  self is operand A of include/mi_ilqr.h's merge; a side without a counted sample leaves the other's
+        numbers as they are; ties of min / max keep self's sample."""
+        nA, nB = self.counted.astype(np.float64), other.counted.astype(np.float64)
+        n = nA + nB
+        with np.errstate(invalid="ignore", divide="ignore"):
+            delta = other.mean - self.mean
+            mean = self.mean + delta * (nB / n)
+            m2 = (self.m2 + other.m2) + (delta * delta) * ((nA * nB) / n)
+        mean = np.where(nB == 0, self.mean, np.where(nA == 0, other.mean, mean))
+        m2 = np.where(nB == 0, self.m2, np.where(nA == 0, other.m2, m2))
+        lo, hi = other.min < self.min, other.max > self.max
+        return PolicyStats(self.n + other.n, self.counted + other.counted, self.success + other.success, mean, m2,
+                           np.where(lo, other.min, self.min), np.where(hi, other.max, self.max), np.where(lo, other.argmin, self.argmin),
+                           np.where(hi, other.argmax, self.argmax), self.steps_total + other.steps_total)
+
+
 class PlantLog:
     """The closed loop's record (plant_log), K = num_resolves * replan_steps steps of the last MPCRun on a solver that holds a plant:
     X (B, n, K+1) - the state at every step, the plant's current state last -, U (B, m, K) the commanded controls, stage_cost (B, K)
@@ -870,13 +979,7 @@ class BatchedIterativeLQR:
             raise ValueError("RolloutPolicy: this solver holds a reference trajectory (SetTargetTrajectory), and the policy kernels "
                              "cost a rollout against a constant target only; SetTargetTrajectory(None) first")
         self._push_costs()
-        if rows is not None:
-            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_STREAM, _capi.ptr(stream), stream.nbytes), "mi_ilqr_set")
-            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_NOISE, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
-            self._policy_noise_set = True
-        elif getattr(self, "_policy_noise_set", False):
-            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_NOISE, None, 0), "mi_ilqr_set")
-            self._policy_noise_set = False
+        self._set_policy_noise(rows, stream)
         B, S = self.B, x0.shape[1]
         cost, x_final, steps = np.empty((B, S)), np.empty((B, S, self.n)), np.empty((B, S), dtype=np.int32)
         X = np.empty((B, S, self.n, self.N)) if trajectories else None
@@ -886,6 +989,54 @@ class BatchedIterativeLQR:
         if U is not None and self._md != self.m:
             U = np.ascontiguousarray(U[:, :, :self.m, :])
         return PolicyRollout(cost, x_final, steps, X, U)
+
+    def _set_policy_noise(self, rows, stream):
+        """The disturbances of the next policy launch: the stream always, the sigma rows or - None - their absence."""
+        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_STREAM, _capi.ptr(stream), stream.nbytes), "mi_ilqr_set")
+        if rows is not None:
+            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_NOISE, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
+            self._policy_noise_set = True
+        elif getattr(self, "_policy_noise_set", False):
+            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_NOISE, None, 0), "mi_ilqr_set")
+            self._policy_noise_set = False
+
+    def RolloutPolicyStats(self, S, x0_mean, x0_spread, *, x0_dist="normal", params_mean=None, params_spread=None, params_dist="uniform",
+                           goal=None, state_noise=None, control_noise=None, seed=0, first_sample=0, common_noise=False, samples=False):
+        """Monte-Carlo evaluation of the policy the solver holds, entirely on the device (include/mi_ilqr.h: "Monte-Carlo on the
+        device"): S samples per problem are DRAWN there - x0 = x0_mean + x0_spread o d with d standard normal (x0_dist="normal") or
+        uniform in (-1, 1) ("uniform"), and with params_mean / params_spread / params_dist the plants' parameters likewise -, rolled
+        out as RolloutPolicy rolls them out (state_noise, control_noise, seed, first_sample, common_noise: as there) and REDUCED
+        there: a PolicyStats of (B,) arrays comes back, nothing of size S crosses the bus.  Means, spreads and goal: (k,) or (B, k).
+        A sample is counted iff it ran to the end with a finite cost; success also asks |x_final - x_nom| <= goal component by
+        component (goal None: success = counted).  A draw depends on (seed, problem, first_sample + s, component) only: windows of one
+        sample set, split over calls with first_sample, are put together with PolicyStats.merge.  samples=True also returns every
+        sample's x0, params, cost and steps (PolicyStats.samples) - what RolloutPolicy reproduces: the same arithmetic up to the
+        compiler's FMA contraction, bit for bit on the models DESIGN 4.2h lists as measured.  Changes nothing in
+        the solver."""
+        n_params = int(self.system.params.size)
+        rows, run = check_mc_args(S, x0_mean, x0_spread, self.B, self.n, n_params, x0_dist=x0_dist, params_mean=params_mean,
+                                  params_spread=params_spread, params_dist=params_dist, goal=goal, samples=samples, first_sample=first_sample)
+        noisy = state_noise is not None or control_noise is not None
+        noise, stream = check_noise_args(state_noise, control_noise, seed, first_sample, common_noise, self.B, self.n, self.m,
+                                         self._md if noisy else None, int(S))
+        if self._tracking():
+            raise ValueError("RolloutPolicyStats: this solver holds a reference trajectory (SetTargetTrajectory), and the policy kernels "
+                             "cost a rollout against a constant target only; SetTargetTrajectory(None) first")
+        self._push_costs()
+        self._set_policy_noise(noise, stream)
+        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_MC_DIST, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
+        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_MC_RUN, _capi.ptr(run), run.nbytes), "mi_ilqr_set")
+        out = np.empty((self.B, _capi.MC_FIELDS))
+        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_STATS, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+        smp = None
+        if samples:
+            n = self.n
+            raw = np.empty((self.B, int(S), n + n_params + 2))
+            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_SAMPLES, _capi.ptr(raw), raw.nbytes), "mi_ilqr_get")
+            smp = PolicySamples(np.ascontiguousarray(raw[:, :, :n]),
+                                np.ascontiguousarray(raw[:, :, n:n + n_params]) if params_mean is not None else None,
+                                np.ascontiguousarray(raw[:, :, n + n_params]), raw[:, :, n + n_params + 1].astype(np.int32))
+        return PolicyStats.from_rows(out, smp)
 
     # ------------------------------------------------------------- the plant of the closed MPC loop
     def SetPlant(self, x, params=None, *, state_noise=None, control_noise=None, seed=0, common_noise=False, feedback=True, clock=0):
@@ -941,6 +1092,12 @@ class BatchedIterativeLQR:
     def plant_kernel_ms(self):
         """Milliseconds of the plant kernels of the last closed-loop MPCRun, summed (HIP events of their own)."""
         return float(self._plant_get(_capi.F_PLANT_KERNEL_MS, (1,))[0])
+
+    def policy_mc_passes(self):
+        """Passes over windows of sample groups the last RolloutPolicyStats call took (1 unless the samples outgrew the window)."""
+        out = np.empty(1, dtype=np.int32)
+        _capi.check(self._lib.mi_ilqr_get_int(self._h, _capi.I_POLICY_MC_PASSES, _capi.ptr(out), 4), "mi_ilqr_get_int")
+        return int(out[0])
 
     def policy_kernel_ms(self):
         """Milliseconds of the rollout kernel of the last RolloutPolicy call (HIP events of its own)."""

@@ -135,12 +135,17 @@ enum {
   MI_F_PLANT_KERNEL_MS = 26, /* (1,) read-only: milliseconds of the plant kernels of the last closed-loop mi_ilqr_mpc_run, summed, from their own HIP events */
   MI_F_X_REF = 27,           /* (B,T,n) reference trajectories: time-varying targets, T from the byte count ("Reference trajectories" below) */
   MI_F_REF_CLOCK = 28,       /* (1,) the row of the reference a solve's window starts at, an integer held in a double */
+  MI_F_POLICY_MC_DIST = 29,  /* (B,3n+2n_params) sampler rows x0_mean | x0_spread | goal | p_mean | p_spread ("Monte-Carlo on the device" below) */
+  MI_F_POLICY_MC_RUN = 30,   /* (5,) write-only COMMAND: S | x0_dist | p_dist | sample_params | samples - mi_ilqr_set RUNS the evaluation */
+  MI_F_POLICY_MC_STATS = 31, /* (B,10) read-only: S | counted | success | mean | M2 | min | max | argmin | argmax | steps_total of the last run */
+  MI_F_POLICY_MC_SAMPLES = 32,/* (B,S,n+n_params+2) read-only: rows x0 | params | cost | steps of the last run, when it was asked for them */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
   MI_I_LS_TRIALS = 102, /* (B,) reference-equivalent line-search trials, summed         */
   MI_I_KP_COUNT = 103,  /* (B,) key-points used by the last linearization               */
   MI_I_KP_LIST = 104,   /* (B,N-1) the key-point indices, first KP_COUNT valid          */
+  MI_I_POLICY_MC_PASSES = 105, /* (1,) read-only (mi_ilqr_get_int): the passes over windows of sample groups the last MI_F_POLICY_MC_RUN took */
   MI_I64_STAGE_CYCLES = 200, /* (B,4) int64: what mi_ilqr_get_cycles returns - here so that mi_ilqr_get_async can queue it behind a solve */
   MI_I64_CLUSTER_WORDS = 201 /* (B,MI_ILQR_CLUSTER_WORDS) uint64 (mi_ilqr_get_int; diagnostic): the handshake words of the last solve / MPC launch
                                 when it shared its linearizations among clusters of workgroups (workgroup-per-problem kernels) - zeros when it
@@ -613,6 +618,60 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
  * and the same Box-Muller - so the plant of problem b at clock k gets the normals that SAMPLE 0 of a policy rollout
  * (first_sample = 0) gets at step t = k: from clock 0, with the same seed and sigmas, the first segment of a closed-loop run is the
  * first replan_steps steps of that rollout. */
+
+/* Monte-Carlo on the device (additive in ABI 10: four selectors of mi_ilqr_set / mi_ilqr_get, no new entry point).
+ * mi_ilqr_policy_rollout takes every sample's x0 from the host and returns every sample's result to it.  Here the samples are DRAWN
+ * where they are used and their costs are REDUCED on the device: per problem ten numbers come back, and nothing of size S crosses
+ * the bus unless the caller asks for the samples.  For problem b and the global sample number g = first_sample + s, s = 0 .. S-1:
+ *   start state   x0[i] = x0_mean[b,i] + x0_spread[b,i] d_i
+ *   parameters    p[j]  = p_mean[b,j] + p_spread[b,j] d_j            with sample_params = 1 (models with n_params > 0); else every sample
+ *                                                                    runs on problem b's own row, as mi_ilqr_policy_rollout with params = NULL
+ *   d, normal  (dist = 0): the Box-Muller normal (as above) of word pair (i mod 4) of the Philox block 512 + i / 4 (parameters: 768 + j / 4)
+ *   d, uniform (dist = 1): d = (w + 1/2) 2^-31 - 1 with w word i mod 4 of that block: exact in fp64, inside (-1, 1), so the draw lies
+ *                          in mean +- spread
+ *   counter = (g, 0, common ? 0 : b, block) under the key of MI_F_POLICY_STREAM's seed - the key of the disturbances, which use the
+ *   blocks 0 .. 9 and 256 .. 259 only: draws and noise are independent under one seed.  A draw depends on (seed, b, g, component) only,
+ *   not on S, the launch geometry or the model; common = 1 gives every problem the same d.  A spread of zero returns the mean's bits.
+ * The rollout is mi_ilqr_policy_rollout's, with MI_F_POLICY_NOISE's disturbances when they are set: the policy, the clamp, the rule by
+ * which a sample ends, the commanded-control cost, per-problem Q / R / Qf / x_nom, limits and padding controls are unchanged.  The two
+ * kernels run the same arithmetic on a sample; what the compiler may do differently in them is which multiply it fuses into which
+ * add (FMA contraction), so a sample's cost agrees with what mi_ilqr_policy_rollout returns for the same x0, parameters and stream
+ * up to the last bits, and its steps agree unless a state lies within that of a feasibility bound.  BIT FOR BIT equality is what
+ * this build was measured to give, and what its tests hold it to, for the models listed under "Monte-Carlo on the device" in
+ * DESIGN.md (4.2h) - not a property of the interface.
+ * A sample is COUNTED iff it ran all N-1 steps and its cost is finite.  The result of problem b, ten doubles:
+ *     S | counted | success | mean | M2 | min | max | argmin | argmax | steps_total
+ * mean, M2 (the sum of squared deviations from the mean), min and max run over the counted samples; argmin / argmax are global sample
+ * numbers g, ties go to the lower g; steps_total is the sum of the steps of ALL S samples; success counts the counted samples with
+ * |x_final_i - x_nom_b,i| <= goal[b,i] for every i (a goal of +inf ignores the component).  counted = 0: mean = M2 = NaN, min = +inf,
+ * max = -inf, argmin = argmax = -1.
+ * The REDUCTION ORDER is fixed and part of the contract: the samples form groups of 64 by s / 64; a group's statistic is the butterfly
+ * over lane distance 1, 2, 4, 8, 16, 32 of Chan's merge of (count, mean, M2) -
+ *     n = nA + nB,  delta = meanB - meanA,  mean = meanA + delta (nB / n),  M2 = (M2A + M2B) + (delta delta) ((nA nB) / n)
+ * with A always the operand from the lower lane, and a merge with a count-0 operand returning the other operand's bits; the groups
+ * of a problem are then folded left to right in group order.  Lanes past a ragged tail and uncounted samples enter with count 0.
+ * The host runs the groups in windows (about 64 MB of the grow-only scratch per pass; the environment variable
+ * MI_ILQR_MC_PASS_GROUPS=k, read once, forces windows of k groups): the result does not depend on the window, bit for bit, and S is
+ * bounded by 2^32 - first_sample, not by memory.
+ *   mi_ilqr_set(MI_F_POLICY_MC_DIST, rows, B*(3n+2n_params)*8)   row b = x0_mean | x0_spread | goal | p_mean | p_spread.  (NULL, 0)
+ *                                            clears the rows.  Survives mi_ilqr_reset.  mi_ilqr_get reads them back (zeros while not set).
+ *                                            Refusals: a NaN anywhere, a mean or spread that is not finite, a negative spread or goal:
+ *                                            MI_ILQR_E_BAD_ARG; wrong `bytes`: MI_ILQR_E_BAD_SHAPE.  A refused call changes nothing.
+ *   mi_ilqr_set(MI_F_POLICY_MC_RUN, v, 40)   v = S | x0_dist | p_dist | sample_params | samples, integers held in doubles: RUNS the
+ *                                            evaluation on the handle's stream and synchronizes once (a run of more than 32 passes: once every 32).  Seed, first_sample and common are
+ *                                            MI_F_POLICY_STREAM's, the noise MI_F_POLICY_NOISE's.  Refusals: no MI_F_POLICY_MC_DIST rows,
+ *                                            S < 1, first_sample + S > 2^32, a value that is no such integer: MI_ILQR_E_BAD_ARG;
+ *                                            sample_params = 1 on a model without parameters, and a handle that holds a reference
+ *                                            trajectory (like mi_ilqr_policy_rollout): MI_ILQR_E_UNSUPPORTED; wrong `bytes`:
+ *                                            MI_ILQR_E_BAD_SHAPE.  A refused run leaves the rows and the last results in place.
+ *                                            Write-only: mi_ilqr_get refuses it.  The handle's solver state is only READ: a solve after
+ *                                            the run is bitwise the solve without it.
+ *   mi_ilqr_get(MI_F_POLICY_MC_STATS, dst, B*10*8)   the last run's result; before any run MI_ILQR_E_BAD_ARG.
+ *   mi_ilqr_get(MI_F_POLICY_MC_SAMPLES, dst, B*S*(n+n_params+2)*8)   rows x0 | params | cost | steps (a double) of every sample of the last
+ *                                            run, when that run had samples = 1 - otherwise MI_ILQR_E_BAD_ARG.  params: the drawn
+ *                                            parameters, or problem b's row when they were not drawn.
+ *   MI_F_POLICY_KERNEL_MS after a run: the rollout kernels of that run, summed over its passes.  The fold kernels are NOT included.
+ *   mi_ilqr_get_int(MI_I_POLICY_MC_PASSES, &k, 4): the passes that run took (before any run MI_ILQR_E_BAD_ARG). */
 
 #ifdef __cplusplus
 }

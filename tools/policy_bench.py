@@ -12,7 +12,8 @@ of B S problems (fx alone is B S n^2 (N-1) doubles: 27 GB for Quad3D at S = 1024
 --emulate-up-to (default 65536: everything but the pendulum at S = 1024, a 1 M-problem handle) - the rates are per sample-step and
 compare across S.  --noise: the same rollouts again with process and actuation noise (state_noise / control_noise: the noisy
 kernels of csrc/policy_rollout.hpp, a Philox block and its Box-Muller normals per four components and step) and the ratio of the
-two kernel times.  Prints one JSON line."""
+two kernel times.  --mc: the whole call instead - RolloutPolicy on host arrays plus the NumPy reduction against RolloutPolicyStats
+(csrc/policy_mc.hpp), wall and kernel times (mc_bench).  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -58,6 +59,67 @@ def summary(ms, work):
     return dict(kernel_ms=med, kernel_ms_min=float(ms.min()), kernel_ms_max=float(ms.max()), sample_steps_per_s=work / (med * 1e-3))
 
 
+def spread3(v):
+    v = np.asarray(v)
+    return dict(median=float(np.median(v)), min=float(v.min()), max=float(v.max()))
+
+
+def mc_bench(a):
+    """--mc: the WHOLE call, old path against new, at S = 1024 samples per problem (pendulum B = 1024, N = 200: 10^6 samples; Quad3D
+    B = 64, N = 40).  (a) what a caller did before: draw the starts in NumPy, RolloutPolicy on the host arrays, reduce the costs in
+    NumPy (count, mean, M2, min, max, argmin, argmax) - wall time, and its three parts; the call and the reduction run on the very
+    samples the device draws (seed 7, fetched once with samples=True), so both kernels roll out the same starts; (b) RolloutPolicyStats - wall time.  Beside
+    them the kernel times (HIP events): policy_rollout_kernel and the Monte-Carlo kernel (its passes summed, the fold not included),
+    without and with noise.  `reps` timed calls after `warmup`, the two paths alternated twice: median [min .. max] of 2 x reps."""
+    import time
+    out = {}
+    for config in a.configs.split(","):
+        p, B, x0b, ug, sigma = problem(config)
+        N, n, S = p["N"], x0b.shape[1], 1024
+        s = solver(p, B, max_iters=5)
+        s.SetInitialState(x0b); s.SetInitialGuess(ug)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            s.Solve()
+        res = dict(B=B, S=S, N=N)
+        # the SAME samples for both kernels: what the device draws for seed 7, fed back to RolloutPolicy as host arrays
+        x0_same = s.RolloutPolicyStats(S, x0b, sigma * np.ones(n), seed=7, samples=True).samples.x0
+        for label, nz in (("no_noise", {}), ("noise", dict(zip(("state_noise", "control_noise"), noise(config, n))))):
+            old, new = dict(wall=[], draw=[], call=[], reduce=[], kernel=[]), dict(wall=[], kernel=[])
+            for rnd in range(2):
+                for i in range(a.warmup + a.reps):
+                    t0 = time.perf_counter()
+                    rng = np.random.default_rng(rnd * 1000 + i)
+                    x0 = x0b[:, None, :] + sigma * rng.standard_normal((B, S, n))     # (the caller's draw: timed, then set aside)
+                    t1 = time.perf_counter()
+                    r = s.RolloutPolicy(x0_same, seed=7, **nz)
+                    t2 = time.perf_counter()
+                    ok = (r.steps == N - 1) & np.isfinite(r.cost)
+                    c = np.where(ok, r.cost, np.nan)
+                    cnt = ok.sum(axis=1)
+                    mean = np.nansum(c, axis=1) / cnt
+                    red = (cnt, mean, np.nansum((c - mean[:, None]) ** 2, axis=1), np.nanmin(c, axis=1), np.nanmax(c, axis=1),
+                           np.nanargmin(c, axis=1), np.nanargmax(c, axis=1), r.steps.sum(axis=1))
+                    t3 = time.perf_counter()
+                    if i >= a.warmup:
+                        for k, v in (("wall", t3 - t0), ("draw", t1 - t0), ("call", t2 - t1), ("reduce", t3 - t2)):
+                            old[k].append(1e3 * v)
+                        old["kernel"].append(s.policy_kernel_ms())
+                for i in range(a.warmup + a.reps):
+                    t0 = time.perf_counter()
+                    st = s.RolloutPolicyStats(S, x0b, sigma * np.ones(n), seed=7, **nz)
+                    t1 = time.perf_counter()
+                    if i >= a.warmup:
+                        new["wall"].append(1e3 * (t1 - t0))
+                        new["kernel"].append(s.policy_kernel_ms())
+            res[label] = dict(host_arrays={k + "_ms": spread3(v) for k, v in old.items()}, on_device={k + "_ms": spread3(v) for k, v in new.items()},
+                              wall_speedup=float(np.median(old["wall"]) / np.median(new["wall"])),
+                              kernel_ratio=float(np.median(new["kernel"]) / np.median(old["kernel"])),
+                              counted_host=int(red[0].sum()), counted_device=int(st.counted.sum()))
+        out["%s_S%d" % (config, S)] = res
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -66,7 +128,10 @@ def main():
     ap.add_argument("--samples", default="64,1024")
     ap.add_argument("--emulate-up-to", type=int, default=65536)
     ap.add_argument("--noise", action="store_true")
+    ap.add_argument("--mc", action="store_true")
     a = ap.parse_args()
+    if a.mc:
+        return mc_bench(a)
     out = {}
     for config in a.configs.split(","):
         p, B, x0b, ug, sigma = problem(config)
