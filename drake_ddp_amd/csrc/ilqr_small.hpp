@@ -316,6 +316,9 @@ __device__ __forceinline__ void aff2_prefix_dpp(Aff2& P) {
 // writes the trajectory straight into the nominal records (:375-376) - no T records, no separate
 // cost and commit passes; fuse = 2 additionally differentiates the dynamics at every step it holds
 // (:380-415 with every step a key-point), again from registers.
+// `coarse`: the caller vouches for all-zero K, kappa and x_bar (first iteration of a cold solve, after the kernel's
+// prologue has zero-filled the records).  With other state the coarse guess would ignore the feedback: a poorer
+// start for the sweeps, never a wrong trajectory - the sweeps, the guard and the final pass use the full control law.
 enum { NEWTON_FAILED = 0, NEWTON_STORED = 1, NEWTON_REJECTED = 2, NEWTON_ACCEPTED = 3 };
 
 template <class M, int JAC, int CH>
@@ -344,22 +347,22 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
     // the chunk start (ceil(steps / CH) dependent steps instead of `steps`) - refined inside every
     // chunk by the plain steps from the coarse chunk start.  Newton's sweeps then pull the whole
     // trajectory onto the fine recurrence; not converged -> sequential rollout as before.
+    // The solver state is all zeros here (the kernel's prologue: K = 0, kappa = 0, x_bar = 0), so the closed loop
+    // u = (u_bar - eps kappa) - K (x - x_bar) IS u_bar, bit for bit; the guess reads u_bar alone and leaves out the
+    // arithmetic on those zeros, which strict floating point keeps - a quarter of a coarse step's instructions on
+    // its 50-step dependent chain.  The sweeps, the guard and the final pass below keep the general form.
     double xc[n] = {x0r[0], x0r[1]};
     const int nchunks = (steps + CH - 1) / CH;
-    struct Rec { double xb[n], kk[n], ub, kap; };
-    auto fetch = [&](Rec& r, int j) __attribute__((always_inline)) {
-      const double* g = w.G + (j * CH) * Ly::GS;              // wave-uniform address: LDS broadcast
-      r.xb[0] = g[Ly::XB + 0]; r.xb[1] = g[Ly::XB + 1]; r.kk[0] = g[Ly::KK + 0]; r.kk[1] = g[Ly::KK + 1];
-      r.ub = g[Ly::UB]; r.kap = g[Ly::KAP];
+    auto fetch = [&](int j) __attribute__((always_inline)) -> double {
+      return w.G[(j * CH) * Ly::GS + Ly::UB];                 // wave-uniform address: LDS broadcast
     };
-    Rec cur, nxt;
-    fetch(cur, 0);
+    double cur = fetch(0);
     for (int j = 0; j < nchunks; ++j) {
-      fetch(nxt, j + 1 < nchunks ? j + 1 : j);                // one record ahead of its use
+      const double nxt = fetch(j + 1 < nchunks ? j + 1 : j);  // one record ahead of its use
       __builtin_amdgcn_sched_barrier(0);
       if (lane == j) { X[0][0] = xc[0]; X[0][1] = xc[1]; }
       double u[m], xn[n];
-      u[0] = (cur.ub - eps * cur.kap) - (cur.kk[0] * (xc[0] - cur.xb[0]) + cur.kk[1] * (xc[1] - cur.xb[1]));
+      u[0] = cur;
       M::template step<double>(xc, u, xn, par.v, (double)CH * a.dt);
       xc[0] = xn[0]; xc[1] = xn[1];
       cur = nxt;
@@ -368,7 +371,7 @@ __device__ inline int rollout_newton_impl(const WS& w, const Consts<M>& c, const
 #pragma unroll
     for (int k = 0; k + 1 < CH; ++k) {
       double u[m], xn[n];
-      u[0] = dd[k] - (Kk[k][0] * (X[k][0] - xb[k][0]) + Kk[k][1] * (X[k][1] - xb[k][1]));
+      u[0] = dd[k];
       M::template step<double>(X[k], u, xn, par.v, a.dt);
       X[k + 1][0] = xn[0]; X[k + 1][1] = xn[1];
     }
