@@ -42,6 +42,12 @@ F_X_REF, F_REF_CLOCK = 27, 28
 F_POLICY_MC_DIST, F_POLICY_MC_RUN, F_POLICY_MC_STATS, F_POLICY_MC_SAMPLES = 29, 30, 31, 32
 MC_DIST_NORMAL, MC_DIST_UNIFORM = 0, 1
 MC_FIELDS = 10
+# what a run observes beside the cost (mi_ilqr.h: "Envelopes and a safety box"): (B, 2n) box rows lo | hi | (1,) observe bits (1 state
+# envelopes, 2 control envelopes) | read-only (B, N, n, 8) and (B, N-1, m, 8) accumulators count | K | s1 | s2 | min | max | argmin |
+# argmax | read-only (B, 3+N) ran | safe | safe_success | exits
+F_POLICY_MC_BOX, F_POLICY_MC_OBSERVE, F_POLICY_MC_ENVELOPE, F_POLICY_MC_ENVELOPE_U, F_POLICY_MC_SAFETY = 33, 34, 35, 36, 37
+MC_OBSERVE_X, MC_OBSERVE_U = 1, 2
+MC_ENV_FIELDS = 8
 I_ITERS, I_STATUS, I_LS_TRIALS, I_KP_COUNT, I_KP_LIST = 100, 101, 102, 103, 104
 I_POLICY_MC_PASSES = 105    # (1,) passes over windows of sample groups of the last on-device Monte-Carlo run
 I64_STAGE_CYCLES = 200

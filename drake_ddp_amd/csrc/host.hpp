@@ -151,6 +151,15 @@ struct mi_ilqr {
   double mc_ms = 0.0;
   int32_t mc_passes = 0;           // passes of the last run (MI_I_POLICY_MC_PASSES)
   bool policy_last_mc = false;
+  // What a run observes beside the cost (MI_F_POLICY_MC_BOX / _OBSERVE / _ENVELOPE / _ENVELOPE_U / _SAFETY; policy_env.hpp).  mc_box:
+  // (B, 2 n) rows lo | hi, `synced` = the handle holds a box and runs observe it; mc_observe: bit 0 state envelopes, bit 1 control
+  // envelopes.  env_acc_x (B, N n, 8) / env_acc_u (B, (N-1) m, 8) / box_counters (B, 3 + N): the kernels' accumulators on the device,
+  // allocated on first use; mc_env_x / mc_env_u / mc_safety: the last run's results on the host (empty: that run did not produce them).
+  RowStore mc_box;
+  int32_t mc_observe = 0;
+  double *env_acc_x = nullptr, *env_acc_u = nullptr;
+  unsigned long long* box_counters = nullptr;
+  std::vector<double> mc_env_x, mc_env_u, mc_safety;
   // the plant of the closed receding-horizon loop (mi_ilqr_mpc_run; plant_advance.hpp).  plant_state: (B, n), `synced` = the handle
   // holds a plant - its device rows ARE the plant (the kernel advances them in place, mi_ilqr_mpc_run brings the mirror up to date);
   // plant_params: (B, n_params), not synced = every plant runs on its problem's model row; plant_noise: (B, n + m) sigma_x | sigma_u,
@@ -345,6 +354,13 @@ struct PolicyMcArgs {
 };
 template <class M> MI_INTERNAL int launch_policy_mc(mi_ilqr* h, const PolicyMcArgs& a);             // policy_mc.hpp; k_policy_mc.hip
 template <class M> MI_INTERNAL int launch_policy_mc_noise(mi_ilqr* h, const PolicyMcArgs& a);       // ... k_policy_mc_noise.hip
+
+// The reductions of a window's trajectory buffers behind a pass of the on-device Monte-Carlo (policy_env.hpp; k_policy_env.hip), on the
+// handle's stream.  launch_policy_env: buf (B, R, win) sample-minor rows -> acc (B, R, 8), first_global the global number of the
+// window's sample 0, first: the accumulators start empty.  launch_policy_box: the X window against box (B, 2 n) -> counters (B, 3 + N).
+MI_INTERNAL int launch_policy_env(mi_ilqr* h, const double* buf, double* acc, size_t B, size_t R, size_t win, double first_global, int first);
+MI_INTERNAL int launch_policy_box(mi_ilqr* h, const double* X, const double* box, const double* x_nom, size_t x_nom_stride,
+                                  const double* goal, size_t goal_stride, unsigned long long* counters, size_t B, int n, int N, size_t win);
 
 // Arguments of plant_advance_kernel<M> (plant_advance.hpp), all device pointers.  "Problem-minor": element e of problem b at e * B + b.
 struct PlantArgs {

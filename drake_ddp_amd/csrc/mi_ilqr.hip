@@ -681,6 +681,7 @@ RowField row_field(mi_ilqr* h, int which) {
     case MI_F_PLANT_PARAMS: return {&h->plant_params, h->d.model_params};   // (not set: the problem's model row, get_plant_field)
     case MI_F_PLANT_NOISE: return {&h->plant_noise, nullptr};
     case MI_F_POLICY_MC_DIST: return {&h->policy_mc_dist, nullptr};    // (not set: zeros)
+    case MI_F_POLICY_MC_BOX: return {&h->mc_box, nullptr};             // (the same)
   }
   return {nullptr, nullptr};
 }
@@ -1000,6 +1001,7 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   h->costs.width = cost_len(h);
   h->policy_noise.width = h->plant_noise.width = h->n + h->m;
   h->policy_mc_dist.width = 3 * (size_t)h->n + 2 * (size_t)model.n_params;
+  h->mc_box.width = 2 * (size_t)h->n;
   h->plant_state.width = h->n;
   h->plant_params.width = model.n_params;
   h->params.batch_minor_copy = h->costs.batch_minor_copy = batch_minor;   // (what the lane kernels read batch-minor: KArgs::param_cols, cost_cols)
@@ -1749,11 +1751,36 @@ static int set_mc_dist(mi_ilqr* h, const double* src, size_t bytes) {
   return store_upload(h, s, src);
 }
 
+// MI_F_POLICY_MC_BOX: (B, 2 n) rows lo | hi, +-inf = unbounded; a NaN or lo > hi is refused; src == NULL with bytes == 0 clears the
+// box.  MI_F_POLICY_MC_OBSERVE: one double, 0 .. 3 (bit 0 state envelopes, bit 1 control envelopes).  A refused call changes nothing.
+static int set_mc_box(mi_ilqr* h, const double* src, size_t bytes) {
+  RowStore& s = h->mc_box;
+  const size_t n = h->n, cnt = (size_t)h->B * 2 * n;
+  if (!src && bytes == 0) { store_drop(s); return MI_ILQR_OK; }
+  if (bytes != cnt * 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  for (size_t b = 0; b < (size_t)h->B; ++b)
+    for (size_t i = 0; i < n; ++i) {
+      const double lo = src[b * 2 * n + i], hi = src[b * 2 * n + n + i];
+      if (!(lo <= hi)) return MI_ILQR_E_BAD_ARG;               // (a NaN on either side, or an inverted interval)
+    }
+  return store_upload(h, s, src);
+}
+
+static int set_mc_observe(mi_ilqr* h, const double* src, size_t bytes) {
+  if (bytes != 8) return MI_ILQR_E_BAD_SHAPE;
+  if (!src) return MI_ILQR_E_BAD_ARG;
+  if (!(*src == 0.0 || *src == 1.0 || *src == 2.0 || *src == 3.0)) return MI_ILQR_E_BAD_ARG;
+  h->mc_observe = (int32_t)*src;
+  return MI_ILQR_OK;
+}
+
 // MI_F_POLICY_MC_RUN: v = S | x0_dist | p_dist | sample_params | samples.  Draws, rolls out and reduces S samples per problem on the
 // handle's stream - passes over windows of sample groups, each one rollout kernel and one fold (policy_mc.hpp) - and synchronizes
 // once.  Nothing of the handle's solver state is written; the staging memory is the grow-only scratch.
 constexpr size_t kMcWindowBytes = 64u << 20;      // what the partials and the optional sample buffers of one pass may take
 constexpr unsigned long long kMcEventPairs = 32;  // event pairs a handle keeps for the passes of a run
+constexpr size_t kMcTrajWindowBytes = (size_t)1 << 30;   // ... and the trajectory windows of a run that observes envelopes or a box (at least one group)
 static int run_policy_mc(mi_ilqr* h, const double* v, size_t bytes) {
   if (bytes != 5 * 8) return MI_ILQR_E_BAD_SHAPE;
   if (!v) return MI_ILQR_E_BAD_ARG;
@@ -1772,6 +1799,14 @@ static int run_policy_mc(mi_ilqr* h, const double* v, size_t bytes) {
   const unsigned long long G = (S + 63) / 64;
   const size_t group_bytes = (size_t)kMcFields * B * 8 + (want_samples ? 2 * B * 64 * SW * 8 : 0);
   unsigned long long k = std::max<unsigned long long>(1, kMcWindowBytes / group_bytes);
+  // what the run observes beside the cost (policy_env.hpp): the window's trajectories stay in the scratch, under a cap of their own
+  const bool want_box = h->mc_box.synced, env_x = (h->mc_observe & 1) != 0, env_u = (h->mc_observe & 2) != 0;
+  const bool keep_x = want_box || env_x, observing = keep_x || env_u;
+  const size_t Rx = N * n, Ru = (N - 1) * m;
+  if (observing) {
+    const size_t traj_group_bytes = B * 64 * 8 * ((keep_x ? Rx : 0) + (env_u ? Ru : 0));
+    k = std::min(k, std::max<unsigned long long>(1, kMcTrajWindowBytes / traj_group_bytes));
+  }
   if (switches().mc_pass_groups > 0) k = (unsigned long long)switches().mc_pass_groups;
   k = std::min(std::min(k, G), std::max<unsigned long long>(1, 0x7fffffffull / B));
   const unsigned long long passes = (G + k - 1) / k;
@@ -1785,10 +1820,19 @@ static int run_policy_mc(mi_ilqr* h, const double* v, size_t bytes) {
   const size_t win_max = (size_t)k * 64;
   const size_t o_pol = take(B * (N - 1) * W), o_prow = take(np ? np : 1), o_part = take((size_t)k * kMcFields * B);
   const size_t o_smp = take(want_samples ? B * SW * win_max : 0), o_smp_out = take(want_samples ? B * win_max * SW : 0);
+  const size_t o_X = take(keep_x ? B * Rx * win_max : 0), o_U = take(env_u ? B * Ru * win_max : 0);
   int rc = ensure_scratch(h, off * 8);
+  if (rc != MI_ILQR_OK && observing) { (void)hipGetLastError(); return MI_ILQR_E_UNSUPPORTED; }   // (the windows did not fit: the last results stay)
   if (rc != MI_ILQR_OK) return rc;
   double* const sc = h->scratch;
   if (!h->mc_acc && (rc = dev_alloc(h, h->mc_acc, (size_t)kMcFields * B)) != MI_ILQR_OK) return rc;
+  if (observing) {
+    if (env_x && !h->env_acc_x) rc = dev_alloc(h, h->env_acc_x, B * Rx * 8);
+    if (rc == MI_ILQR_OK && env_u && !h->env_acc_u) rc = dev_alloc(h, h->env_acc_u, B * Ru * 8);
+    if (rc == MI_ILQR_OK && want_box && !h->box_counters) rc = dev_alloc(h, h->box_counters, B * (3 + N));
+    if (rc != MI_ILQR_OK) { (void)hipGetLastError(); return MI_ILQR_E_UNSUPPORTED; }
+    if (want_box) HIPCHK(hipMemsetAsync(h->box_counters, 0, B * (3 + N) * 8, h->stream));
+  }
   // one start / stop pair per pass, at most kMcEventPairs of them: a run of more passes waits for the stream every kMcEventPairs
   // passes, adds their times up and uses the pairs again
   const size_t pairs = (size_t)std::min<unsigned long long>(passes, kMcEventPairs);
@@ -1822,6 +1866,17 @@ static int run_policy_mc(mi_ilqr* h, const double* v, size_t bytes) {
   a.r.dt = h->d.dt; a.r.N = (int32_t)N; a.r.B = (int32_t)B; a.r.m_user = model->p.m_user > 0 ? model->p.m_user : (int32_t)m;
   a.dist = h->policy_mc_dist.rows; a.partials = sc + o_part; a.acc = h->mc_acc; a.samples = want_samples ? sc + o_smp : nullptr;
   a.S = S; a.x0_dist = (int32_t)v[1]; a.p_dist = (int32_t)v[2]; a.sample_params = sample_params ? 1 : 0;
+  if (keep_x) a.r.X = sc + o_X;
+  if (env_u) a.r.U = sc + o_U;
+  std::vector<double> env_x_out, env_u_out, safety_out;
+  std::vector<unsigned long long> box_out;
+  if (observing) {
+    try {
+      if (env_x) env_x_out.resize(B * Rx * 8);
+      if (env_u) env_u_out.resize(B * Ru * 8);
+      if (want_box) { box_out.resize(B * (3 + N)); safety_out.resize(B * (3 + N)); }
+    } catch (const std::bad_alloc&) { return MI_ILQR_E_UNSUPPORTED; }
+  }
   // From here on copies into `samples` and `acc` may be queued on the stream: whatever fails, the stream is waited for before
   // the two go out of scope.
   std::vector<double> acc((size_t)kMcFields * B);
@@ -1846,6 +1901,16 @@ static int run_policy_mc(mi_ilqr* h, const double* v, size_t bytes) {
       a.group0 = (uint32_t)g0; a.groups = (int32_t)kg; a.win_samples = win; a.first_pass = pass == 0 ? 1 : 0;
       a.ev0 = h->mc_events[2 * slot]; a.ev1 = h->mc_events[2 * slot + 1];
       if (const int rl = model->p.launch(h, kModePolicyMC, &a); rl != MI_ILQR_OK) return rl;
+      if (observing) {        // the window's trajectories, reduced before the next pass overwrites them
+        const double g_first = (double)h->policy_first_sample + (double)s0;
+        int re = MI_ILQR_OK;
+        if (env_x) re = launch_policy_env(h, sc + o_X, h->env_acc_x, B, Rx, win, g_first, a.first_pass);
+        if (re == MI_ILQR_OK && env_u) re = launch_policy_env(h, sc + o_U, h->env_acc_u, B, Ru, win, g_first, a.first_pass);
+        if (re == MI_ILQR_OK && want_box)
+          re = launch_policy_box(h, sc + o_X, h->mc_box.rows, a.r.x_nom, a.r.x_nom_stride, a.dist + 2 * n, h->policy_mc_dist.width,
+                                 h->box_counters, B, (int)n, (int)N, win);
+        if (re != MI_ILQR_OK) return re;
+      }
       if (want_samples) {     // sample-minor (B, SW, win) -> (B, win, SW), then rows s0 .. s0 + win - 1 of every problem's block
         if (const int rt = transpose_tiles(h, sc + o_smp, sc + o_smp_out, (int)SW, (int)win, B, 1, SW * win, 0, win, win * SW, 0, SW);
             rt != MI_ILQR_OK) return rt;
@@ -1854,6 +1919,9 @@ static int run_policy_mc(mi_ilqr* h, const double* v, size_t bytes) {
       }
     }
     HIPCHK(hipMemcpyAsync(acc.data(), h->mc_acc, acc.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    if (env_x) HIPCHK(hipMemcpyAsync(env_x_out.data(), h->env_acc_x, env_x_out.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    if (env_u) HIPCHK(hipMemcpyAsync(env_u_out.data(), h->env_acc_u, env_u_out.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    if (want_box) HIPCHK(hipMemcpyAsync(box_out.data(), h->box_counters, box_out.size() * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return timed((passes - 1) % kMcEventPairs + 1);
   };
@@ -1869,6 +1937,10 @@ static int run_policy_mc(mi_ilqr* h, const double* v, size_t bytes) {
     if (row[1] == 0.0) row[3] = row[4] = std::nan("");
   }
   h->mc_samples.swap(samples);
+  h->mc_env_x.swap(env_x_out);                 // (not observed: empty, and the selectors refuse)
+  h->mc_env_u.swap(env_u_out);
+  for (size_t i = 0; i < box_out.size(); ++i) safety_out[i] = (double)box_out[i];
+  h->mc_safety.swap(safety_out);
   h->mc_ms = ms_sum;
   h->mc_passes = (int32_t)std::min<unsigned long long>(passes, 0x7fffffffull);
   h->policy_last_mc = true;
@@ -2168,6 +2240,18 @@ int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
     std::memcpy(dst, r.data(), bytes);
     return MI_ILQR_OK;
   }
+  if (which == MI_F_POLICY_MC_OBSERVE) {
+    if (bytes != 8) return MI_ILQR_E_BAD_SHAPE;
+    *dst = (double)h->mc_observe;
+    return MI_ILQR_OK;
+  }
+  if (which == MI_F_POLICY_MC_ENVELOPE || which == MI_F_POLICY_MC_ENVELOPE_U || which == MI_F_POLICY_MC_SAFETY) {   // host copies too
+    const std::vector<double>& r = which == MI_F_POLICY_MC_ENVELOPE ? h->mc_env_x : (which == MI_F_POLICY_MC_ENVELOPE_U ? h->mc_env_u : h->mc_safety);
+    if (h->mc_stats.empty() || r.empty()) return MI_ILQR_E_BAD_ARG;      // (the last run did not produce them)
+    if (bytes != r.size() * 8) return MI_ILQR_E_BAD_SHAPE;
+    std::memcpy(dst, r.data(), bytes);
+    return MI_ILQR_OK;
+  }
   if (which == MI_F_POLICY_KERNEL_MS) {        // the rollout kernel of the last mi_ilqr_policy_rollout, from its own events
     if (bytes != 8) return MI_ILQR_E_BAD_SHAPE;
     if (h->policy_last_mc) { *dst = h->mc_ms; return MI_ILQR_OK; }      // (an on-device Monte-Carlo run: its rollout kernels, summed over the passes)
@@ -2259,6 +2343,9 @@ int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
   if (h && which == MI_F_POLICY_STREAM) return set_policy_stream(h, src, bytes);
   if (h && which == MI_F_POLICY_MC_DIST) return set_mc_dist(h, src, bytes);      // (src == NULL, bytes == 0: no sampler rows)
   if (h && which == MI_F_POLICY_MC_RUN) return run_policy_mc(h, src, bytes);     // (a command: runs the evaluation)
+  if (h && which == MI_F_POLICY_MC_BOX) return set_mc_box(h, src, bytes);        // (src == NULL, bytes == 0: no box)
+  if (h && which == MI_F_POLICY_MC_OBSERVE) return set_mc_observe(h, src, bytes);
+  if (which == MI_F_POLICY_MC_ENVELOPE || which == MI_F_POLICY_MC_ENVELOPE_U || which == MI_F_POLICY_MC_SAFETY) return MI_ILQR_E_BAD_ARG;   // (read-only)
   if (h && which == MI_F_PLANT_STATE) return set_plant_state(h, src, bytes);     // (src == NULL, bytes == 0: no plant)
   if (h && which == MI_F_PLANT_PARAMS) return set_plant_params(h, src, bytes);   // (the same: the problems' model rows)
   if (h && which == MI_F_PLANT_NOISE) return set_noise_rows(h, h->plant_noise, src, bytes);

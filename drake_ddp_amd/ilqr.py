@@ -271,16 +271,125 @@ class PolicySamples:
         self.x0, self.params, self.cost, self.steps = x0, params, cost, steps
 
 
+def check_mc_observe(envelope, controls, safe_box, B, n):
+    """RolloutPolicyStats' observing arguments -> (bits, box): bits the value of MI_F_POLICY_MC_OBSERVE (1 state envelopes, 2 control
+    envelopes), box None or the contiguous (B, 2 n) float64 rows lo | hi of MI_F_POLICY_MC_BOX.  safe_box: None or a pair (lo, hi),
+    each None - unbounded - or (n,) / (B, n) with +-inf for an unbounded component.  ValueError - decided here, before anything
+    reaches the device - for a flag that is no bool, a safe_box that is no pair, any other shape, a NaN, or lo > hi anywhere."""
+    for name, v in (("envelope", envelope), ("controls", controls)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"RolloutPolicyStats: {name} must be True or False; got {v!r}")
+    bits = (_capi.MC_OBSERVE_X if envelope else 0) | (_capi.MC_OBSERVE_U if controls else 0)
+    if safe_box is None:
+        return bits, None
+    if not isinstance(safe_box, (tuple, list)) or len(safe_box) != 2:
+        raise ValueError("RolloutPolicyStats: safe_box must be a pair (lo, hi)")
+    box = np.empty((B, 2 * n))
+    for j, (name, v, dflt) in enumerate((("safe_box lo", safe_box[0], -np.inf), ("safe_box hi", safe_box[1], np.inf))):
+        if v is None:
+            box[:, j * n:(j + 1) * n] = dflt
+            continue
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"RolloutPolicyStats: {name} is not an array of numbers ({e})") from None
+        if a.shape != (n,) and a.shape != (B, n):
+            raise ValueError(f"RolloutPolicyStats: {name} must be ({n},) or ({B}, {n}); got {a.shape}")
+        if np.isnan(a).any():
+            raise ValueError(f"RolloutPolicyStats: NaN in {name}")
+        box[:, j * n:(j + 1) * n] = a
+    if (box[:, :n] > box[:, n:]).any():
+        raise ValueError("RolloutPolicyStats: safe_box has lo > hi")
+    return bits, box
+
+
+def _chan(nA, meanA, m2A, nB, meanB, m2B):
+    """include/mi_ilqr.h's merge of (count, mean, M2), A the operand of the lower sample numbers; a count-0 side leaves the other's."""
+    fA, fB = nA.astype(np.float64), nB.astype(np.float64)
+    n = fA + fB
+    with np.errstate(invalid="ignore", divide="ignore"):
+        delta = meanB - meanA
+        mean = meanA + delta * (fB / n)
+        m2 = (m2A + m2B) + (delta * delta) * ((fA * fB) / n)
+    return (np.where(fB == 0, meanA, np.where(fA == 0, meanB, mean)), np.where(fB == 0, m2A, np.where(fA == 0, m2B, m2)))
+
+
+class PolicyEnvelope:
+    """Per-step statistics over the samples of a RolloutPolicyStats(..., envelope=True / controls=True) call, arrays (B, N, n) - for
+    the controls (B, N-1, m): count, the samples that held a finite value at that step (a sample that ended leaves its later
+    steps out); mean, m2 (the sum of squared deviations), min, max over those; argmin / argmax the global sample numbers of min /
+    max (-1 where count is 0, and there mean = m2 = NaN, min = +inf, max = -inf)."""
+    __slots__ = ("count", "mean", "m2", "min", "max", "argmin", "argmax")
+
+    def __init__(self, count, mean, m2, min, max, argmin, argmax):   # noqa: A002
+        self.count, self.mean, self.m2, self.min, self.max, self.argmin, self.argmax = count, mean, m2, min, max, argmin, argmax
+
+    @classmethod
+    def from_raw(cls, raw):
+        """raw (..., 8): the accumulators count | K | s1 | s2 | min | max | argmin | argmax of MI_F_POLICY_MC_ENVELOPE, finalised by
+        the header's formulas mean = K + s1 / count, M2 = max(0, s2 - s1 s1 / count)."""
+        cnt, K, s1, s2 = (raw[..., k] for k in range(4))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = K + s1 / cnt
+            m2 = np.maximum(0.0, s2 - s1 * s1 / cnt)
+        empty = cnt == 0
+        return cls(cnt.astype(np.int64), np.where(empty, np.nan, mean), np.where(empty, np.nan, m2), raw[..., 4].copy(), raw[..., 5].copy(),
+                   raw[..., 6].astype(np.int64), raw[..., 7].astype(np.int64))
+
+    @property
+    def var(self):
+        """The sample variance, m2 / (count - 1); NaN with fewer than two values."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.count > 1, self.m2 / (self.count - 1), np.nan)
+
+    def merge(self, other):
+        """The envelope of self's samples and those of a DISJOINT, LATER window (other): counts add, extrema by comparison with ties
+        to self - exact -, mean and m2 by Chan's merge - correct to round-off, not the bits of one call."""
+        mean, m2 = _chan(self.count, self.mean, self.m2, other.count, other.mean, other.m2)
+        lo, hi = other.min < self.min, other.max > self.max
+        return PolicyEnvelope(self.count + other.count, mean, m2, np.where(lo, other.min, self.min), np.where(hi, other.max, self.max),
+                              np.where(lo, other.argmin, self.argmin), np.where(hi, other.argmax, self.argmax))
+
+
+class PolicySafety:
+    """The safety box of a RolloutPolicyStats(..., safe_box=(lo, hi)) call: of n samples per problem `ran` held finite states at all
+    N steps, `safe` of those never left the box and `safe_success` of those also ended within `goal` of the target, (B,) each;
+    exits (B, N): the samples whose FIRST state outside the box is x_t (the box only observes: a sample goes on)."""
+    __slots__ = ("n", "ran", "safe", "safe_success", "exits")
+
+    def __init__(self, n, ran, safe, safe_success, exits):
+        self.n, self.ran, self.safe, self.safe_success, self.exits = n, ran, safe, safe_success, exits
+
+    @classmethod
+    def from_rows(cls, n, rows):
+        """rows: the (B, 3 + N) array of MI_F_POLICY_MC_SAFETY."""
+        r = rows.astype(np.int64)
+        return cls(np.asarray(n, dtype=np.int64), r[:, 0], r[:, 1], r[:, 2], r[:, 3:])
+
+    @property
+    def survival(self):
+        """(B, N): the share of the samples that have not left the box up to and including step t, 1 - cumsum(exits) / n."""
+        return 1.0 - np.cumsum(self.exits, axis=-1) / np.asarray(self.n)[..., None]
+
+    def merge(self, other):
+        """Integer counters: they add, exactly."""
+        return PolicySafety(self.n + other.n, self.ran + other.ran, self.safe + other.safe, self.safe_success + other.safe_success,
+                            self.exits + other.exits)
+
+
 class PolicyStats:
     """What RolloutPolicyStats returns, (B,) arrays: n samples, of which `counted` ran to the end with a finite cost and `success`
     also ended within `goal` of the target; mean, m2 (the sum of squared deviations), min, max over the counted samples; argmin /
     argmax the global sample numbers of min / max (-1 without a counted sample); steps_total the steps of all n samples.
-    samples: None or a PolicySamples."""
-    __slots__ = ("n", "counted", "success", "mean", "m2", "min", "max", "argmin", "argmax", "steps_total", "samples")
+    samples: None or a PolicySamples.  envelope, control_envelope: None or a PolicyEnvelope; safety: None or a PolicySafety."""
+    __slots__ = ("n", "counted", "success", "mean", "m2", "min", "max", "argmin", "argmax", "steps_total", "samples", "envelope",
+                 "control_envelope", "safety")
 
-    def __init__(self, n, counted, success, mean, m2, min, max, argmin, argmax, steps_total, samples=None):   # noqa: A002
+    def __init__(self, n, counted, success, mean, m2, min, max, argmin, argmax, steps_total, samples=None, envelope=None,   # noqa: A002
+                 control_envelope=None, safety=None):
         self.n, self.counted, self.success, self.mean, self.m2 = n, counted, success, mean, m2
         self.min, self.max, self.argmin, self.argmax, self.steps_total, self.samples = min, max, argmin, argmax, steps_total, samples
+        self.envelope, self.control_envelope, self.safety = envelope, control_envelope, safety
 
     @classmethod
     def from_rows(cls, rows, samples=None):
@@ -301,7 +410,10 @@ class PolicyStats:
     def merge(self, other):
         """Chan's merge with the result of a DISJOINT, LATER window of samples (first_sample): how a sample set split over calls or
         ranks is put together.  self is operand A of include/mi_ilqr.h's merge; a side without a counted sample leaves the other's
-        numbers as they are; ties of min / max keep self's sample."""
+        numbers as they are; ties of min / max keep self's sample.  envelope, control_envelope and safety are joined too where both
+        sides hold them (else None): their counts, exits, extrema and argmin / argmax exactly, their mean / m2 correct to round-off
+        (Chan's merge of two finalised halves is not the one left fold's bits)."""
+        both = lambda k: None if getattr(self, k) is None or getattr(other, k) is None else getattr(self, k).merge(getattr(other, k))   # noqa: E731
         nA, nB = self.counted.astype(np.float64), other.counted.astype(np.float64)
         n = nA + nB
         with np.errstate(invalid="ignore", divide="ignore"):
@@ -313,7 +425,8 @@ class PolicyStats:
         lo, hi = other.min < self.min, other.max > self.max
         return PolicyStats(self.n + other.n, self.counted + other.counted, self.success + other.success, mean, m2,
                            np.where(lo, other.min, self.min), np.where(hi, other.max, self.max), np.where(lo, other.argmin, self.argmin),
-                           np.where(hi, other.argmax, self.argmax), self.steps_total + other.steps_total)
+                           np.where(hi, other.argmax, self.argmax), self.steps_total + other.steps_total, None, both("envelope"),
+                           both("control_envelope"), both("safety"))
 
 
 class PlantLog:
@@ -1001,7 +1114,8 @@ class BatchedIterativeLQR:
             self._policy_noise_set = False
 
     def RolloutPolicyStats(self, S, x0_mean, x0_spread, *, x0_dist="normal", params_mean=None, params_spread=None, params_dist="uniform",
-                           goal=None, state_noise=None, control_noise=None, seed=0, first_sample=0, common_noise=False, samples=False):
+                           goal=None, state_noise=None, control_noise=None, seed=0, first_sample=0, common_noise=False, samples=False,
+                           envelope=False, controls=False, safe_box=None):
         """Monte-Carlo evaluation of the policy the solver holds, entirely on the device (include/mi_ilqr.h: "Monte-Carlo on the
         device"): S samples per problem are DRAWN there - x0 = x0_mean + x0_spread o d with d standard normal (x0_dist="normal") or
         uniform in (-1, 1) ("uniform"), and with params_mean / params_spread / params_dist the plants' parameters likewise -, rolled
@@ -1012,10 +1126,17 @@ class BatchedIterativeLQR:
         sample set, split over calls with first_sample, are put together with PolicyStats.merge.  samples=True also returns every
         sample's x0, params, cost and steps (PolicyStats.samples) - what RolloutPolicy reproduces: the same arithmetic up to the
         compiler's FMA contraction, bit for bit on the models DESIGN 4.2h lists as measured.  Changes nothing in
-        the solver."""
+        the solver.
+        envelope=True / controls=True: the result's `envelope` / `control_envelope` is a PolicyEnvelope, the per-step statistics of the
+        states (B, N, n) / the commanded controls (B, N-1, m) over the samples; safe_box=(lo, hi), each None or (n,) / (B, n) with
+        +-inf for no bound: its `safety` is a PolicySafety, the samples that stay inside the box and the step at which the others
+        first leave it (include/mi_ilqr.h: "Envelopes and a safety box").  All reduced on the device from the trajectories
+        RolloutPolicy(trajectories=True) returns for the same samples; the three default to off, cost nothing then, and the solver's
+        box and observe settings are after the call what they were before it."""
         n_params = int(self.system.params.size)
         rows, run = check_mc_args(S, x0_mean, x0_spread, self.B, self.n, n_params, x0_dist=x0_dist, params_mean=params_mean,
                                   params_spread=params_spread, params_dist=params_dist, goal=goal, samples=samples, first_sample=first_sample)
+        bits, box = check_mc_observe(envelope, controls, safe_box, self.B, self.n)
         noisy = state_noise is not None or control_noise is not None
         noise, stream = check_noise_args(state_noise, control_noise, seed, first_sample, common_noise, self.B, self.n, self.m,
                                          self._md if noisy else None, int(S))
@@ -1025,9 +1146,40 @@ class BatchedIterativeLQR:
         self._push_costs()
         self._set_policy_noise(noise, stream)
         _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_MC_DIST, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
-        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_MC_RUN, _capi.ptr(run), run.nbytes), "mi_ilqr_set")
+        before = np.empty(1)
+        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_OBSERVE, _capi.ptr(before), 8), "mi_ilqr_get")
+
+        def observe(v):
+            word = np.array([float(v)])
+            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_MC_OBSERVE, _capi.ptr(word), 8), "mi_ilqr_set")
+
+        set_box = lambda r: _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_MC_BOX, _capi.ptr(r), 0 if r is None else r.nbytes), "mi_ilqr_set")   # noqa: E731
+        try:
+            if before[0] != bits:
+                observe(bits)
+            if box is not None:
+                set_box(box)
+            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_MC_RUN, _capi.ptr(run), run.nbytes), "mi_ilqr_set")
+        finally:
+            if before[0] != bits:
+                observe(before[0])
+            if box is not None:
+                set_box(None)                                      # (this class leaves no box on the handle between calls)
         out = np.empty((self.B, _capi.MC_FIELDS))
         _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_STATS, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+        env = cenv = safety = None
+        if envelope:
+            raw = np.empty((self.B, self.N, self.n, _capi.MC_ENV_FIELDS))
+            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_ENVELOPE, _capi.ptr(raw), raw.nbytes), "mi_ilqr_get")
+            env = PolicyEnvelope.from_raw(raw)
+        if controls:
+            raw = np.empty((self.B, self.N - 1, self._md, _capi.MC_ENV_FIELDS))
+            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_ENVELOPE_U, _capi.ptr(raw), raw.nbytes), "mi_ilqr_get")
+            cenv = PolicyEnvelope.from_raw(raw[:, :, :self.m])
+        if box is not None:
+            raw = np.empty((self.B, 3 + self.N))
+            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_SAFETY, _capi.ptr(raw), raw.nbytes), "mi_ilqr_get")
+            safety = PolicySafety.from_rows(np.full(self.B, int(S), dtype=np.int64), raw)
         smp = None
         if samples:
             n = self.n
@@ -1036,7 +1188,9 @@ class BatchedIterativeLQR:
             smp = PolicySamples(np.ascontiguousarray(raw[:, :, :n]),
                                 np.ascontiguousarray(raw[:, :, n:n + n_params]) if params_mean is not None else None,
                                 np.ascontiguousarray(raw[:, :, n + n_params]), raw[:, :, n + n_params + 1].astype(np.int32))
-        return PolicyStats.from_rows(out, smp)
+        st = PolicyStats.from_rows(out, smp)
+        st.envelope, st.control_envelope, st.safety = env, cenv, safety
+        return st
 
     # ------------------------------------------------------------- the plant of the closed MPC loop
     def SetPlant(self, x, params=None, *, state_noise=None, control_noise=None, seed=0, common_noise=False, feedback=True, clock=0):

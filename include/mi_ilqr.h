@@ -139,6 +139,11 @@ enum {
   MI_F_POLICY_MC_RUN = 30,   /* (5,) write-only COMMAND: S | x0_dist | p_dist | sample_params | samples - mi_ilqr_set RUNS the evaluation */
   MI_F_POLICY_MC_STATS = 31, /* (B,10) read-only: S | counted | success | mean | M2 | min | max | argmin | argmax | steps_total of the last run */
   MI_F_POLICY_MC_SAMPLES = 32,/* (B,S,n+n_params+2) read-only: rows x0 | params | cost | steps of the last run, when it was asked for them */
+  MI_F_POLICY_MC_BOX = 33,   /* (B,2n) safety box rows lo | hi, +-inf = unbounded ("Envelopes and a safety box" below) */
+  MI_F_POLICY_MC_OBSERVE = 34,/* (1,) what a run observes beside the cost: bit 0 state envelopes, bit 1 control envelopes, an integer held in a double */
+  MI_F_POLICY_MC_ENVELOPE = 35,/* (B,N,n,8) read-only: count | K | s1 | s2 | min | max | argmin | argmax of every state row of the last run */
+  MI_F_POLICY_MC_ENVELOPE_U = 36,/* (B,N-1,m,8) read-only: the same of every control row, m the device's control dimension */
+  MI_F_POLICY_MC_SAFETY = 37,/* (B,3+N) read-only: ran | safe | safe_success | exits[0 .. N-1] of the last run, integers held in doubles */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
@@ -672,6 +677,42 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
  *                                            parameters, or problem b's row when they were not drawn.
  *   MI_F_POLICY_KERNEL_MS after a run: the rollout kernels of that run, summed over its passes.  The fold kernels are NOT included.
  *   mi_ilqr_get_int(MI_I_POLICY_MC_PASSES, &k, 4): the passes that run took (before any run MI_ILQR_E_BAD_ARG). */
+
+/* ---- Envelopes and a safety box (ABI 10; selectors of mi_ilqr_set / mi_ilqr_get, no new entry point) ----
+ * What a MI_F_POLICY_MC_RUN observes BESIDE the cost, reduced on the device: per-step statistics of the states and of the controls over
+ * the samples, and the samples that stay inside a box.  The values reduced are the trajectories mi_ilqr_policy_rollout returns for the
+ * same samples (X, U: NaN from the step at which a sample ended); nothing of size S crosses the bus.  A run that observes nothing
+ * is the run it was: its ten numbers, its samples, MI_F_POLICY_KERNEL_MS and its pass count do not change.
+ *   mi_ilqr_set(MI_F_POLICY_MC_OBSERVE, &v, 8)   v = 0 .. 3, an integer held in a double: bit 0 state envelopes, bit 1 control
+ *                                            envelopes.  Persists on the handle.  Any other value: MI_ILQR_E_BAD_ARG.
+ *   mi_ilqr_set(MI_F_POLICY_MC_BOX, rows, B*2n*8)   row b = lo | hi, +inf / -inf = unbounded.  A NaN or lo > hi: MI_ILQR_E_BAD_ARG.
+ *                                            (NULL, 0) clears the box.  While the handle holds a box, runs observe it.  mi_ilqr_get
+ *                                            reads the rows back (zeros while not set).  Survives mi_ilqr_reset.
+ * THE FOLD.  A row is one (t, i) of one problem: the S values x_t[i] (u_t[k]) of its samples.  Per row eight doubles,
+ *     count | K | s1 | s2 | min | max | argmin | argmax
+ * are a LEFT FOLD in global sample order g = first_sample + s, s ascending: a non-finite v is skipped; the first finite v sets K = v;
+ * then d = v - K, s1 += d, s2 += d d (a rounded product, then a rounded sum: no FMA), count += 1; min and max use strict comparisons, so
+ * a tie keeps the lower sample number; argmin / argmax are global sample numbers.  An empty row: count = 0, K = s1 = s2 = 0,
+ * min = +inf, max = -inf, argmin = argmax = -1.  The caller finalises:
+ *     mean = K + s1 / count,   M2 = max(0, s2 - s1 s1 / count)
+ * (the shifted-data one-pass variance; M2 the sum of squared deviations from the mean).  The order is fixed and nothing is contracted:
+ * the eight doubles do not depend on the window (MI_ILQR_MC_PASS_GROUPS), bit for bit.
+ * THE BOX.  Per sample: ran - all N states are finite; the state x_t is OUTSIDE if x_t[i] < lo[i] or x_t[i] > hi[i] for some i
+ * (comparisons: a NaN is never outside, a value on a bound is inside); exit - the first t at which the sample is outside, t = 0
+ * included; safe = ran and never outside; safe_success = safe and |x_{N-1}[i] - x_nom_b[i]| <= goal[b,i] for every i (the success
+ * criterion above, on the run's target and goal rows).  The box only observes: a sample goes on after leaving it.  Per problem
+ *     ran | safe | safe_success | exits[0 .. N-1]
+ * with exits[t] the number of samples whose first outside state is x_t; integers, added as integers.
+ *   mi_ilqr_get(MI_F_POLICY_MC_ENVELOPE, dst, B*N*n*8*8)        the state rows of the last run, when bit 0 was set for it
+ *   mi_ilqr_get(MI_F_POLICY_MC_ENVELOPE_U, dst, B*(N-1)*m*8*8)  the control rows (the COMMANDED controls, m the device's: padding
+ *                                            controls read as exact zeros), when bit 1 was set
+ *   mi_ilqr_get(MI_F_POLICY_MC_SAFETY, dst, B*(3+N)*8)          the counters, when the handle held a box
+ *                                            When the last run did not produce them: MI_ILQR_E_BAD_ARG.  Setting one of the three:
+ *                                            MI_ILQR_E_BAD_ARG (read-only).  Wrong `bytes` anywhere: MI_ILQR_E_BAD_SHAPE.  A refused
+ *                                            call changes nothing.
+ * The trajectories of a window of samples stay in the handle's grow-only scratch (about 1 GiB per pass at most, never less than one
+ * group of 64 samples per problem); when that memory cannot be had the run is refused with MI_ILQR_E_UNSUPPORTED and the last results
+ * stay in place. */
 
 #ifdef __cplusplus
 }

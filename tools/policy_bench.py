@@ -13,7 +13,9 @@ of B S problems (fx alone is B S n^2 (N-1) doubles: 27 GB for Quad3D at S = 1024
 compare across S.  --noise: the same rollouts again with process and actuation noise (state_noise / control_noise: the noisy
 kernels of csrc/policy_rollout.hpp, a Philox block and its Box-Muller normals per four components and step) and the ratio of the
 two kernel times.  --mc: the whole call instead - RolloutPolicy on host arrays plus the NumPy reduction against RolloutPolicyStats
-(csrc/policy_mc.hpp), wall and kernel times (mc_bench).  Prints one JSON line."""
+(csrc/policy_mc.hpp), wall and kernel times (mc_bench).  --mc --envelope [--host-fold N]: RolloutPolicyStats plain, with state envelopes,
+and with both envelopes and a safety box, beside RolloutPolicy(trajectories=True) plus the NumPy fold (envelope_bench).  Prints one
+JSON line."""
 import argparse
 import json
 import os
@@ -120,6 +122,85 @@ def mc_bench(a):
     print(json.dumps(out))
 
 
+def host_fold(r, lo, hi):
+    """What a caller did before the device reduced them: RolloutPolicy's trajectories X (B, S, n, N) / U to per-step count, mean, M2,
+    min, max, argmin, argmax over the samples, and the box counts, in vectorised NumPy."""
+    out = []
+    for V in (r.X, r.U):
+        ok = np.isfinite(V)
+        cnt = ok.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = np.nansum(np.where(ok, V, np.nan), axis=1) / cnt
+            m2 = np.nansum(np.where(ok, V - mean[:, None], np.nan) ** 2, axis=1)
+        out.append((cnt, mean, m2, np.min(np.where(ok, V, np.inf), axis=1), np.max(np.where(ok, V, -np.inf), axis=1),
+                    np.argmin(np.where(ok, V, np.inf), axis=1), np.argmax(np.where(ok, V, -np.inf), axis=1)))
+    with np.errstate(invalid="ignore"):
+        outside = ((r.X < lo[:, None, :, None]) | (r.X > hi[:, None, :, None])).any(axis=2)      # (B, S, N)
+    ran = np.isfinite(r.X).all(axis=(2, 3))
+    ever = outside.any(axis=2)
+    first = np.where(ever, np.argmax(outside, axis=2), -1)
+    exits = np.stack([np.bincount(f[f >= 0], minlength=r.X.shape[3]) for f in first])
+    out.append((ran.sum(axis=1), (ran & ~ever).sum(axis=1), exits))
+    return out
+
+
+def envelope_bench(a):
+    """--mc --envelope: the WHOLE call with what a run observes beside the cost (csrc/policy_env.hpp), S = 1024 samples per problem:
+    (a) plain RolloutPolicyStats, (b) with state envelopes, (c) with state and control envelopes and a box - alternated, `reps` timed
+    calls after `warmup` in each of two rounds: median [min .. max] of the wall times, and the rollout kernels' own milliseconds.
+    --host-fold N: also (d), N times: RolloutPolicy(trajectories=True) on starts drawn in NumPy plus the NumPy reduction (host_fold) -
+    the only equivalent there was; it uses nothing this feature added, so with --reps 0 it runs on an older checkout as well."""
+    import time
+    out = {}
+    for config in a.configs.split(","):
+        p, B, x0b, ug, sigma = problem(config)
+        N, n, S = p["N"], x0b.shape[1], 1024
+        s = solver(p, B, max_iters=5)
+        s.SetInitialState(x0b); s.SetInitialGuess(ug)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            s.Solve()
+        spread = sigma * np.ones(n)
+        lo, hi = np.full((B, n), -np.inf), x0b + 3.0 * sigma               # a box most samples stay in for a while
+        res = dict(B=B, S=S, N=N, state_window_bytes=8 * B * N * n * S)
+        if a.reps > 0:
+            forms = (("plain", {}), ("states", dict(envelope=True)), ("all", dict(envelope=True, controls=True, safe_box=(lo, hi))))
+            wall, kern = {k: [] for k, _ in forms}, {k: [] for k, _ in forms}
+            for rnd in range(2):
+                for i in range(a.warmup + a.reps):
+                    for k, more in forms:                                  # alternated: a, b, c, a, b, c, ...
+                        t0 = time.perf_counter()
+                        st = s.RolloutPolicyStats(S, x0b, spread, seed=7, **more)
+                        t1 = time.perf_counter()
+                        if i >= a.warmup:
+                            wall[k].append(1e3 * (t1 - t0)); kern[k].append(s.policy_kernel_ms())
+                        res["passes_" + k] = s.policy_mc_passes()
+                        if st.safety is not None:
+                            res["safe_share"] = float(st.safety.safe.sum() / (B * S))
+                        del st                                             # (an observing result is tens of MB: freed outside the next call's clock)
+            res["on_device"] = {k: dict(wall_ms=spread3(wall[k]), rollout_kernel_ms=spread3(kern[k])) for k, _ in forms}
+            res["states_over_plain"] = float(np.median(wall["states"]) / np.median(wall["plain"]))
+            res["all_over_plain"] = float(np.median(wall["all"]) / np.median(wall["plain"]))
+        if a.host_fold > 0:
+            x0_same = x0b[:, None, :] + sigma * np.random.default_rng(7).standard_normal((B, S, n))     # (drawn here: any build runs this part)
+            parts = dict(wall=[], call=[], reduce=[])
+            for i in range(a.host_fold):
+                t0 = time.perf_counter()
+                r = s.RolloutPolicy(x0_same, trajectories=True, seed=7)
+                t1 = time.perf_counter()
+                red = host_fold(r, lo, hi)
+                t2 = time.perf_counter()
+                for k, v in (("wall", t2 - t0), ("call", t1 - t0), ("reduce", t2 - t1)):
+                    parts[k].append(1e3 * v)
+                del r
+            res["host_fold"] = {k + "_ms": spread3(v) for k, v in parts.items()}
+            res["host_fold_safe_share"] = float(red[2][1].sum() / (B * S))
+            if "on_device" in res:
+                res["host_fold_over_states"] = float(np.median(parts["wall"]) / np.median(wall["states"]))
+        out["%s_S%d" % (config, S)] = res
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -129,7 +210,11 @@ def main():
     ap.add_argument("--emulate-up-to", type=int, default=65536)
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--mc", action="store_true")
+    ap.add_argument("--envelope", action="store_true")
+    ap.add_argument("--host-fold", type=int, default=0)
     a = ap.parse_args()
+    if a.mc and a.envelope:
+        return envelope_bench(a)
     if a.mc:
         return mc_bench(a)
     out = {}
