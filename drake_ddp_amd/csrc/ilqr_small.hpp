@@ -1420,10 +1420,34 @@ __device__ inline void backward_mfma(const WS& w, const Consts<M>& c) {
 // gives every lane the value function at the right edge of its chunk; (3) from there each lane
 // runs the REFERENCE recursion (ilqr.py:651-667, backward_step) over its own few steps and
 // writes K_t, kappa_t, dV_t.  ~1.7 k instructions instead of ~12 k on the critical path.
-// Only the chunk-edge value functions come out of the re-associated arithmetic: measured against
-// the sequential sweep on C2 iterations the gains agree to <= 4e-13 relative
-// (oracle-side prototype: same formulas in NumPy), inside every tolerance of the parity tests.
+// Only the chunk-edge value functions come out of the re-associated arithmetic.  What that costs depends
+// on cond(I + C_i J_j): on C2 iterates the gains agree with the sequential sweep to <= 4e-13 relative, on
+// C4 iterates (cond <= 1e5) the NumPy statement of the scan (tests/riccati_scan_np.py) stays within 6e-12
+// of the extended-precision pass, but the compositions lose digits in proportion to that condition number - measured
+// against the reference recursion in extended precision (tests/test_gpu_small_backward.py) the unguarded
+// scan was 8 x outside the yardstick on the acrobot's own cost at N = 130 (cond 3e4), 1e5 x outside with
+// R x 1e-3, Qf x 100 (cond 3e8, gains off by 5e-3), and 270 x outside on the pendulum with R x 1e-9
+// (cond 2e12), where the sequential sweep stays inside everywhere.  So the scan checks its own result
+// (phase (4) of backward_scan) and hands the pass to the sequential sweep when it cannot be trusted.
 // ---------------------------------------------------------------------------
+// Largest disagreement between the gain a lane wrote for the first step of its chunk - computed from the scan's value
+// function - and the same gain from the value function the neighbouring lane's recursion arrives at, relative to the largest such
+// gain in the wave, beyond which the pass is redone sequentially (backward_scan, phase (4)).  The iterates of C2 and C4 stay
+// below 3e-13; the first pass that misses the yardstick sits at 1.4e-11.
+constexpr double kScanGainTol = 2e-12;
+// n = 2: largest relative disagreement (max-norm of Vxx's upper triangle) between the scan's value function at the left edge of a
+// lane's chunk and the one the lane's own recursion arrives at.  The iterates of C2 stay below 8e-14; passes up to 1e-9 are
+// inside the yardstick, the first that misses it sits at 6e-8.
+constexpr double kScanEdgeTol = 1e-10;
+// Maximum over the wave of non-negative values, result in every lane: wave_sum's moves (wave_ops.hpp).
+__device__ __forceinline__ double wave_max(double v) {
+  v = fmax(v, row_ror_f64<8>(v));
+  v = fmax(v, row_ror_f64<4>(v));
+  v = fmax(v, row_ror_f64<2>(v));
+  v = fmax(v, row_ror_f64<1>(v));
+  return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
+}
+
 template <int n>
 struct RicElem {
   double A[n][n], b[n], C[n][n], e[n], J[n][n];
@@ -1442,7 +1466,11 @@ __device__ __forceinline__ void ric_identity(RicElem<n>& r) {
 // M = P^-1 for P = I + C_i J_j.  n = 2: adjugate / determinant (det >= 1: C, J are PSD).  n > 2:
 // Gauss-Jordan WITHOUT pivoting - P is not symmetric and a pivot can in principle come out small or
 // negative although det P >= 1, so the smallest pivot magnitude is reported and the caller falls back
-// to the sequential sweep when it is not comfortably away from zero (never seen on the configs).
+// to the sequential sweep when it is not comfortably away from zero.  Pivots of 1e-3 .. 7e-2 do occur on
+// C4-like inputs (acrobot / cart-pole with wall, N = 130 .. 200, R x 1e-3, Qf x 100), but the pivot size
+// says little about the accuracy: the loss of digits follows cond(P), and passes with every pivot above
+// 1e-2 were 1e4 x outside the yardstick.  This check only keeps a near-zero pivot from producing
+// infinities; the accuracy guard is phase (4) of backward_scan.
 template <int n>
 __device__ __forceinline__ void ric_invert(const double (&P)[n][n], double (&Mi)[n][n], double& min_pivot) {
   if constexpr (n == 2) {
@@ -1752,7 +1780,72 @@ __device__ inline bool backward_scan(const WS& w, const Consts<M>& c) {
       riccati_step(q, t);
     }
   }
-  return true;
+  // ---- (4) the scan checks itself.  Lane l - 1's recursion has just carried Vxx to the left edge of its chunk - the right edge
+  // of this lane's, where this lane STARTED from the scan's value.  The gain of this lane's first step is computed once more from
+  // the recursed Vxx (K = Quu^-1 fu^T Vxx fx: ~40 multiply-adds) and compared with the one written above.  The two agree to
+  // round-off while the compositions kept their digits; cond(I + C_i J_j) takes them away (small R, large Qf, long or stiff
+  // horizons), and then the gains are off by orders of magnitude more than the sequential sweep's.  One lane beyond
+  // kScanGainTol of the largest such gain in the wave: the caller redoes the pass sequentially, which overwrites everything
+  // written above.  K only: kappa and dV pass through zero as a solve converges.  NaNs fail the comparison.
+  // Thresholds and measurements: DESIGN 8.
+  // n = 2: the gain check's LDS reads (one lane per bank row: serialized) and wave maximum cost the C2 pass 10 % (+3.5 % per
+  // solve).  There the plain comparison of value functions separates as well, at a dozen instructions: the recursion has also
+  // carried Vxx to the LEFT edge of this lane's chunk, where the scan holds the same quantity in this lane's own J.  (For
+  // n = 4 it does not: the stiff C4 iterates reach 3e-12 there with gains inside the yardstick, the acrobot's failing passes
+  // start at 2e-12.)
+  if constexpr (n == 2) {
+    bool edge_ok = true;
+    if (t_hi >= e0) {                                       // (lanes past the horizon ran no step)
+      double d = 0.0, s = 0.0;
+#pragma unroll
+      for (int i = 0; i < n; ++i)
+#pragma unroll
+        for (int j = i; j < n; ++j) { d = fmax(d, fabs(Vxx[i][j] - S.J[i][j])); s = fmax(s, fabs(S.J[i][j])); }
+      edge_ok = d <= kScanEdgeTol * s;
+    }
+    return __all(edge_ok);
+  }
+  double Vr[n][n];
+#pragma unroll
+  for (int i = 0; i < n; ++i)
+#pragma unroll
+    for (int j = 0; j < n; ++j) Vr[i][j] = dpp_f64_or_zero<0x138, 0xF>(Vxx[i][j]);   // wave_shr:1
+  const int t1 = e0 + chunk - 1;                            // this lane's first step, when it started from the scan's value:
+  const bool from_scan = t1 < N - 1;                        // (then lane l - 1 exists and holds the steps after t1, or the terminal value)
+  double Kr[n], Ks[n], ks = 0.0;
+#pragma unroll
+  for (int j = 0; j < n; ++j) Kr[j] = Ks[j] = 0.0;
+  if (from_scan) {
+    const double* jr = w.J + t1 * Ly::JS;
+    const double* kk = w.G + t1 * Ly::GS + Ly::KK;
+    double fu[n], Bm[n], quu = R2[0][0];
+#pragma unroll
+    for (int i = 0; i < n; ++i) fu[i] = jr[Ly::FU + i * m];
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < n; ++k) s += fu[k] * Vr[k][j];
+      Bm[j] = s;                                            // fu^T Vxx
+    }
+#pragma unroll
+    for (int k = 0; k < n; ++k) quu += Bm[k] * fu[k];
+    const double iq = fast_rcp(quu);
+#pragma unroll
+    for (int j = 0; j < n; ++j) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < n; ++k) s += Bm[k] * jr[Ly::FX + k * n + j];
+      Kr[j] = s * iq;
+      Ks[j] = kk[j];
+      ks = fmax(ks, fabs(Kr[j]));
+    }
+  }
+  const double bound = kScanGainTol * wave_max(ks);
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < n; ++j) ok = ok && fabs(Kr[j] - Ks[j]) <= bound;
+  return __all(ok);
 }
 
 // n = 3..4: the scan keeps three n x n elements and the temporaries of a composition live - all 512
@@ -1792,7 +1885,7 @@ __device__ inline void backward(const WS& w, const Consts<M>& c, int mode = 0) {
     }
     backward_mfma<M>(w, c);
   }
-  else if constexpr (M::n == 2 && M::m == 1) { if (sequential) backward_scalar<M>(w, c); else backward_scan<M>(w, c); }
+  else if constexpr (M::n == 2 && M::m == 1) { if (sequential || !backward_scan<M>(w, c)) backward_scalar<M>(w, c); }
   else backward_scalar<M>(w, c);
 }
 
