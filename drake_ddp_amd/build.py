@@ -2,8 +2,8 @@
 
     python -m drake_ddp_amd.build [--force] [--resource-usage]
 
-One translation unit per model's kernels (csrc/k_<model>.hip) plus the host side of the C ABI
-(csrc/mi_ilqr.hip), compiled in parallel and linked into drake_ddp_amd/lib/libmi_ilqr.so (git-ignored,
+One translation unit per model's kernels (csrc/k_<model>.hip) plus the host side of the C ABI, a unit per
+concern (csrc/mi_ilqr.hip and csrc/h_<concern>.hip: host_sources()), compiled in parallel and linked into drake_ddp_amd/lib/libmi_ilqr.so (git-ignored,
 but it travels to the GPU box with the gpurun snapshot).  hipcc cross-compiles without a GPU.
 Objects are cached in drake_ddp_amd/lib/obj, each beside the dependency file the compiler wrote for it (<obj>.d), and rebuilt
 when their source, a file it includes or the flags change.
@@ -32,6 +32,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math"
 
 def sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
+
+
+def host_sources():
+    """The host units: every unit that is not a kernel unit (k_*.hip)."""
+    return [s for s in sources() if not os.path.basename(s).startswith("k_")]
 
 
 def headers():
@@ -114,21 +119,21 @@ ASAN_RT = "/opt/rocm/lib/llvm/lib/clang/22/lib/linux/libclang_rt.asan-x86_64.so"
 
 
 def build_asan(verbose=False):
-    """libmi_ilqr_asan.so: the HOST side of the C ABI (csrc/mi_ilqr.hip) instrumented with AddressSanitizer, linked
+    """libmi_ilqr_asan.so: the HOST side of the C ABI (host_sources()) instrumented with AddressSanitizer, linked
     with the regular kernel objects (device code cannot be instrumented on gfx950).  tests/test_gpu_asan.py drives it."""
     build(verbose=verbose)
-    host_src = os.path.join(CSRC, "mi_ilqr.hip")
-    obj = os.path.join(OBJDIR, "mi_ilqr-asan.o")
-    if _stale(obj, host_src):
-        cmd = [HIPCC] + [f for f in FLAGS if f != "-O3"] + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address", "-shared-libsan",
-                                                           "-Wno-option-ignored", "-MD", "-MF", obj + ".d", "-c", host_src, "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-    if not os.path.exists(ASAN_LIB) or os.path.getmtime(ASAN_LIB) < max(os.path.getmtime(obj), os.path.getmtime(LIB)):
-        objs = [_obj(s_, "") for s_ in sources() if os.path.basename(s_) != "mi_ilqr.hip"]
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address", "-shared-libsan", "-Wno-option-ignored",
-                               obj] + objs + ["-o", ASAN_LIB, "-ldl"])
+    flags = [f for f in FLAGS if f != "-O3"] + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address", "-shared-libsan", "-Wno-option-ignored"]
+    host = [(s, _obj(s, "-asan")) for s in host_sources()]
+    for src, obj in host:
+        if _stale(obj, src):
+            _, rc, out = _compile(src, obj, flags, verbose)
+            if rc != 0:
+                sys.stderr.write(out)
+                raise subprocess.CalledProcessError(rc, [HIPCC, src])
+    if not os.path.exists(ASAN_LIB) or os.path.getmtime(ASAN_LIB) < max([os.path.getmtime(o) for _, o in host] + [os.path.getmtime(LIB)]):
+        objs = [_obj(s_, "") for s_ in sources() if s_ not in host_sources()]
+        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address", "-shared-libsan", "-Wno-option-ignored"] +
+                              [o for _, o in host] + objs + ["-o", ASAN_LIB, "-ldl"])
     return ASAN_LIB
 
 

@@ -1,6 +1,6 @@
 // Host-side pieces shared by the translation units of libmi_ilqr.so: the handle, the error macro and the
-// kernel-launch templates.  mi_ilqr.hip holds the C ABI; every model's kernels are instantiated in their own
-// k_<model>.hip (built in parallel, drake_ddp_amd/build.py), reached through the model's launch entry (launch_entry below).
+// kernel-launch templates.  mi_ilqr.hip and the h_<concern>.hip units hold the C ABI (what only they share: host_internal.hpp);
+// every model's kernels are instantiated in their own k_<model>.hip (built in parallel, drake_ddp_amd/build.py), reached through the model's launch entry (launch_entry below).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -19,7 +19,7 @@
 
 // One per-problem (B, width) array of a handle (mi_ilqr_set MI_F_X_NOM / MI_F_TARGET_STEP / MI_F_MODEL_PARAMS / MI_F_COST_MATRICES /
 // MI_F_POLICY_NOISE / MI_F_PLANT_STATE / MI_F_PLANT_PARAMS / MI_F_PLANT_NOISE;
-// mi_ilqr.hip: store_upload / store_drop / store_read).  The host mirror is the truth: what mi_ilqr_get returns without touching the
+// h_memory.hip: store_upload / store_drop / store_read).  The host mirror is the truth: what mi_ilqr_get returns without touching the
 // stream and what mi_ilqr_mpc_run advances; the device copies follow it on the handle's stream.  `synced` - they equal it - is the
 // array's per-problem mode: only then do the kernels get the pointers, a failed copy leaves the mode, and rows the caller repeats
 // (Solve() pushes them on every call) are not sent again.  The buffers are allocated on first use and kept when the mode is

@@ -1,6 +1,6 @@
 // What crosses the launch boundary: the argument block every solve kernel takes by value (KArgs), the kernel modes, the per-solve
 // statistics record, and the accessors that say where a problem's target, cost matrices and model parameters live.  Shared by the
-// host (host.hpp, mi_ilqr.hip) and by every kernel family; knows no model and no key-point code.
+// host (host.hpp, the host units) and by every kernel family; knows no model and no key-point code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -70,7 +70,7 @@ MI_MODEL_TRAIT(HasPivSplit, kPivSplit, bool, false, M::kPivSplit);
 
 // The same model with the kernels' backward pass run as the time-parallel scan.  For n = 3..4 the scan
 // pays from two steps per lane on (N > 128) and its register appetite must not touch the kernels of
-// short horizons, so the host picks this instantiation by horizon (mi_ilqr.hip: launch_jac).
+// short horizons, so the host picks this instantiation by horizon (launch_small.hpp: launch_jac).
 template <class M>
 struct LongHorizon : M { static constexpr bool kScanBackward = true; };
 // The same model with the kernels' backward pass run as the reference's scalar recursion verbatim

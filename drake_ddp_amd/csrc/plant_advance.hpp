@@ -7,7 +7,7 @@
 //
 // Contrast with policy_rollout.hpp, where a wave serves one problem and reads the policy through the scalar unit: here a lane IS a
 // problem, so the policy row, the cost matrices, the target, the bounds, the sigmas and the parameters all differ between lanes and
-// nothing is wave-uniform.  The host stages them PROBLEM-MINOR (mi_ilqr.hip: plant_pack_kernel, rows_to_cols_kernel): element e of
+// nothing is wave-uniform.  The host stages them PROBLEM-MINOR (h_policy.hip: pack_policy; h_mpc.hip: rows_to_cols_kernel): element e of
 // problem b at e * B + b, so that a wave's load of one element is a contiguous run of 64 doubles.  The log is written problem-minor
 // too and transposed once when it is read out.  The plant state itself is the (B, n) array the selector exposes: n loads and n
 // stores per lane and launch.

@@ -10,7 +10,7 @@
 // parameters.  They are read-only kernel arguments the kernel never writes (`const __restrict__`), indexed by uniform values only:
 // the compiler reads them through the scalar unit (s_load into SGPRs, an SGPR operand of the v_fma_f64 that uses the value) - one
 // fetch per wave instead of 64 identical vector loads, and no vector register per value.  The policy arrives as the call's own
-// time-major copy (mi_ilqr.hip: policy_pack_kernel), whatever the layout the handle's solver kernels keep it in.
+// time-major copy (h_policy.hip: pack_policy), whatever the layout the handle's solver kernels keep it in.
 // What differs between lanes is sample-minor in memory - x0 (B, n, S), the per-sample parameters (B, n_params, S), the outputs - so a
 // wave's loads and stores are contiguous.
 //

@@ -1,6 +1,6 @@
 """The layering of the native headers (drake_ddp_amd/csrc/*.hpp; DESIGN.md, "Source layout"): every header compiles as the only
 include of a translation unit, and the `#include "..."` lines keep the kernel families apart - no family header includes
-another, the host (host.hpp, mi_ilqr.hip) includes none of them, policy_rollout.hpp names what it uses.  Compile-only
+another, the host (host.hpp, host_internal.hpp and every host unit) includes none of them, policy_rollout.hpp names what it uses.  Compile-only
 (-fsyntax-only) and text checks: needs hipcc, no GPU."""
 import os
 import re
@@ -64,10 +64,48 @@ def test_policy_rollout_names_what_it_uses():
     assert {"host.hpp", "fastmath.hpp", "model_traits.hpp", "models.hpp"} <= set(includes("policy_rollout.hpp"))
 
 
+HOST_UNITS = sorted(os.path.basename(s) for s in build.host_sources())
+INTERNAL = "host_internal.hpp"
+
+
+def test_the_host_units_are_the_units_that_are_no_kernel_units():
+    units = sorted(f for f in os.listdir(build.CSRC) if f.endswith(".hip"))
+    assert HOST_UNITS == [f for f in units if not f.startswith("k_")]
+    assert "mi_ilqr.hip" in HOST_UNITS and all(f == "mi_ilqr.hip" or f.startswith("h_") for f in HOST_UNITS), HOST_UNITS
+    assert len(HOST_UNITS) >= 2
+
+
+@pytest.mark.parametrize("unit", HOST_UNITS)
+def test_no_host_unit_includes_a_family_header_or_kernel_templates(unit):
+    inc = set(includes(unit))
+    assert INTERNAL in inc or "host.hpp" in inc, sorted(inc)
+    assert not (inc & FAMILY) and not any(i.startswith("launch_") for i in inc), sorted(inc)
+
+
 def test_the_abi_unit_includes_the_interface_and_no_kernel_templates():
     inc = set(includes("mi_ilqr.hip"))
-    assert {"host.hpp", "kernel_args.hpp", "lds_layout.hpp", "models.hpp"} <= inc
+    assert {"host.hpp", INTERNAL, "kernel_args.hpp", "lds_layout.hpp", "models.hpp"} <= inc
     assert not (inc & FAMILY) and not any(i.startswith("launch_") for i in inc), sorted(inc)
+
+
+def test_the_internal_header_is_the_host_units_own():
+    """host_internal.hpp: included by host units only - no kernel unit, no header, not the plugin template - and it includes host.hpp
+    and no family header or launch templates."""
+    inc = set(includes(INTERNAL))
+    assert "host.hpp" in inc and not (inc & FAMILY) and not any(i.startswith("launch_") for i in inc), sorted(inc)
+    for name in sorted(os.listdir(build.CSRC)):
+        if (name.endswith(".hip") or name.endswith(".hpp")) and name not in HOST_UNITS:
+            assert INTERNAL not in includes(name), name
+    from drake_ddp_amd import plugin
+    for family in ("small", "large"):
+        assert INTERNAL not in plugin.source("t", 2, 1, "xn[0] = x[0]; xn[1] = x[1] + dt * u[0];", [], family)
+
+
+def test_the_communicator_alone_includes_rccl_and_dlfcn():
+    for name in sorted(f for f in os.listdir(build.CSRC) if f.endswith(".hip") or f.endswith(".hpp")):
+        with open(os.path.join(build.CSRC, name)) as f:
+            system = set(re.findall(r"^\s*#\s*include\s+<([^>]+)>", f.read(), re.M))
+        assert not (system & {"rccl/rccl.h", "dlfcn.h"}) or name == "h_comm.hip", name
 
 
 def test_each_launch_header_serves_one_family():

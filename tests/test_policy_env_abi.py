@@ -61,8 +61,11 @@ def test_the_kernel_header_keeps_the_layering():
         with open(path) as f:
             return re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)
     assert includes(os.path.join(CSRC, "policy_env.hpp")) == ["host.hpp"]
+    from drake_ddp_amd import build
+    host_units = {os.path.basename(s) for s in build.host_sources()}
+    assert {"mi_ilqr.hip", "h_policy.hip"} <= host_units
     for name in os.listdir(CSRC):
-        if name.endswith(".hpp") or name == "mi_ilqr.hip":
+        if name.endswith(".hpp") or name in host_units:
             assert "policy_env.hpp" not in includes(os.path.join(CSRC, name)), name
     assert includes(os.path.join(CSRC, "k_policy_env.hip")) == ["policy_env.hpp"]
     with open(os.path.join(CSRC, "host.hpp")) as f:

@@ -64,8 +64,11 @@ def test_the_kernel_header_keeps_the_layering():
         with open(path) as f:
             return re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)
     assert "policy_rollout.hpp" in includes(os.path.join(CSRC, "policy_mc.hpp")) and "wave_ops.hpp" in includes(os.path.join(CSRC, "policy_mc.hpp"))
+    from drake_ddp_amd import build
+    host_units = {os.path.basename(s) for s in build.host_sources()}
+    assert {"mi_ilqr.hip", "h_policy.hip"} <= host_units
     for name in os.listdir(CSRC):
-        if name.endswith(".hpp") or name == "mi_ilqr.hip":
+        if name.endswith(".hpp") or name in host_units:
             assert "policy_mc.hpp" not in includes(os.path.join(CSRC, name)), name
     assert includes(os.path.join(CSRC, "k_policy_mc.hip")) == ["policy_mc.hpp"] == includes(os.path.join(CSRC, "k_policy_mc_noise.hip"))
     from drake_ddp_amd import plugin

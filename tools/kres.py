@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Print per-kernel register/scratch/LDS usage (hipcc -Rpass-analysis=kernel-resource-usage)."""
 import re, subprocess, sys
-src = sys.argv[1] if len(sys.argv) > 1 else "drake_ddp_amd/csrc/mi_ilqr.hip"
+src = sys.argv[1] if len(sys.argv) > 1 else "drake_ddp_amd/csrc/h_memory.hip"
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-fast-math",
                       "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/tmp/_kres.o"],
