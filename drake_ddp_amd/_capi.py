@@ -48,6 +48,10 @@ MC_FIELDS = 10
 F_POLICY_MC_BOX, F_POLICY_MC_OBSERVE, F_POLICY_MC_ENVELOPE, F_POLICY_MC_ENVELOPE_U, F_POLICY_MC_SAFETY = 33, 34, 35, 36, 37
 MC_OBSERVE_X, MC_OBSERVE_U = 1, 2
 MC_ENV_FIELDS = 8
+# multi-start (mi_ilqr.h: "Multi-start"): (B, m) sigma_u rows | write-only command (6,) K | op | seed | round | hold | 0 | read-only (G, 3)
+# winner | cost | eligible | read-only (G, n, N), (G, m, N-1), (G,) the winners' rows of the last gather | read-only (1,) ms of the kernel
+F_SEEDS_SIGMA, F_SEEDS_RUN, F_SEEDS_BEST, F_SEEDS_X_BAR, F_SEEDS_U_BAR, F_SEEDS_COST, F_SEEDS_KERNEL_MS = 38, 39, 40, 41, 42, 43, 44
+SEEDS_PERTURB, SEEDS_SELECT, SEEDS_RESEED, SEEDS_GATHER = 0, 1, 2, 3
 I_ITERS, I_STATUS, I_LS_TRIALS, I_KP_COUNT, I_KP_LIST = 100, 101, 102, 103, 104
 I_POLICY_MC_PASSES = 105    # (1,) passes over windows of sample groups of the last on-device Monte-Carlo run
 I64_STAGE_CYCLES = 200

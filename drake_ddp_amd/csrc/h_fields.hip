@@ -1,6 +1,6 @@
 // libmi_ilqr.so, host side - the fields: the table of the selectors that are plain device arrays, the setters that only validate and
 // upload, and the boundary's generic entry points mi_ilqr_set / _get / _get_async / _get_int / _device_ptr, which send every other
-// selector to the unit that owns it.
+// selector to the unit that owns it (the policy's: h_policy.hip, the plant's: h_mpc.hip, multi-start: h_seeds.hip).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -197,6 +197,7 @@ extern "C" {
 int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
   if (const int rc = get_plant_field(h, which, dst, bytes); rc != kNotPlantField) return rc;
+  if (const int rc = get_seeds_field(h, which, dst, bytes); rc != kNotSeedsField) return rc;      // (the last command's results, host copies)
   if (const RowField r = row_field(h, which); r.store) return store_read(h, *r.store, r.shared_row, dst, bytes);   // (host mirrors)
   if (which == MI_F_POLICY_STREAM) {
     if (bytes != 3 * 8) return MI_ILQR_E_BAD_SHAPE;
@@ -311,6 +312,10 @@ int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
     case MI_F_POLICY_MC_BOX: return set_mc_box(h, src, bytes);
     case MI_F_POLICY_MC_OBSERVE: return set_mc_observe(h, src, bytes);
     case MI_F_POLICY_MC_ENVELOPE: case MI_F_POLICY_MC_ENVELOPE_U: case MI_F_POLICY_MC_SAFETY: return MI_ILQR_E_BAD_ARG;   // (read-only)
+    case MI_F_SEEDS_SIGMA: return set_seeds_sigma(h, src, bytes);
+    case MI_F_SEEDS_RUN: return run_seeds(h, src, bytes);                    // (a command: perturb / select / reseed / gather)
+    case MI_F_SEEDS_BEST: case MI_F_SEEDS_X_BAR: case MI_F_SEEDS_U_BAR: case MI_F_SEEDS_COST: case MI_F_SEEDS_KERNEL_MS:
+      return MI_ILQR_E_BAD_ARG;                                              // (read-only)
     case MI_F_PLANT_STATE: return set_plant_state(h, src, bytes);
     case MI_F_PLANT_PARAMS: return set_param_rows(h, h->plant_params, src, bytes);
     case MI_F_PLANT_NOISE: return set_noise_rows(h, h->plant_noise, src, bytes);

@@ -271,6 +271,7 @@ RowField row_field(mi_ilqr* h, int which) {
     case MI_F_PLANT_NOISE: return {&h->plant_noise, nullptr};
     case MI_F_POLICY_MC_DIST: return {&h->policy_mc_dist, nullptr};    // (not set: zeros)
     case MI_F_POLICY_MC_BOX: return {&h->mc_box, nullptr};             // (the same)
+    case MI_F_SEEDS_SIGMA: return {&h->seeds_sigma, nullptr};          // (the same)
   }
   return {nullptr, nullptr};
 }

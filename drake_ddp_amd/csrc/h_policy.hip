@@ -42,11 +42,11 @@ __global__ void __launch_bounds__(256) policy_pack_kernel(const double* __restri
 
 namespace mi_host {
 
-namespace {
-
 // The controls of the policy as the handle holds it now: a pending initial guess is the u_bar the next launch would start from, a
 // reset handle's u_bar reads as zeros (nullptr).
 const double* policy_u_source(const mi_ilqr* h) { return h->u_pending ? h->u_guess : (h->u_zero ? nullptr : h->u_bar); }
+
+namespace {
 
 // What the two policy calls refuse alike.  `draws`: the samples the call takes from the handle's stream (a noise-free rollout: none).
 int policy_call_refused(const mi_ilqr* h, unsigned long long draws) {

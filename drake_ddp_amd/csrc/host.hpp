@@ -173,6 +173,17 @@ struct mi_ilqr {
   int plant_log_rows = 0;          // ... and the rows that run wrote (0: no such run yet)
   hipEvent_t plant_ev0 = nullptr, plant_ev1 = nullptr;   // the plant kernel's own event pair (MI_F_PLANT_KERNEL_MS)
   double plant_ms = 0.0;           // summed over the plant kernels of the last closed-loop run
+  // multi-start (MI_F_SEEDS_*; seeds.hpp, h_seeds.hip): the handle read as groups of K consecutive problems.  seeds_sigma: (B, m)
+  // sigma_u rows of the perturbation, problem data like the noise rows (not synced: zeros).  seeds_best_dev: the (G, 3) rows
+  // winner | cost | eligible on the device, room for G = B; seeds_best / seeds_x / seeds_u / seeds_cost: what the last select and
+  // the last gather left, on the host - what the read-only selectors return (empty: no such command yet).  seeds_ev0 / seeds_ev1:
+  // the command's own event pair (MI_F_SEEDS_KERNEL_MS), seeds_ran: they hold a launch.
+  RowStore seeds_sigma;
+  double* seeds_best_dev = nullptr;
+  std::vector<double> seeds_best, seeds_x, seeds_u, seeds_cost;
+  hipEvent_t seeds_ev0 = nullptr, seeds_ev1 = nullptr;
+  bool seeds_ran = false;
+  double seeds_ms = 0.0;
 };
 
 // Run-time switches for A/B runs (README): the environment is read once per process.
@@ -361,6 +372,26 @@ template <class M> MI_INTERNAL int launch_policy_mc_noise(mi_ilqr* h, const Poli
 MI_INTERNAL int launch_policy_env(mi_ilqr* h, const double* buf, double* acc, size_t B, size_t R, size_t win, double first_global, int first);
 MI_INTERNAL int launch_policy_box(mi_ilqr* h, const double* X, const double* box, const double* x_nom, size_t x_nom_stride,
                                   const double* goal, size_t goal_stride, unsigned long long* counters, size_t B, int n, int N, size_t win);
+
+// Arguments of seeds_kernel (seeds.hpp; k_seeds.hip), the multi-start command of MI_F_SEEDS_RUN: device pointers, one workgroup per
+// group of K consecutive problems.  Trajectory arrays are in the handle's kernel layout, `layout` 0 = [b][row][t], 1 = [b][t][row],
+// 2 = [t][row][b] (host_internal.hpp: LAYOUT_TL / TM / BM).
+enum { SEEDS_PERTURB = 0, SEEDS_SELECT = 1, SEEDS_RESEED = 2, SEEDS_GATHER = 3 };
+struct SeedsArgs {
+  const double* u_src;        // (B, m, N-1): the controls as the handle holds them now, or nullptr: zeros.  May BE u_dst (a pending guess)
+  double* u_dst;              // (B, m, N-1): the initial guess the next solve starts from (perturb, reseed)
+  const double* sigma;        // (B, m) sigma_u rows, or nullptr: zeros
+  const double* cost;         // (B,) and
+  const int32_t* status;      // (B,) of the last solve (select, reseed, gather)
+  double* best;               // (G, 3) rows winner | cost | eligible, written by select, reseed and gather
+  const double* x_bar;        // (B, n, N), or nullptr: zeros (gather)
+  double *gx, *gu, *gc;       // (G, n, N) and (G, m, N-1), time last, and (G,): the winners' rows (gather)
+  unsigned long long seed;    // the Philox key
+  uint32_t round;             // counter word 0
+  int32_t B, K, n, m, m_user, N, layout, op, hold;   // m_user: controls m_user .. m-1 are padding and get no noise
+  hipEvent_t ev0, ev1;        // the kernel's start / stop events
+};
+MI_INTERNAL int launch_seeds(mi_ilqr* h, const SeedsArgs& a);
 
 // Arguments of plant_advance_kernel<M> (plant_advance.hpp), all device pointers.  "Problem-minor": element e of problem b at e * B + b.
 struct PlantArgs {

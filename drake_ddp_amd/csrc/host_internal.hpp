@@ -2,8 +2,8 @@
 // in the unit named above each group, all of it hidden from the dynamic symbol table.  Host units only: no k_*.hip unit, no
 // launch_*.hpp, no family header and not the plugin template includes this header, and it includes no family header.
 // The calls go one way: h_memory.hip calls nothing of the others; mi_ilqr.hip (the core) calls h_memory.hip, and of h_fields.hip the
-// field table alone; h_policy.hip and h_mpc.hip call the core and h_memory.hip (the plant its policy's pack); h_fields.hip, the
-// boundary's selectors, calls all of them.  h_comm.hip stands alone.
+// field table alone; h_policy.hip, h_mpc.hip and h_seeds.hip call the core and h_memory.hip (the plant its policy's pack, the seeds
+// its rule for the controls a launch starts from); h_fields.hip, the boundary's selectors, calls all of them.  h_comm.hip stands alone.
 #pragma once
 #include "host.hpp"
 #include "mc_window.hpp"
@@ -107,10 +107,17 @@ MI_INTERNAL bool prefix_ok(int which, size_t bytes, size_t field_bytes);
 // layout into dst, (B, steps, W) or (steps, W, B) - nothing of the handle is written
 enum { PACK_TIME_MAJOR = 0, PACK_PROBLEM_MINOR = 1 };
 MI_INTERNAL int pack_policy(mi_ilqr* h, double* dst, int steps, int order);
+MI_INTERNAL const double* policy_u_source(const mi_ilqr* h);      // the controls the next launch would start from; nullptr: zeros
 MI_INTERNAL int set_mc_dist(mi_ilqr* h, const double* src, size_t bytes);
 MI_INTERNAL int set_mc_box(mi_ilqr* h, const double* src, size_t bytes);
 MI_INTERNAL int set_mc_observe(mi_ilqr* h, const double* src, size_t bytes);
 MI_INTERNAL int run_policy_mc(mi_ilqr* h, const double* v, size_t bytes);
+
+// ---- h_seeds.hip: multi-start (MI_F_SEEDS_*) - the sigma rows, the command and what the read-only selectors return
+MI_INTERNAL int set_seeds_sigma(mi_ilqr* h, const double* src, size_t bytes);
+MI_INTERNAL int run_seeds(mi_ilqr* h, const double* v, size_t bytes);
+constexpr int kNotSeedsField = 1;
+MI_INTERNAL int get_seeds_field(mi_ilqr* h, int which, double* dst, size_t bytes);
 
 // ---- h_mpc.hip: mi_ilqr_get of the plant's and the reference's selectors; kNotPlantField for every other one
 constexpr int kNotPlantField = 1;

@@ -1,7 +1,7 @@
 // libmi_ilqr.so - host side of the C ABI declared in include/mi_ilqr.h, the core: the model table, the handle's creation, the
 // launch of the solver kernels (make_args, launch) with the solve, collect and stage entry points, the cost, initial-guess and
 // control-limit entry points, timing.  The other concerns of the host have units of their own (h_memory.hip, h_fields.hip,
-// h_policy.hip, h_mpc.hip, h_comm.hip; host_internal.hpp declares what they share).
+// h_policy.hip, h_mpc.hip, h_seeds.hip, h_comm.hip; host_internal.hpp declares what they share).
 //
 // The library owns the device-resident solver state of a batch (the persistent attributes of the reference class, ilqr.py:61-91,
 // with a leading batch axis), dispatches the gfx950 kernels and moves data across the boundary.  No compute happens on the host:
@@ -744,6 +744,7 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
   h->policy_noise.width = h->plant_noise.width = h->n + h->m;
   h->policy_mc_dist.width = 3 * (size_t)h->n + 2 * (size_t)model.n_params;
   h->mc_box.width = 2 * (size_t)h->n;
+  h->seeds_sigma.width = h->m;
   h->plant_state.width = h->n;
   h->plant_params.width = model.n_params;
   h->params.batch_minor_copy = h->costs.batch_minor_copy = batch_minor;   // (what the lane kernels read batch-minor: KArgs::param_cols, cost_cols)
@@ -769,6 +770,8 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
   if (h->policy_ev0) (void)hipEventDestroy(h->policy_ev0);
   if (h->policy_ev1) (void)hipEventDestroy(h->policy_ev1);
   for (hipEvent_t e : h->mc_events) (void)hipEventDestroy(e);
+  if (h->seeds_ev0) (void)hipEventDestroy(h->seeds_ev0);
+  if (h->seeds_ev1) (void)hipEventDestroy(h->seeds_ev1);
   if (h->plant_ev0) (void)hipEventDestroy(h->plant_ev0);
   if (h->plant_ev1) (void)hipEventDestroy(h->plant_ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);

@@ -303,6 +303,67 @@ def check_mc_observe(envelope, controls, safe_box, B, n):
     return bits, box
 
 
+def check_seed_args(K, B, m, sigma_u=None, seed=0, round=0, hold=1, m_dev=None, what="PerturbInitialGuess"):   # noqa: A002
+    """The multi-start arguments -> (K, rows, seed, round, hold): K the group size as an int, rows None for sigma_u=None (SelectBest,
+    GatherBest) or the contiguous (B, m_dev) float64 sigma_u rows with zeros on the padding controls (m_dev: the device's number of
+    controls, default m); sigma_u: scalar, (m,) or (B, m).  ValueError - decided here, before anything reaches the library - for a K
+    that is no integer >= 1 or does not divide B, a hold that is no integer in [1, 2^31), a seed that is no integer in [0, 2^53), a
+    round that is no integer in [0, 2^32), any other shape of sigma_u and a negative, NaN or infinite entry in it."""
+    m_dev = m if m_dev is None else int(m_dev)
+
+    def integer(v, name, lo, end, rng):
+        ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer, float, np.floating))
+        if ok and isinstance(v, (float, np.floating)):
+            ok = bool(np.isfinite(v) and v == np.floor(v))
+        if not ok or not lo <= int(v) < end:
+            raise ValueError(f"{what}: {name} must be an integer in {rng}; got {v!r}")
+        return int(v)
+
+    K = integer(K, "K", 1, 1 << 31, "[1, 2^31)")
+    if B % K != 0:
+        raise ValueError(f"{what}: K must divide the batch: {B} problems are no whole number of groups of {K}")
+    seed = integer(seed, "seed", 0, 1 << 53, "[0, 2^53)")
+    round = integer(round, "round", 0, 1 << 32, "[0, 2^32)")   # noqa: A001
+    hold = integer(hold, "hold", 1, 1 << 31, "[1, 2^31)")
+    if sigma_u is None:
+        return K, None, seed, round, hold
+    try:
+        a = np.asarray(sigma_u, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{what}: sigma_u is not an array of numbers ({e})") from None
+    if a.shape not in ((), (m,), (B, m)):
+        raise ValueError(f"{what}: sigma_u must be a scalar, ({m},) or ({B}, {m}); got {a.shape}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what}: NaN or infinity in sigma_u")
+    if (a < 0.0).any():
+        raise ValueError(f"{what}: negative entry in sigma_u (standard deviations)")
+    rows = np.zeros((B, m_dev))
+    rows[:, :m] = a
+    return K, rows, seed, round, hold
+
+
+class SeedSelection:
+    """What SelectBest found in every group of K seeds (include/mi_ilqr.h: "Multi-start"), (G,) arrays: winner - the member index of
+    the eligible member of least cost, -1 when no member is eligible -, its cost (+inf then) and the number of eligible members."""
+    __slots__ = ("K", "winner", "cost", "eligible")
+
+    def __init__(self, K, winner, cost, eligible):
+        self.K, self.winner, self.cost, self.eligible = K, winner, cost, eligible
+
+    @classmethod
+    def from_rows(cls, K, rows):
+        return cls(int(K), rows[:, 0].astype(np.int64), np.ascontiguousarray(rows[:, 1]), rows[:, 2].astype(np.int64))
+
+    @property
+    def problem(self):
+        """(G,) the winners as problem numbers g K + winner; -1 for a group without a winner."""
+        g = np.arange(self.winner.size) * self.K
+        return np.where(self.winner >= 0, g + self.winner, -1)
+
+    def __repr__(self):
+        return f"SeedSelection(K={self.K}, winner={self.winner.tolist()}, eligible={self.eligible.tolist()})"
+
+
 def _chan(nA, meanA, m2A, nB, meanB, m2B):
     """include/mi_ilqr.h's merge of (count, mean, M2), A the operand of the lower sample numbers; a count-0 side leaves the other's."""
     fA, fB = nA.astype(np.float64), nB.astype(np.float64)
@@ -1257,6 +1318,92 @@ class BatchedIterativeLQR:
         """Milliseconds of the rollout kernel of the last RolloutPolicy call (HIP events of its own)."""
         out = np.empty(1)
         _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_KERNEL_MS, _capi.ptr(out), 8), "mi_ilqr_get")
+        return float(out[0])
+
+    # ------------------------------------------------------------- multi-start (include/mi_ilqr.h: "Multi-start")
+    def _seeds_run(self, op, K, rows=None, seed=0, round=0, hold=1):   # noqa: A002
+        if rows is not None:
+            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_SIGMA, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
+        v = np.array([K, op, seed, round, hold, 0], dtype=np.float64)
+        rc = self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_RUN, _capi.ptr(v), v.nbytes)
+        if rc == _capi.E_UNSUPPORTED:
+            raise ValueError("multi-start: a solver of at most 4 problems on the wave-per-problem kernels keeps its inputs in host "
+                             "memory and has no seed groups to join; use a larger batch")
+        _capi.check(rc, "mi_ilqr_set")
+
+    def _seeds_best(self, K):
+        rows = np.empty((self.B // K, 3))
+        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_SEEDS_BEST, _capi.ptr(rows), rows.nbytes), "mi_ilqr_get")
+        return SeedSelection.from_rows(K, rows)
+
+    def PerturbInitialGuess(self, K, sigma_u, seed=0, round=0, hold=1):   # noqa: A002
+        """Read the batch as B / K groups of K consecutive problems - the same problem under K guesses - and draw the guesses on
+        the device: every member k >= 1 of every group gets base + sigma_u o z, member 0 keeps base (the elite slot: best-of-K is
+        never worse than the single start).  base is what the next Solve would have started from: the guess given to
+        SetInitialGuess, else the controls the solver holds, else zeros.  z: standard normals of (seed, round, problem, step div
+        hold, control) alone; hold > 1 keeps a disturbance over `hold` steps.  sigma_u: scalar, (m,) or (B, m).  The next Solve
+        starts cold from these guesses.  Nothing of the size of the guesses crosses the bus."""
+        K, rows, seed, round, hold = check_seed_args(K, self.B, self.m, sigma_u, seed, round, hold, self._md)   # noqa: A001
+        if rows is None:
+            raise ValueError("PerturbInitialGuess: sigma_u is required")
+        self._push_problem()                                   # (a guess given to SetInitialGuess is the base)
+        self._seeds_run(_capi.SEEDS_PERTURB, K, rows, seed, round, hold)
+
+    def SelectBest(self, K):
+        """The best member of every group of K: the eligible one (converged or stopped at max_iters, finite cost) of least cost,
+        ties to the lowest index -> SeedSelection.  Reads the last solve's cost and status on the device; changes nothing."""
+        K = check_seed_args(K, self.B, self.m, what="SelectBest")[0]
+        self._seeds_run(_capi.SEEDS_SELECT, K)
+        return self._seeds_best(K)
+
+    def ReseedFromBest(self, K, sigma_u, seed=0, round=0, hold=1):   # noqa: A002
+        """SelectBest, then new guesses around the winners: the winner's slot gets its own controls unperturbed, every other member
+        of its group the winner's controls + sigma_u o z (PerturbInitialGuess' noise at this `round`).  A group without a winner
+        is perturbed around each member's own controls (non-finite entries read as 0).  -> the SeedSelection it used.  The next
+        Solve starts cold from these guesses."""
+        K, rows, seed, round, hold = check_seed_args(K, self.B, self.m, sigma_u, seed, round, hold, self._md, "ReseedFromBest")   # noqa: A001
+        if rows is None:
+            raise ValueError("ReseedFromBest: sigma_u is required")
+        self._seeds_run(_capi.SEEDS_RESEED, K, rows, seed, round, hold)
+        return self._seeds_best(K)
+
+    def GatherBest(self, K):
+        """SelectBest, then the winners' results -> (x_bar (G, n, N), u_bar (G, m, N-1), cost (G,), SeedSelection); a group without a
+        winner: NaN rows and cost +inf.  Only these G rows cross the bus; changes nothing."""
+        K = check_seed_args(K, self.B, self.m, what="GatherBest")[0]
+        self._seeds_run(_capi.SEEDS_GATHER, K)
+        G = self.B // K
+        x, u, c = np.empty((G, self.n, self.N)), np.empty((G, self._md, self.N - 1)), np.empty(G)
+        for which, out in ((_capi.F_SEEDS_X_BAR, x), (_capi.F_SEEDS_U_BAR, u), (_capi.F_SEEDS_COST, c)):
+            _capi.check(self._lib.mi_ilqr_get(self._h, which, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+        return x, np.ascontiguousarray(u[:, :self.m, :]), c, self._seeds_best(K)
+
+    def SolveMultiStart(self, K, rounds, sigma_u, seed=0, hold=1, shrink=1.0):
+        """Multi-start on the device: PerturbInitialGuess -> Solve -> (ReseedFromBest with sigma_u shrink^r at round r -> Solve)
+        x (rounds - 1) -> GatherBest.  -> (x_bar (G, n, N), u_bar (G, m, N-1), cost (G,), selections): the winners of the last
+        round and the SeedSelection of every round, the last one the gather's."""
+        if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, (int, np.integer)) or rounds < 1:
+            raise ValueError(f"SolveMultiStart: rounds must be an integer >= 1; got {rounds!r}")
+        if not (isinstance(shrink, (int, float, np.integer, np.floating)) and np.isfinite(shrink) and shrink >= 0.0):
+            raise ValueError(f"SolveMultiStart: shrink must be a finite number >= 0; got {shrink!r}")
+        sigma = check_seed_args(K, self.B, self.m, sigma_u, seed, 0, hold, self._md, "SolveMultiStart")[1]
+        if sigma is None:
+            raise ValueError("SolveMultiStart: sigma_u is required")
+        sigma = sigma[:, :self.m]
+        selections = []
+        self.PerturbInitialGuess(K, sigma, seed, 0, hold)
+        self.Solve()
+        for r in range(1, int(rounds)):
+            selections.append(self.ReseedFromBest(K, sigma * float(shrink) ** r, seed, r, hold))
+            self.Solve()
+        x, u, c, sel = self.GatherBest(K)
+        selections.append(sel)
+        return x, u, c, selections
+
+    def seeds_kernel_ms(self):
+        """Milliseconds of the kernel of the last multi-start command (HIP events of its own)."""
+        out = np.empty(1)
+        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_SEEDS_KERNEL_MS, _capi.ptr(out), 8), "mi_ilqr_get")
         return float(out[0])
 
     # ------------------------------------------------------------- multi-GPU helper

@@ -144,6 +144,13 @@ enum {
   MI_F_POLICY_MC_ENVELOPE = 35,/* (B,N,n,8) read-only: count | K | s1 | s2 | min | max | argmin | argmax of every state row of the last run */
   MI_F_POLICY_MC_ENVELOPE_U = 36,/* (B,N-1,m,8) read-only: the same of every control row, m the device's control dimension */
   MI_F_POLICY_MC_SAFETY = 37,/* (B,3+N) read-only: ran | safe | safe_success | exits[0 .. N-1] of the last run, integers held in doubles */
+  MI_F_SEEDS_SIGMA = 38,     /* (B,m) sigma_u rows of the multi-start perturbation, m the device's control dimension ("Multi-start" below) */
+  MI_F_SEEDS_RUN = 39,       /* (6,) write-only COMMAND: K | op | seed | round | hold | reserved = 0 - mi_ilqr_set RUNS perturb / select / reseed / gather */
+  MI_F_SEEDS_BEST = 40,      /* (G,3) read-only: winner | cost | eligible of every group of the last select, integers held in doubles */
+  MI_F_SEEDS_X_BAR = 41,     /* (G,n,N) read-only: the winners' x_bar of the last gather */
+  MI_F_SEEDS_U_BAR = 42,     /* (G,m,N-1) read-only: the winners' u_bar of the last gather, m the device's control dimension */
+  MI_F_SEEDS_COST = 43,      /* (G,) read-only: the winners' cost of the last gather */
+  MI_F_SEEDS_KERNEL_MS = 44, /* (1,) read-only: milliseconds of the kernel of the last MI_F_SEEDS_RUN, from its own HIP events */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
@@ -713,6 +720,43 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
  * The trajectories of a window of samples stay in the handle's grow-only scratch (about 1 GiB per pass at most, never less than one
  * group of 64 samples per problem); when that memory cannot be had the run is refused with MI_ILQR_E_UNSUPPORTED and the last results
  * stay in place. */
+
+/* ---- Multi-start (ABI 10; selectors of mi_ilqr_set / mi_ilqr_get, no new entry point) ----
+ * iLQR is a local method: the answer depends on the initial guess.  A handle of B problems is read as G = B / K SEED GROUPS of K
+ * consecutive problems: group g holds problems g K .. g K + K - 1, meant to be the same problem (x0, target, costs, parameters - not
+ * checked) under K different guesses.  Four operations work on the handle's resident state, one kernel each (one workgroup per
+ * group); nothing of size B m (N-1) crosses the bus.
+ * PERTURB (op 0).  u_guess[b,j,t] = base[b,j,t] + sigma_u[b,j] z(seed, round, b, t div hold, j) for every member k >= 1 of every
+ * group; member 0, the ELITE slot, gets base unchanged, so best-of-K is never worse than the single start.  base is what the next
+ * solve would have started from: the pending guess, else u_bar, else zeros (a fresh or reset handle).  z is a standard normal:
+ * Philox4x32-10 under the key (seed mod 2^32, seed div 2^32) at counter = (round, t div hold, b, 768 + j / 4), Box-Muller normal
+ * j mod 4 of the block (words (0, 1) -> normals 0, 1; words (2, 3) -> normals 2, 3, as under "Process and actuation noise").  A normal
+ * depends on (seed, round, b, t div hold, j) and nothing else: not on K, not on the launch, not on the layout.  hold >= 1 keeps the
+ * disturbance constant over `hold` steps.  sigma z is a rounded product, the sum a rounded sum (no FMA); where sigma = 0, and on
+ * padding controls, the element is base bit for bit.  The result is not clamped on a handle with control limits: the rollouts clamp.
+ * Afterwards the handle is where mi_ilqr_reset followed by mi_ilqr_set_initial(u_guess) would leave it: cold, the guess pending.
+ * SELECT (op 1).  A member is ELIGIBLE iff its status with MI_STATUS_FLAG_INDEFINITE masked off is MI_STATUS_CONVERGED or
+ * MI_STATUS_MAX_ITERS and its cost is finite.  The winner is the eligible member of least cost, ties go to the lowest index.  Per
+ * group three doubles: winner (the member index k) | its cost | the number of eligible members; no eligible member: -1 | +inf | 0.
+ * RESEED (op 2).  Select, then rebuild the guesses: the winner's slot gets its own u_bar unperturbed, every other member the winner's
+ * u_bar plus the noise of PERTURB at this round.  A group without a winner falls back to PERTURB with each member's own u_bar as
+ * base, non-finite entries read as 0.  The handle ends as after PERTURB.
+ * GATHER (op 3).  Select, then the winners' x_bar (G,n,N), u_bar (G,m,N-1) and cost (G,); a group without a winner: NaN rows, +inf.
+ * SELECT and GATHER change nothing in the solver's state: a solve after them is bitwise the solve without them.
+ *   mi_ilqr_set(MI_F_SEEDS_SIGMA, rows, B*m*8)   row b = sigma_u of problem b, m the device's control dimension: finite, non-negative,
+ *                                            zero on padding controls - else MI_ILQR_E_BAD_ARG; wrong `bytes`: MI_ILQR_E_BAD_SHAPE.
+ *                                            (NULL, 0) clears the rows (zeros).  Survives mi_ilqr_reset; mi_ilqr_get reads them back.
+ *   mi_ilqr_set(MI_F_SEEDS_RUN, v, 48)       v = K | op | seed | round | hold | reserved = 0, integers held in doubles: RUNS the
+ *                                            operation on the handle's stream and synchronizes once.  Refusals: K < 1, K not dividing
+ *                                            B, an unknown op, hold < 1, a seed outside [0, 2^53), a round outside [0, 2^32), a value
+ *                                            that is no such integer, reserved != 0: MI_ILQR_E_BAD_ARG; a handle whose inputs live in
+ *                                            host memory (B <= 4 on the wave-per-problem kernels): MI_ILQR_E_UNSUPPORTED; wrong `bytes`:
+ *                                            MI_ILQR_E_BAD_SHAPE.  A refused command changes nothing.  Write-only.
+ *   mi_ilqr_get(MI_F_SEEDS_BEST, dst, G*3*8) the rows of the last SELECT, RESEED or GATHER; before any: MI_ILQR_E_BAD_ARG.
+ *   mi_ilqr_get(MI_F_SEEDS_X_BAR, dst, G*n*N*8), (MI_F_SEEDS_U_BAR, dst, G*m*(N-1)*8), (MI_F_SEEDS_COST, dst, G*8)   the winners'
+ *                                            rows, when the last command that selected was a GATHER - else MI_ILQR_E_BAD_ARG.
+ *   mi_ilqr_get(MI_F_SEEDS_KERNEL_MS, &ms, 8)   the kernel of the last command, from its own HIP events; before any: MI_ILQR_E_BAD_ARG.
+ *                                            Setting one of the five read-only selectors: MI_ILQR_E_BAD_ARG. */
 
 #ifdef __cplusplus
 }
