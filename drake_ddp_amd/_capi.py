@@ -52,6 +52,9 @@ MC_ENV_FIELDS = 8
 # winner | cost | eligible | read-only (G, n, N), (G, m, N-1), (G,) the winners' rows of the last gather | read-only (1,) ms of the kernel
 F_SEEDS_SIGMA, F_SEEDS_RUN, F_SEEDS_BEST, F_SEEDS_X_BAR, F_SEEDS_U_BAR, F_SEEDS_COST, F_SEEDS_KERNEL_MS = 38, 39, 40, 41, 42, 43, 44
 SEEDS_PERTURB, SEEDS_SELECT, SEEDS_RESEED, SEEDS_GATHER = 0, 1, 2, 3
+# the long form of the command ("Multi-start in the receding-horizon loop"): (8,) K | SEEDS_RESEED | seed | round | hold | 0 |
+# num_resolves | replan_steps; F_SEEDS_BEST then holds (num_resolves + 1, G, 3)
+SEEDS_RUN_DOUBLES, SEEDS_MPC_RUN_DOUBLES = 6, 8
 I_ITERS, I_STATUS, I_LS_TRIALS, I_KP_COUNT, I_KP_LIST = 100, 101, 102, 103, 104
 I_POLICY_MC_PASSES = 105    # (1,) passes over windows of sample groups of the last on-device Monte-Carlo run
 I64_STAGE_CYCLES = 200

@@ -21,9 +21,12 @@ namespace {     // the kernel: global, like every kernel of the host units - a n
 // problem) - the writes are coalesced either way.
 __global__ void __launch_bounds__(256) policy_pack_kernel(const double* __restrict__ x_bar, const double* __restrict__ u_bar,
                                                             const double* __restrict__ K, double* __restrict__ dst,
-                                                            int B, int n, int m, int N, int steps, int layout, int order) {
+                                                            int B, int n, int m, int N, int steps, int layout, int order,
+                                                            const double* __restrict__ sel, int group, int cols) {
+  // `cols` columns are written (B without groups).  Grouped (sel != nullptr: the (G, 3) selection rows on the device): column g is
+  // the policy of problem g `group` + w_g, the group's winner - member 0 where the group has none
   const int W = n + m + m * n, M1 = N - 1;
-  const size_t total = (size_t)B * steps * W;
+  const size_t total = (size_t)cols * steps * W;
   auto at = [&](const double* f, int rows, int len, int b, int r, int t) -> double {
     if (!f) return 0.0;
     if (layout == LAYOUT_TL) return f[((size_t)b * rows + r) * len + t];
@@ -32,8 +35,9 @@ __global__ void __launch_bounds__(256) policy_pack_kernel(const double* __restri
   };
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
     int b, w, t;
-    if (order == PACK_PROBLEM_MINOR) { b = (int)(e % B); const size_t tw = e / B; w = (int)(tw % W); t = (int)(tw / W); }
+    if (order == PACK_PROBLEM_MINOR) { b = (int)(e % cols); const size_t tw = e / cols; w = (int)(tw % W); t = (int)(tw / W); }
     else { w = (int)(e % W); const size_t bt = e / W; t = (int)(bt % steps); b = (int)(bt / steps); }
+    if (sel) { const double wg = sel[(size_t)b * 3]; b = b * group + (wg > 0.0 ? (int)wg : 0); }
     dst[e] = w < n ? at(x_bar, n, N, b, w, t) : (w < n + m ? at(u_bar, m, M1, b, w - n, t) : at(K, m * n, M1, b, w - n - m, t));
   }
 }
@@ -245,13 +249,15 @@ void mc_publish(mi_ilqr* h, McRun& r) {
 
 }  // namespace
 
-int pack_policy(mi_ilqr* h, double* dst, int steps, int order) {
+int pack_policy(mi_ilqr* h, double* dst, int steps, int order, const double* sel, int K) {
   if (steps < 1 || steps > h->N - 1) return MI_ILQR_E_BAD_ARG;      // (the controls and gains have N - 1 columns)
-  const size_t total = (size_t)h->B * steps * (size_t)(h->n + h->m + h->m * h->n);
+  if (sel && (K < 1 || h->B % K != 0)) return MI_ILQR_E_BAD_ARG;
+  const int cols = sel ? h->B / K : h->B;
+  const size_t total = (size_t)cols * steps * (size_t)(h->n + h->m + h->m * h->n);
   const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
   // a cold handle's x_bar and K read as zeros
   hipLaunchKernelGGL(policy_pack_kernel, dim3(blocks), dim3(256), 0, h->stream, h->cold ? nullptr : h->x_bar, policy_u_source(h),
-                     h->cold ? nullptr : h->K, dst, h->B, h->n, h->m, h->N, steps, layout_of(h), order);
+                     h->cold ? nullptr : h->K, dst, h->B, h->n, h->m, h->N, steps, layout_of(h), order, sel, K, cols);
   HIPCHK(hipGetLastError());
   return MI_ILQR_OK;
 }

@@ -1,7 +1,9 @@
 // libmi_ilqr.so, host side - multi-start (include/mi_ilqr.h, "Multi-start"; seeds.hpp): the sigma rows of the perturbation, the command
 // MI_F_SEEDS_RUN - perturb, select, reseed, select + gather on the handle's resident state, one launch of seeds_kernel each - and
 // the host copies the read-only selectors return.  Select and gather write nothing of the solver's state; perturb and reseed leave
-// the handle where mi_ilqr_reset followed by mi_ilqr_set_initial would: cold, with a pending guess.
+// the handle where mi_ilqr_reset followed by mi_ilqr_set_initial would: cold, with a pending guess.  The LONG form of the command
+// (8 doubles: multi-start in the receding-horizon loop) is validated here and run by h_mpc.hip's mpc_run_seeds; its selection log and
+// its kernels' time are kept here, behind the same selectors.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -15,12 +17,14 @@ namespace mi_host {
 
 namespace {
 
-// v = K | op | seed | round | hold | reserved, integers held in doubles (the comparisons are false for a NaN)
-struct SeedsRun { int32_t K = 0, op = 0, hold = 1; unsigned long long seed = 0; uint32_t round = 0; };
+// v = K | op | seed | round | hold | reserved [| num_resolves | replan_steps: the long form], integers held in doubles (the
+// comparisons are false for a NaN)
+struct SeedsRun { int32_t K = 0, op = 0, hold = 1, num_resolves = 0, replan_steps = 0; unsigned long long seed = 0; uint32_t round = 0; };
 
 int seeds_validate(const mi_ilqr* h, const double* v, size_t bytes, SeedsRun& r) {
   if (h->host_inputs) return MI_ILQR_E_UNSUPPORTED;              // (x0 and the guess live in host memory there: B <= 4, nothing to group)
-  if (bytes != 6 * 8) return MI_ILQR_E_BAD_SHAPE;
+  const bool long_form = bytes == 8 * 8;
+  if (bytes != 6 * 8 && !long_form) return MI_ILQR_E_BAD_SHAPE;
   if (!v) return MI_ILQR_E_BAD_ARG;
   auto whole = [](double x, double lo, double end) { return x >= lo && x < end && x == std::floor(x); };
   if (!whole(v[0], 1.0, 0x1p31) || !whole(v[1], 0.0, 4.0) || !whole(v[2], 0.0, 0x1p53) || !whole(v[3], 0.0, 0x1p32) ||
@@ -28,6 +32,10 @@ int seeds_validate(const mi_ilqr* h, const double* v, size_t bytes, SeedsRun& r)
     return MI_ILQR_E_BAD_ARG;
   r.K = (int32_t)v[0]; r.op = (int32_t)v[1]; r.seed = (unsigned long long)v[2]; r.round = (uint32_t)v[3]; r.hold = (int32_t)v[4];
   if (h->B % r.K != 0) return MI_ILQR_E_BAD_ARG;
+  if (long_form) {                                               // the receding-horizon loop: reseed is the one operation it joins with
+    if (r.op != SEEDS_RESEED || !whole(v[6], 1.0, 0x1p31) || !whole(v[7], 1.0, (double)(h->N - 1))) return MI_ILQR_E_BAD_ARG;
+    r.num_resolves = (int32_t)v[6]; r.replan_steps = (int32_t)v[7];
+  }
   return MI_ILQR_OK;
 }
 
@@ -60,6 +68,16 @@ int run_seeds(mi_ilqr* h, const double* v, size_t bytes) {
   SeedsRun r;
   int rc = seeds_validate(h, v, bytes, r);
   if (rc != MI_ILQR_OK) return rc;
+  if (r.num_resolves > 0) {                                      // the long form: the loop of h_mpc.hip, the results kept here
+    std::vector<double> log;
+    double ms = 0.0;
+    if ((rc = mpc_run_seeds(h, SeedsMpcRun{r.K, r.hold, r.num_resolves, r.replan_steps, r.seed, r.round}, log, ms)) != MI_ILQR_OK) return rc;
+    h->seeds_best.swap(log);
+    h->seeds_x.clear(); h->seeds_u.clear(); h->seeds_cost.clear();   // (the last command that selected was no gather)
+    h->seeds_ms = ms;
+    h->seeds_ran = true;
+    return MI_ILQR_OK;
+  }
   const size_t B = h->B, n = h->n, m = h->m, N = h->N, G = B / (size_t)r.K;
   HIPCHK(hipSetDevice(h->d.device_id));
   if (!h->seeds_best_dev && (rc = dev_alloc(h, h->seeds_best_dev, B * 3)) != MI_ILQR_OK) return rc;

@@ -177,9 +177,12 @@ struct mi_ilqr {
   // sigma_u rows of the perturbation, problem data like the noise rows (not synced: zeros).  seeds_best_dev: the (G, 3) rows
   // winner | cost | eligible on the device, room for G = B; seeds_best / seeds_x / seeds_u / seeds_cost: what the last select and
   // the last gather left, on the host - what the read-only selectors return (empty: no such command yet).  seeds_ev0 / seeds_ev1:
-  // the command's own event pair (MI_F_SEEDS_KERNEL_MS), seeds_ran: they hold a launch.
+  // the command's own event pair (MI_F_SEEDS_KERNEL_MS), seeds_ran: they hold a launch.  seeds_log_dev: the (R + 1, G, 3) selection
+  // log of the long form (multi-start in the receding-horizon loop), grow-only, seeds_log_cap doubles.
   RowStore seeds_sigma;
   double* seeds_best_dev = nullptr;
+  double* seeds_log_dev = nullptr;
+  size_t seeds_log_cap = 0;
   std::vector<double> seeds_best, seeds_x, seeds_u, seeds_cost;
   hipEvent_t seeds_ev0 = nullptr, seeds_ev1 = nullptr;
   bool seeds_ran = false;
@@ -392,6 +395,32 @@ struct SeedsArgs {
   hipEvent_t ev0, ev1;        // the kernel's start / stop events
 };
 MI_INTERNAL int launch_seeds(mi_ilqr* h, const SeedsArgs& a);
+
+// Arguments of seeds_mpc_join_kernel (seeds.hpp; k_seeds.hip), the join between two re-solves of the long form of MI_F_SEEDS_RUN:
+// select, then the shifted winner handed to every member of its group.  Source and destination never alias (the host materialises
+// a pending guess first).
+struct SeedsJoinArgs {
+  const double* u_bar;        // (B, m, N-1): the plans of the last solve
+  const double* x_bar;        // (B, n, N)
+  double* u_guess;            // (B, m, N-1): the initial guess of the next solve
+  double* x0;                 // (B, n): its initial states
+  const double* sigma;        // (B, m) sigma_u rows, or nullptr: zeros
+  const double* cost;         // (B,) and
+  const int32_t* status;      // (B,) of the last solve
+  double* best;               // (G, 3): this round's row of the selection log
+  double* mpc_dead;           // (B,): the MPC log's flags, cleared for the members of a group with a winner
+  // the closed loop, one plant per group (all nullptr without a plant): the groups' plants after this round's segment, compact -
+  // they become every member's x0 in the place of the prediction, and every member's row of the (B, ..) arrays the selectors read
+  const double* plant_x;      // (G, n) states
+  const double* plant_ended;  // (G,): 1.0 = the group's plant has ended; its members stop logging, winner or not
+  double* plant_rows;         // (B, n): MI_F_PLANT_STATE's rows
+  double* plant_dead;         // (B,): the plants' flags per problem
+  unsigned long long seed;
+  uint32_t round;
+  int32_t B, K, n, m, m_user, N, layout, hold, replan;
+  hipEvent_t ev0, ev1;
+};
+MI_INTERNAL int launch_seeds_mpc_join(mi_ilqr* h, const SeedsJoinArgs& a);
 
 // Arguments of plant_advance_kernel<M> (plant_advance.hpp), all device pointers.  "Problem-minor": element e of problem b at e * B + b.
 struct PlantArgs {

@@ -3,7 +3,8 @@
 // launch_*.hpp, no family header and not the plugin template includes this header, and it includes no family header.
 // The calls go one way: h_memory.hip calls nothing of the others; mi_ilqr.hip (the core) calls h_memory.hip, and of h_fields.hip the
 // field table alone; h_policy.hip, h_mpc.hip and h_seeds.hip call the core and h_memory.hip (the plant its policy's pack, the seeds
-// its rule for the controls a launch starts from); h_fields.hip, the boundary's selectors, calls all of them.  h_comm.hip stands alone.
+// its rule for the controls a launch starts from, and - the one call between two of them - h_seeds.hip hands the long form of its
+// command to the loop in h_mpc.hip); h_fields.hip, the boundary's selectors, calls all of them.  h_comm.hip stands alone.
 #pragma once
 #include "host.hpp"
 #include "mc_window.hpp"
@@ -106,7 +107,8 @@ MI_INTERNAL bool prefix_ok(int which, size_t bytes, size_t field_bytes);
 // pack_policy: the first `steps` rows t of x_bar_t | u_bar_t | K_t (W = n + m + m n doubles) gathered from the handle's kernel
 // layout into dst, (B, steps, W) or (steps, W, B) - nothing of the handle is written
 enum { PACK_TIME_MAJOR = 0, PACK_PROBLEM_MINOR = 1 };
-MI_INTERNAL int pack_policy(mi_ilqr* h, double* dst, int steps, int order);
+// sel != nullptr (the (G, 3) selection rows of multi-start, on the device): G = B / K columns, column g the policy of its group's winner
+MI_INTERNAL int pack_policy(mi_ilqr* h, double* dst, int steps, int order, const double* sel = nullptr, int K = 1);
 MI_INTERNAL const double* policy_u_source(const mi_ilqr* h);      // the controls the next launch would start from; nullptr: zeros
 MI_INTERNAL int set_mc_dist(mi_ilqr* h, const double* src, size_t bytes);
 MI_INTERNAL int set_mc_box(mi_ilqr* h, const double* src, size_t bytes);
@@ -122,5 +124,10 @@ MI_INTERNAL int get_seeds_field(mi_ilqr* h, int which, double* dst, size_t bytes
 // ---- h_mpc.hip: mi_ilqr_get of the plant's and the reference's selectors; kNotPlantField for every other one
 constexpr int kNotPlantField = 1;
 MI_INTERNAL int get_plant_field(mi_ilqr* h, int which, double* dst, size_t bytes);
+// ... and the receding-horizon loop with the seeds of a group joined between its re-solves: the long form of MI_F_SEEDS_RUN, which
+// h_seeds.hip validates and hands over (the loop belongs to the unit that owns the MPC log and the targets' clocks).  On success
+// `best` holds the (num_resolves + 1, G, 3) selection log and `join_ms` the join kernels' events, summed.
+struct SeedsMpcRun { int32_t K = 0, hold = 1, num_resolves = 0, replan_steps = 0; unsigned long long seed = 0; uint32_t round = 0; };
+MI_INTERNAL int mpc_run_seeds(mi_ilqr* h, const SeedsMpcRun& r, std::vector<double>& best, double& join_ms);
 
 }  // namespace mi_host

@@ -38,6 +38,7 @@ constexpr uint32_t kSeedsBlock = 768;      // the perturbation's first Philox bl
 
 #if defined(__HIPCC__)
 using mi_host::SeedsArgs;
+using mi_host::SeedsJoinArgs;
 using mi_host::SEEDS_PERTURB;
 using mi_host::SEEDS_SELECT;
 using mi_host::SEEDS_RESEED;
@@ -57,6 +58,45 @@ __device__ __forceinline__ size_t seeds_at(int layout, int B, int rows, int len,
   return ((size_t)t * rows + r) * B + b;
 }
 
+// SELECT of group b0 .. b0 + K - 1 by one workgroup of kSeedsThreads: every thread returns the winner (-1: none), its cost (+inf) and the
+// number of eligible members.  All threads call it (the DPP moves read every lane, and there is one barrier inside).
+__device__ __forceinline__ void seeds_select(const double* cost, const int32_t* status, int b0, int K, int tid, double* s_cost, int* s_idx,
+                                             int* s_cnt, int& winner, double& win_cost, int& eligible) {
+  double c = INFINITY;
+  int i = 0x7fffffff, cnt = 0;
+  for (int k = tid; k < K; k += kSeedsThreads) {
+    const double ck = cost[b0 + k];
+    const int st = status[b0 + k] & ~MI_STATUS_FLAG_INDEFINITE;
+    if ((st == MI_STATUS_CONVERGED || st == MI_STATUS_MAX_ITERS) && fabs(ck) < INFINITY) {      // (a NaN compares false)
+      ++cnt;
+      seeds_better(c, i, ck, k);
+    }
+  }
+  // all 256 threads are here: the DPP moves below read every lane
+  seeds_better(c, i, row_xor_f64<1>(c), row_xor_i32<1>(i)); cnt += row_xor_i32<1>(cnt);
+  seeds_better(c, i, row_xor_f64<2>(c), row_xor_i32<2>(i)); cnt += row_xor_i32<2>(cnt);
+  seeds_better(c, i, row_xor_f64<4>(c), row_xor_i32<4>(i)); cnt += row_xor_i32<4>(cnt);
+  seeds_better(c, i, row_xor_f64<8>(c), row_xor_i32<8>(i)); cnt += row_xor_i32<8>(cnt);
+  double wc = readlane_f64(c, 0);
+  int wi = __builtin_amdgcn_readlane(i, 0), wn = __builtin_amdgcn_readlane(cnt, 0);
+#pragma unroll
+  for (int row = 16; row < 64; row += 16) {
+    seeds_better(wc, wi, readlane_f64(c, row), __builtin_amdgcn_readlane(i, row));
+    wn += __builtin_amdgcn_readlane(cnt, row);
+  }
+  if ((tid & 63) == 0) { s_cost[tid >> 6] = wc; s_idx[tid >> 6] = wi; s_cnt[tid >> 6] = wn; }
+  __syncthreads();
+  wc = s_cost[0]; wi = s_idx[0]; wn = s_cnt[0];
+#pragma unroll
+  for (int w = 1; w < kSeedsThreads / 64; ++w) {
+    seeds_better(wc, wi, s_cost[w], s_idx[w]);
+    wn += s_cnt[w];
+  }
+  eligible = wn;
+  winner = -1; win_cost = INFINITY;
+  if (wn > 0) { winner = wi; win_cost = wc; }
+}
+
 __global__ void __launch_bounds__(kSeedsThreads) seeds_kernel(SeedsArgs a) {
   __shared__ double s_cost[kSeedsThreads / 64];
   __shared__ int s_idx[kSeedsThreads / 64], s_cnt[kSeedsThreads / 64];
@@ -66,38 +106,7 @@ __global__ void __launch_bounds__(kSeedsThreads) seeds_kernel(SeedsArgs a) {
   double win_cost = INFINITY;
 
   if (a.op != SEEDS_PERTURB) {
-    double c = INFINITY;
-    int i = 0x7fffffff, cnt = 0;
-    for (int k = tid; k < K; k += kSeedsThreads) {
-      const double ck = a.cost[b0 + k];
-      const int st = a.status[b0 + k] & ~MI_STATUS_FLAG_INDEFINITE;
-      if ((st == MI_STATUS_CONVERGED || st == MI_STATUS_MAX_ITERS) && fabs(ck) < INFINITY) {      // (a NaN compares false)
-        ++cnt;
-        seeds_better(c, i, ck, k);
-      }
-    }
-    // all 256 threads are here: the DPP moves below read every lane
-    seeds_better(c, i, row_xor_f64<1>(c), row_xor_i32<1>(i)); cnt += row_xor_i32<1>(cnt);
-    seeds_better(c, i, row_xor_f64<2>(c), row_xor_i32<2>(i)); cnt += row_xor_i32<2>(cnt);
-    seeds_better(c, i, row_xor_f64<4>(c), row_xor_i32<4>(i)); cnt += row_xor_i32<4>(cnt);
-    seeds_better(c, i, row_xor_f64<8>(c), row_xor_i32<8>(i)); cnt += row_xor_i32<8>(cnt);
-    double wc = readlane_f64(c, 0);
-    int wi = __builtin_amdgcn_readlane(i, 0), wn = __builtin_amdgcn_readlane(cnt, 0);
-#pragma unroll
-    for (int row = 16; row < 64; row += 16) {
-      seeds_better(wc, wi, readlane_f64(c, row), __builtin_amdgcn_readlane(i, row));
-      wn += __builtin_amdgcn_readlane(cnt, row);
-    }
-    if ((tid & 63) == 0) { s_cost[tid >> 6] = wc; s_idx[tid >> 6] = wi; s_cnt[tid >> 6] = wn; }
-    __syncthreads();
-    wc = s_cost[0]; wi = s_idx[0]; wn = s_cnt[0];
-#pragma unroll
-    for (int w = 1; w < kSeedsThreads / 64; ++w) {
-      seeds_better(wc, wi, s_cost[w], s_idx[w]);
-      wn += s_cnt[w];
-    }
-    eligible = wn;
-    if (wn > 0) { winner = wi; win_cost = wc; }
+    seeds_select(a.cost, a.status, b0, K, tid, s_cost, s_idx, s_cnt, winner, win_cost, eligible);
     if (tid == 0) {
       a.best[(size_t)g * 3 + 0] = (double)winner;
       a.best[(size_t)g * 3 + 1] = win_cost;
@@ -157,6 +166,164 @@ __global__ void __launch_bounds__(kSeedsThreads) seeds_kernel(SeedsArgs a) {
     a.u_dst[seeds_at(a.layout, B, m, M1, b, j, t)] = v;
   }
 }
+
+// seeds_mpc_join_kernel: the join between two re-solves of the receding-horizon loop (include/mi_ilqr.h, "Multi-start in the
+// receding-horizon loop"), ONE WORKGROUP PER GROUP like seeds_kernel.  SELECT as above, then for a group with winner w
+// every member gets x0 <- x_bar[w][:, replan] and u_guess[.., t] <- u_bar[w][.., min(t + replan, N - 2)] (+ sigma z for the members
+// that are not w): mpc_shift's shift and seeds_kernel's reseed in one pass, the winner's plan read once per element.  No winner: each
+// member's own shifted plan with non-finite entries read as 0, member 0 unperturbed, each member's own x_bar[:, replan].
+// NOISE ONCE PER BLOCK.  An ITEM is (member k, control block jb = j div 4, window w = t div hold): one Philox block, whose four
+// normals serve the block's up to four controls over the window's `hold` steps.  The group's K JB W items are numbered in the
+// layout's order - [b][row][t]: (k, jb, w), window fastest; [b][t][row]: (k, w, jb), block fastest; [t][row][b]: (w, jb, k), member
+// fastest - and taken 256 at a time: thread i of a TILE draws item i's normals (only the Box-Muller pairs whose live controls have
+// sigma != 0; none for the winner's slot) into LDS, held per normal (s_z[jj][i]: consecutive threads, consecutive doubles), and
+// after a barrier the tile's elements - item x control of the block x step of the window - are written with the time-last layout
+// walking (control, item, step), the time-major one (step, item, control) and the batch-minor one (step, control, item): in each the
+// fastest index of the walk is the fastest index of the layout, so consecutive lanes store consecutive addresses - runs of a whole
+// row, of m controls and of K members - whatever `hold` is.  (A thread that kept its item's run of `hold` steps to itself would
+// store at a stride of `hold` doubles in the time-last layout.)  With hold = 1 and m = 1 an item is one element and nothing is
+// shared: the thread that draws the normal stores the element, without LDS and barriers.  The normals are those of seeds_kernel bit
+// for bit: the same counter, the same Box-Muller call on the same word pair, the same rounded product and rounded sum.
+constexpr int kSeedsJoinSteps = 1024;      // steps of a window taken per pass over a tile: the tile's element count stays below 2^20
+
+__device__ __forceinline__ void seeds_mixed3(size_t i, uint32_t r0, uint32_t r1, uint32_t& d0, uint32_t& d1, uint32_t& d2) {
+  d0 = (uint32_t)(i % r0);
+  const size_t q = i / r0;
+  d1 = (uint32_t)(q % r1);
+  d2 = (uint32_t)(q / r1);
+}
+
+// item `il` of a tile whose first item has the digits (t0, t1, t2) under the radices (r0, r1), fastest first - two 32-bit divisions
+// (t0 + il < 2^31 + 256) - and which digit is what: [b][row][t] w | jb | k, [b][t][row] jb | w | k, [t][row][b] k | jb | w
+__device__ __forceinline__ void seeds_item(int layout, uint32_t il, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t r0, uint32_t r1, int& k,
+                                           uint32_t& jb, uint32_t& w) {
+  const uint32_t x0 = t0 + il, c0 = x0 / r0, d0 = x0 - c0 * r0, x1 = t1 + c0, c1 = x1 / r1, d1 = x1 - c1 * r1, d2 = t2 + c1;
+  if (layout == 0) { w = d0; jb = d1; k = (int)d2; }
+  else if (layout == 1) { jb = d0; w = d1; k = (int)d2; }
+  else { k = (int)d0; jb = d1; w = d2; }
+}
+
+// What the two write paths of seeds_mpc_join_kernel share, per element (member k = b - b0, control j, step t): the shifted plan of
+// the source problem - the winner's, or the member's own with non-finite entries read as 0 where the group has none -, the
+// member's sigma (0 for the elite slot and the padding controls), and base + sigma z as a rounded product and a rounded sum.
+__device__ __forceinline__ double seeds_join_base(const SeedsJoinArgs& a, int M1, int src_b, int j, int t, bool from_winner) {
+  const int ts = t + a.replan < M1 ? t + a.replan : M1 - 1;
+  double v = a.u_bar[seeds_at(a.layout, a.B, a.m, M1, src_b, j, ts)];
+  if (!from_winner && !(fabs(v) < INFINITY)) v = 0.0;
+  return v;
+}
+__device__ __forceinline__ double seeds_join_sigma(const SeedsJoinArgs& a, int b, int j, bool elite) {
+  return (a.sigma && !elite && j < a.m_user) ? a.sigma[(size_t)b * a.m + j] : 0.0;
+}
+__device__ __forceinline__ double seeds_rounded_add(double v, double sg, double z) {
+  double sz = sg * z;
+  asm volatile("" : "+v"(sz));                                   // the product is rounded before it is added (no FMA)
+  return v + sz;
+}
+
+__global__ void __launch_bounds__(kSeedsThreads) seeds_mpc_join_kernel(SeedsJoinArgs a) {
+  __shared__ double s_cost[kSeedsThreads / 64];
+  __shared__ int s_idx[kSeedsThreads / 64], s_cnt[kSeedsThreads / 64];
+  __shared__ double s_z[4][kSeedsThreads];
+  const int g = (int)blockIdx.x, tid = (int)threadIdx.x, K = a.K, B = a.B;
+  const int b0 = g * K;
+  int winner, eligible;
+  double win_cost;
+  seeds_select(a.cost, a.status, b0, K, tid, s_cost, s_idx, s_cnt, winner, win_cost, eligible);
+  if (tid == 0) {
+    a.best[(size_t)g * 3 + 0] = (double)winner;
+    a.best[(size_t)g * 3 + 1] = win_cost;
+    a.best[(size_t)g * 3 + 2] = (double)eligible;
+  }
+  const bool from_winner = winner >= 0;
+  const int elite = from_winner ? winner : 0;
+  const int n = a.n, N = a.N, m = a.m, M1 = N - 1, rp = a.replan, layout = a.layout;
+
+  // the K initial states (x0 is (B, n) in every layout) - with a plant the group's plant state, which every member's plant row
+  // gets too -, and the log's flags: a failed seed replaced by the winner logs again, the members of a group whose plant has ended
+  // do not
+  for (size_t e = tid; e < (size_t)K * n; e += kSeedsThreads) {
+    const int k = (int)(e / n), i = (int)(e - (size_t)k * n);
+    const double v = a.plant_x ? a.plant_x[(size_t)g * n + i] : a.x_bar[seeds_at(layout, B, n, N, b0 + (from_winner ? winner : k), i, rp)];
+    a.x0[(size_t)(b0 + k) * n + i] = v;
+    if (a.plant_x) a.plant_rows[(size_t)(b0 + k) * n + i] = v;
+  }
+  const bool ended = a.plant_x && a.plant_ended[g] != 0.0;
+  for (int k = tid; k < K; k += kSeedsThreads) {
+    if (a.mpc_dead && (from_winner || ended)) a.mpc_dead[b0 + k] = ended ? 1.0 : 0.0;
+    if (a.plant_x) a.plant_dead[b0 + k] = ended ? 1.0 : 0.0;
+  }
+
+  const uint32_t hold = (uint32_t)a.hold, W = (uint32_t)(((unsigned long long)M1 + hold - 1) / hold), JB = (uint32_t)(m + 3) >> 2;
+  const uint32_t JJ = m < 4 ? (uint32_t)m : 4u, run = hold < (uint32_t)M1 ? hold : (uint32_t)M1;
+  // the radices of an item's number, fastest first (seeds_item)
+  const uint32_t r0 = layout == 0 ? W : (layout == 1 ? JB : (uint32_t)K), r1 = layout == 1 ? W : JB;
+  const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffull), k1 = (uint32_t)(a.seed >> 32);
+  const size_t items = (size_t)K * JB * W;
+  for (size_t tile0 = 0; tile0 < items; tile0 += kSeedsThreads) {
+    const uint32_t IT = (uint32_t)(items - tile0 < (size_t)kSeedsThreads ? items - tile0 : (size_t)kSeedsThreads);
+    uint32_t t0, t1, t2;                                         // the digits of the tile's first item (the same in every thread)
+    seeds_mixed3(tile0, r0, r1, t0, t1, t2);
+    if (run == 1 && JJ == 1) {
+      // hold = 1 and m = 1: an item IS an element and there is nothing to share - the thread that draws the normal stores the
+      // element, no LDS and no barrier (the condition is the same in every thread); items are numbered in address order
+      if ((uint32_t)tid < IT) {
+        int k; uint32_t jb, w;
+        seeds_item(layout, (uint32_t)tid, t0, t1, t2, r0, r1, k, jb, w);
+        const int t = (int)w, b = b0 + k;
+        double v = seeds_join_base(a, M1, from_winner ? b0 + winner : b, 0, t, from_winner);
+        const double sg = seeds_join_sigma(a, b, 0, k == elite);
+        if (sg != 0.0) {
+          uint32_t c[4] = {a.round, w, (uint32_t)b, kSeedsBlock};
+          philox4x32_10(k0, k1, c);
+          double z0, z1;
+          box_muller(c[0], c[1], z0, z1);
+          v = seeds_rounded_add(v, sg, z0);
+        }
+        a.u_guess[seeds_at(layout, B, m, M1, b, 0, t)] = v;
+      }
+      continue;
+    }
+    __syncthreads();                                             // (the previous tile's normals have been read)
+    if ((uint32_t)tid < IT) {
+      int k; uint32_t jb, w;
+      seeds_item(layout, (uint32_t)tid, t0, t1, t2, r0, r1, k, jb, w);
+      bool pair0 = false, pair1 = false;
+      if (a.sigma && k != elite) {
+        const double* sg = a.sigma + (size_t)(b0 + k) * m;
+        const int j0 = (int)(jb << 2);
+        pair0 = (j0 < a.m_user && sg[j0] != 0.0) || (j0 + 1 < a.m_user && sg[j0 + 1] != 0.0);
+        pair1 = (j0 + 2 < a.m_user && sg[j0 + 2] != 0.0) || (j0 + 3 < a.m_user && sg[j0 + 3] != 0.0);
+      }
+      if (pair0 || pair1) {
+        uint32_t c[4] = {a.round, w, (uint32_t)(b0 + k), kSeedsBlock + jb};
+        philox4x32_10(k0, k1, c);
+        if (pair0) { double z0, z1; box_muller(c[0], c[1], z0, z1); s_z[0][tid] = z0; s_z[1][tid] = z1; }
+        if (pair1) { double z2, z3; box_muller(c[2], c[3], z2, z3); s_z[2][tid] = z2; s_z[3][tid] = z3; }
+      }
+    }
+    __syncthreads();
+    for (uint32_t s0 = 0; s0 < run; s0 += kSeedsJoinSteps) {
+      const uint32_t S = run - s0 < (uint32_t)kSeedsJoinSteps ? run - s0 : (uint32_t)kSeedsJoinSteps, slots = IT * JJ * S;
+      for (uint32_t q = tid; q < slots; q += kSeedsThreads) {
+        uint32_t il, jj, s;
+        if (layout == 0) { const uint32_t r = q / S; s = q - r * S; jj = r / IT; il = r - jj * IT; }
+        else if (layout == 1) { const uint32_t r = q / JJ; jj = q - r * JJ; s = r / IT; il = r - s * IT; }
+        else { const uint32_t r = q / IT; il = q - r * IT; s = r / JJ; jj = r - s * JJ; }
+        int k; uint32_t jb, w;
+        seeds_item(layout, il, t0, t1, t2, r0, r1, k, jb, w);
+        const unsigned long long tt = (unsigned long long)w * hold + s0 + s;
+        const int j = (int)((jb << 2) + jj);
+        if (tt >= (unsigned long long)M1 || j >= m) continue;    // (the last window's tail, the last block's)
+        const int t = (int)tt, b = b0 + k;
+        double v = seeds_join_base(a, M1, from_winner ? b0 + winner : b, j, t, from_winner);
+        const double sg = seeds_join_sigma(a, b, j, k == elite);
+        if (sg != 0.0) v = seeds_rounded_add(v, sg, s_z[jj][il]);
+        a.u_guess[seeds_at(layout, B, m, M1, b, j, t)] = v;
+      }
+    }
+  }
+}
 #endif
 
 }  // namespace mi
@@ -169,6 +336,17 @@ int launch_seeds(mi_ilqr* h, const SeedsArgs& a) {
   SeedsArgs args = a;
   void* argv[] = {&args};
   HIPCHK(hipExtLaunchKernel(reinterpret_cast<const void*>(seeds_kernel), dim3((unsigned)(a.B / a.K)), dim3(kSeedsThreads), argv, 0,
+                            h->stream, a.ev0, a.ev1, 0));
+  return MI_ILQR_OK;
+}
+
+int launch_seeds_mpc_join(mi_ilqr* h, const SeedsJoinArgs& a) {
+  if (a.K < 1 || a.B % a.K != 0 || a.hold < 1 || a.replan < 1 || a.replan >= a.N - 1 || a.layout < 0 || a.layout > 2) return MI_ILQR_E_BAD_ARG;
+  if (!a.u_bar || !a.x_bar || !a.u_guess || !a.x0 || !a.cost || !a.status || !a.best) return MI_ILQR_E_BAD_ARG;
+  if (a.plant_x && (!a.plant_ended || !a.plant_rows || !a.plant_dead)) return MI_ILQR_E_BAD_ARG;
+  SeedsJoinArgs args = a;
+  void* argv[] = {&args};
+  HIPCHK(hipExtLaunchKernel(reinterpret_cast<const void*>(seeds_mpc_join_kernel), dim3((unsigned)(a.B / a.K)), dim3(kSeedsThreads), argv, 0,
                             h->stream, a.ev0, a.ev1, 0));
   return MI_ILQR_OK;
 }

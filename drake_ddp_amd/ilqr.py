@@ -1400,6 +1400,75 @@ class BatchedIterativeLQR:
         selections.append(sel)
         return x, u, c, selections
 
+    def MPCRunMultiStart(self, K, num_resolves, replan_steps, sigma_u, seed=0, round=0, hold=1, target_step=None):   # noqa: A002
+        """The receding-horizon loop with the seeds of every group joined between its re-solves, on the device (include/mi_ilqr.h:
+        "Multi-start in the receding-horizon loop"): num_resolves x { SelectBest; every member of a group gets the winner's plan
+        shifted by replan_steps - the members that are not the winner plus sigma_u o z at round + r - and the winner's predicted state
+        x_bar[:, replan_steps]; the targets move; Solve }, then one more SelectBest.  A group without a winner continues each
+        member's own plan.  The solver must hold a solve.  -> the num_resolves + 1 SeedSelections; `mpc_log` has the per-re-solve
+        record, `stats` the last re-solve's.  K = 1 is the plain loop of MPCShift + solve_resident, bitwise.  target_step: as in
+        MPCRun, (n,) or (B, n); it is turned into per-problem rows.  On a solver that holds a plant (SetPlant) this is the closed
+        loop with ONE plant per group, member 0's: it advances replan_steps steps under the winner's policy, every member re-solves
+        from its state, and `plant_log` / `plant_state` report the group's plant in every member's row.
+        The sigma_u rows and - with target_step or per-problem targets - the target-step rows are sent before the command, as
+        ReseedFromBest sends its rows: when the library then refuses the command for the state of the handle (no solve to select
+        on), these two fields keep the new values and a shared target has become per-problem rows; nothing else has changed."""
+        what = "MPCRunMultiStart"
+        K, rows, seed, round, hold = check_seed_args(K, self.B, self.m, sigma_u, seed, round, hold, self._md, what)   # noqa: A001
+        if rows is None:
+            raise ValueError(f"{what}: sigma_u is required")
+        for name, v, lo, end in (("num_resolves", num_resolves, 1, 1 << 31), ("replan_steps", replan_steps, 1, self.N - 1)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) < end:
+                raise ValueError(f"{what}: {name} must be an integer in [{lo}, {end}); got {v!r}")
+        if round + int(num_resolves) > 1 << 32:
+            raise ValueError(f"{what}: round + num_resolves must not exceed 2^32 (re-solve r draws at round + r)")
+        if self._tracking() and target_step is not None:
+            raise ValueError(f"{what}: this solver holds a reference trajectory (SetTargetTrajectory) - it is the reference that "
+                             "moves the target, replan_steps rows per re-solve; target_step must be None")
+        steps = None if target_step is None else np.asarray(target_step, dtype=np.float64)
+        if steps is not None and steps.shape not in ((self.n,), (self.B, self.n)):
+            raise ValueError(f"{what}: target_step must be ({self.n},) or ({self.B}, {self.n}); got {steps.shape}")
+        per_problem = self._per_problem_targets() or steps is not None
+        if per_problem:                # the long form carries no shared step: every problem's target moves by its own row
+            self._set_field(_capi.F_TARGET_STEP, np.zeros((self.B, self.n)) if steps is None else np.broadcast_to(steps, (self.B, self.n)))
+        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_SIGMA, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
+        v = np.array([K, _capi.SEEDS_RESEED, seed, round, hold, 0, int(num_resolves), int(replan_steps)], dtype=np.float64)
+        rc = self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_RUN, _capi.ptr(v), v.nbytes)
+        if rc == _capi.E_UNSUPPORTED:
+            raise ValueError(f"{what}: not on this solver - at most 4 problems on the wave-per-problem kernels keep their inputs in "
+                             "host memory and have no seed groups to join")
+        if rc == _capi.E_BAD_ARG:      # (the arguments were checked above: what is left is the state of the handle)
+            raise ValueError(f"{what}: the solver holds no solve to select on (Solve() first; a reseed or a Reset() since then leaves "
+                             "none), or the reference's clock would pass its end")
+        _capi.check(rc, "mi_ilqr_set")
+        if per_problem:                # the targets as the loop left them
+            out = np.empty((self.B, self.n))
+            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_X_NOM, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+            self.x_nom = out
+        stats = _capi.Stats()
+        _capi.check(self._lib.mi_ilqr_collect_stats(self._h, C.byref(stats)), "mi_ilqr_collect_stats")
+        self.stats = stats
+        self._mpc_resolves = int(num_resolves)
+        self._mpc_replan = int(replan_steps)
+        self._check_internal(stats)
+        G = self.B // K
+        log = np.empty((int(num_resolves) + 1, G, 3))
+        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_SEEDS_BEST, _capi.ptr(log), log.nbytes), "mi_ilqr_get")
+        return [SeedSelection.from_rows(K, log[r]) for r in range(int(num_resolves) + 1)]
+
+    def mpc_winner_log(self, selections):
+        """(G, R, n + 2): for re-solve r the `mpc_log` row x0 | cost | iterations of the member that selection r + 1 names - the
+        trajectory of each group's best -, NaN where no member won.  selections: what MPCRunMultiStart returned."""
+        R = self._mpc_resolves
+        if len(selections) != R + 1:
+            raise ValueError(f"mpc_winner_log: {R + 1} selections belong to the last run of {R} re-solves; got {len(selections)}")
+        log = self.mpc_log
+        out = np.full((selections[0].winner.size, R, self.n + 2), np.nan)
+        for r in range(R):
+            p = selections[r + 1].problem
+            out[p >= 0, r] = log[p[p >= 0], r]
+        return out
+
     def seeds_kernel_ms(self):
         """Milliseconds of the kernel of the last multi-start command (HIP events of its own)."""
         out = np.empty(1)

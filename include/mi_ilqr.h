@@ -145,8 +145,8 @@ enum {
   MI_F_POLICY_MC_ENVELOPE_U = 36,/* (B,N-1,m,8) read-only: the same of every control row, m the device's control dimension */
   MI_F_POLICY_MC_SAFETY = 37,/* (B,3+N) read-only: ran | safe | safe_success | exits[0 .. N-1] of the last run, integers held in doubles */
   MI_F_SEEDS_SIGMA = 38,     /* (B,m) sigma_u rows of the multi-start perturbation, m the device's control dimension ("Multi-start" below) */
-  MI_F_SEEDS_RUN = 39,       /* (6,) write-only COMMAND: K | op | seed | round | hold | reserved = 0 - mi_ilqr_set RUNS perturb / select / reseed / gather */
-  MI_F_SEEDS_BEST = 40,      /* (G,3) read-only: winner | cost | eligible of every group of the last select, integers held in doubles */
+  MI_F_SEEDS_RUN = 39,       /* (6,) write-only COMMAND: K | op | seed | round | hold | reserved = 0 - mi_ilqr_set RUNS perturb / select / reseed / gather; (8,): the long form, "Multi-start in the receding-horizon loop" */
+  MI_F_SEEDS_BEST = 40,      /* (G,3) read-only: winner | cost | eligible of every group of the last select, integers held in doubles; (R+1,G,3) after a long-form run */
   MI_F_SEEDS_X_BAR = 41,     /* (G,n,N) read-only: the winners' x_bar of the last gather */
   MI_F_SEEDS_U_BAR = 42,     /* (G,m,N-1) read-only: the winners' u_bar of the last gather, m the device's control dimension */
   MI_F_SEEDS_COST = 43,      /* (G,) read-only: the winners' cost of the last gather */
@@ -757,6 +757,48 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
  *                                            rows, when the last command that selected was a GATHER - else MI_ILQR_E_BAD_ARG.
  *   mi_ilqr_get(MI_F_SEEDS_KERNEL_MS, &ms, 8)   the kernel of the last command, from its own HIP events; before any: MI_ILQR_E_BAD_ARG.
  *                                            Setting one of the five read-only selectors: MI_ILQR_E_BAD_ARG. */
+
+/* ---- Multi-start in the receding-horizon loop (ABI 10; the LONG FORM of MI_F_SEEDS_RUN, no new selector, no new entry point) ----
+ * The receding-horizon loop is where a local minimum hurts most: every re-solve starts from the shifted previous plan, and one bad
+ * warm start is carried from re-solve to re-solve.  The long form joins the seeds of every group BETWEEN the re-solves of the
+ * host-loop form of mi_ilqr_mpc_run, one fused kernel per re-solve (one workgroup per group), nothing of size B m (N-1) crossing the bus:
+ *   mi_ilqr_set(MI_F_SEEDS_RUN, v, 64)       v = K | op | seed | round | hold | reserved = 0 | num_resolves | replan_steps, integers
+ *                                            held in doubles, checked as the six of the short form are.  op must be RESEED (2),
+ *                                            num_resolves >= 1 (below 2^31), 1 <= replan_steps < N - 1, round + num_resolves <= 2^32 -
+ *                                            else MI_ILQR_E_BAD_ARG.  The 48-byte form is what it was; every other `bytes`:
+ *                                            MI_ILQR_E_BAD_SHAPE.
+ * The handle must hold a solve: a cold one (fresh, reset, or left with a pending guess by PERTURB / RESEED) is MI_ILQR_E_BAD_ARG.  A
+ * handle whose inputs live in host memory is MI_ILQR_E_UNSUPPORTED, as in the short form.  A refused command changes
+ * nothing.  With R = num_resolves and r = replan_steps, for i = 0 .. R - 1:
+ *   1. SELECT on the cost and status the handle holds (the rule of the short form) -> row i of the selection log.
+ *   2. JOIN.  For a group g with winner w every member k receives
+ *        x0[gK+k]           <- x_bar[gK+w][:, r]
+ *        u_guess[gK+k][j,t] <- u_bar[gK+w][j, min(t + r, N-2)]  (+ sigma_u[gK+k,j] z(seed, round + i, gK+k, t div hold, j) for k != w)
+ *      - mi_ilqr_mpc_shift's shift and RESEED's reseed, applied in that order.  The winner's own slot, every element with sigma = 0
+ *      and every padding control get the shifted value bit for bit; sigma z is a rounded product, the sum a rounded sum (no FMA); z is
+ *      the normal of PERTURB at round + i.  A group WITHOUT a winner gets what mi_ilqr_mpc_shift followed by RESEED's fallback gives
+ *      it: each member's own shifted plan with non-finite entries read as 0, member 0 unperturbed, each member's own x_bar[:, r].  A
+ *      pending guess (mi_ilqr_set_initial, mi_ilqr_mpc_shift on a solved handle) is taken as the plan.  The members of a group with a
+ *      winner log again: a seed whose re-solve failed is replaced, its `dead` flag of the MPC log is cleared.
+ *      CLOSED LOOP (a handle that holds a plant, MI_F_PLANT_STATE): ONE PLANT PER GROUP, member 0's - its state row, plant parameters,
+ *      noise sigmas, cost matrices, target and bounds.  Between SELECT and JOIN the group's plant advances r steps under the WINNER's
+ *      policy (member 0's where the group has no winner), by the plant kernel of mi_ilqr_mpc_run on G lanes: lane g draws the normals
+ *      of problem index g, so a K = 1 run is bitwise the closed loop of mi_ilqr_mpc_run.  The join then gives the plant's state to
+ *      every member as x0 - in the place of the prediction, winner or not - and to all K rows of MI_F_PLANT_STATE.  MI_F_PLANT_LOG and
+ *      the plants' flags keep their (B, ..) shapes: every member reports its group's plant.  The plant clock, MI_F_PLANT_KERNEL_MS
+ *      and the 32-bit clock check behave as in mi_ilqr_mpc_run.  The members of a group whose plant has ended stop logging and are
+ *      solved on from the plant's last finite state, as there.  (A reference trajectory and a plant exclude each other, as there.)
+ *   3. The targets move as in the host loop of mi_ilqr_mpc_run: MI_F_TARGET_STEP rows once per re-solve, a reference trajectory's
+ *      clock by r.  The long form carries no shared target_step; a caller turns one into MI_F_TARGET_STEP rows.
+ *   4. mi_ilqr_solve, then row i of the MPC log of every member (x0 | cost | iterations, mi_ilqr_get_mpc_log).  For K > 1 the re-solve
+ *      is COLD from the guess, as after RESEED - a member's own gains belong to a plan it no longer follows; for K = 1 every member
+ *      continues its own plan and the loop is bitwise mi_ilqr_mpc_shift + mi_ilqr_solve, the host loop of mi_ilqr_mpc_run.
+ * After the loop one more SELECT gives row R.  mi_ilqr_get(MI_F_SEEDS_BEST, dst, (R+1)*G*3*8) returns the log (the byte count
+ * decides, as MI_F_X_REF takes T from its byte count); MI_F_SEEDS_X_BAR / _U_BAR / _COST answer MI_ILQR_E_BAD_ARG (the run was no
+ * GATHER); mi_ilqr_collect_stats gives the last re-solve's statistics; MI_F_SEEDS_KERNEL_MS the join kernels' own events, summed over
+ * the run.  A run that fails part-way leaves the reference's clock where it was.  mi_ilqr_mpc_run itself, in both forms, is untouched.
+ * Splitting a run is exact: one call of R re-solves is bitwise R calls of one with `round` advanced by hand (each call starts a new
+ * MPC log). */
 
 #ifdef __cplusplus
 }
