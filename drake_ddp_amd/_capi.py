@@ -55,6 +55,9 @@ SEEDS_PERTURB, SEEDS_SELECT, SEEDS_RESEED, SEEDS_GATHER = 0, 1, 2, 3
 # the long form of the command ("Multi-start in the receding-horizon loop"): (8,) K | SEEDS_RESEED | seed | round | hold | 0 |
 # num_resolves | replan_steps; F_SEEDS_BEST then holds (num_resolves + 1, G, 3)
 SEEDS_RUN_DOUBLES, SEEDS_MPC_RUN_DOUBLES = 6, 8
+# the sampling form ("Sampling-based MPC"): (10,) S | SEEDS_RESEED | seed | first_sample | hold | 0 | iterations | shift | temperature | 0;
+# F_SEEDS_BEST then holds (iterations, B, 3), F_SEEDS_COST (iterations + 1, B, 2), F_SEEDS_U_BAR (B, m, N - 1)
+SEEDS_MPPI_RUN_DOUBLES = 10
 I_ITERS, I_STATUS, I_LS_TRIALS, I_KP_COUNT, I_KP_LIST = 100, 101, 102, 103, 104
 I_POLICY_MC_PASSES = 105    # (1,) passes over windows of sample groups of the last on-device Monte-Carlo run
 I64_STAGE_CYCLES = 200

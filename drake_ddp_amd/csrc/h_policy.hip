@@ -59,6 +59,8 @@ int policy_call_refused(const mi_ilqr* h, unsigned long long draws) {
   return MI_ILQR_OK;
 }
 
+}  // namespace
+
 // The rollout kernels' arguments that come from the handle: the packed policy, every per-problem array - its device rows with a
 // row's stride, else the one shared row with stride 0 (the descriptor's parameter row is staged into prow_scratch for that) - the
 // bounds, the noise rows and their stream, dt, N, B, m_user.  The caller adds its inputs and outputs.
@@ -82,6 +84,8 @@ int fill_policy_args(mi_ilqr* h, const Model* model, const double* policy, doubl
   a.dt = h->d.dt; a.N = (int32_t)h->N; a.B = (int32_t)h->B; a.m_user = device_m_user(model, h);
   return MI_ILQR_OK;
 }
+
+namespace {
 
 // MI_F_POLICY_MC_RUN, stage by stage: what the request asks for, the window plan, the scratch offsets (in doubles) and the host
 // buffers the stream copies into.

@@ -258,6 +258,9 @@ constexpr int kModePlantAdvance = 0x504c54;
 // mi_ilqr_set(MI_F_POLICY_MC_RUN): the launch entry takes a PolicyMcArgs (below) and launches policy_mc_kernel<M> and the fold behind
 // it (policy_mc.hpp) for one window of sample groups.
 constexpr int kModePolicyMC = 0x504d43;
+// mi_ilqr_set(MI_F_SEEDS_RUN) in its sampling form: the launch entry takes a MppiArgs (below) and launches mppi_rollout_kernel<M>
+// (mppi.hpp), one lane per sample of the perturbed nominal plan, whatever the handle's kernel family.
+constexpr int kModeSampledRollout = 0x4d5050;
 constexpr int kMaxBatchPluginN = 6;      // family-0 models up to this n also get the lane-per-problem kernels
 
 // The dynamic-LDS ceiling of a kernel is raised once per (kernel, device), to the hardware maximum - not
@@ -422,6 +425,41 @@ struct SeedsJoinArgs {
 };
 MI_INTERNAL int launch_seeds_mpc_join(mi_ilqr* h, const SeedsJoinArgs& a);
 
+// Arguments of mppi_rollout_kernel<M> (mppi.hpp; k_mppi.hip), the sampling form of MI_F_SEEDS_RUN: device pointers.
+struct MppiArgs {
+  PolicyArgs r;               // the rollout's per-problem data: param_rows, cost, x_nom, ulim, the strides, dt, N, B, m_user (nothing else is read)
+  const double* nominal;      // (B, N-1, m) time-major: the plans the samples perturb
+  const double* x0;           // (B, n)
+  const double* sigma;        // (B, m) sigma_u rows, or nullptr: zeros
+  double* cost_out;           // (B, S)
+  unsigned long long seed;    // the Philox key
+  uint32_t sample0;           // the global number of this launch's sample 0
+  int32_t S, hold;
+  hipEvent_t ev0, ev1;        // start / stop events riding on the launch, or nullptr
+};
+template <class M> MI_INTERNAL int launch_mppi_rollout(mi_ilqr* h, const MppiArgs& a);              // mppi.hpp; k_mppi.hip
+// ... and of mppi_update_kernel (no model), one workgroup per problem: weights, log rows, the blend into the next nominal
+struct MppiUpdateArgs {
+  const double* nom_in;       // (B, N-1, m) time-major: the nominal the samples were drawn around
+  double* nom_out;            // (B, N-1, m): the next nominal (never nom_in)
+  const double* cost;         // (B, S): the samples' costs
+  const double* sigma;        // (B, m) or nullptr
+  const double* ulim;         // (B, 2, m) or nullptr
+  double* best;               // (B, 3): this iteration's row argmin | cost | finite
+  double* costlog;            // (B, 2): this iteration's row nominal cost | ESS
+  unsigned long long seed;
+  double temperature;
+  uint32_t sample0;
+  int32_t B, S, m, m_user, N, hold;
+  hipEvent_t ev0, ev1;
+};
+MI_INTERNAL int launch_mppi_update(mi_ilqr* h, const MppiUpdateArgs& a);
+// the nominal from the handle's layout into the staging copy (src nullptr: zeros); the final nominal into u_guess (shifted), the
+// time-last copy and the closing row of the cost log
+MI_INTERNAL int launch_mppi_stage(mi_ilqr* h, const double* src, double* nom, int B, int m, int N, int layout, hipEvent_t ev0);
+MI_INTERNAL int launch_mppi_handover(mi_ilqr* h, const double* nom, double* u_guess, double* tl, const double* cost1, double* costlog, int B,
+                                     int m, int N, int layout, int shift, hipEvent_t ev1);
+
 // Arguments of plant_advance_kernel<M> (plant_advance.hpp), all device pointers.  "Problem-minor": element e of problem b at e * B + b.
 struct PlantArgs {
   const double* policy;       // (steps, n + m + m n, B) problem-minor: row j = x_bar_j | u_bar_j | K_j (m x n, row-major), the first `steps` columns
@@ -468,6 +506,7 @@ int model_entry(mi_ilqr* h, int mode, const void* kargs) {
     const PolicyMcArgs& a = *static_cast<const PolicyMcArgs*>(kargs);
     return a.r.noise ? launch_policy_mc_noise<M>(h, a) : launch_policy_mc<M>(h, a);
   }
+  if (mode == kModeSampledRollout) return launch_mppi_rollout<M>(h, *static_cast<const MppiArgs*>(kargs));
   if (mode == kModePlantAdvance) {
     const PlantArgs& a = *static_cast<const PlantArgs*>(kargs);
     return a.noise ? launch_plant_advance_noise<M>(h, a) : launch_plant_advance<M>(h, a);

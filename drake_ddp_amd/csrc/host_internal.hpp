@@ -2,7 +2,7 @@
 // in the unit named above each group, all of it hidden from the dynamic symbol table.  Host units only: no k_*.hip unit, no
 // launch_*.hpp, no family header and not the plugin template includes this header, and it includes no family header.
 // The calls go one way: h_memory.hip calls nothing of the others; mi_ilqr.hip (the core) calls h_memory.hip, and of h_fields.hip the
-// field table alone; h_policy.hip, h_mpc.hip and h_seeds.hip call the core and h_memory.hip (the plant its policy's pack, the seeds
+// field table alone; h_policy.hip, h_mpc.hip, h_seeds.hip and h_mppi.hip call the core and h_memory.hip (the plant its policy's pack, the seeds
 // its rule for the controls a launch starts from, and - the one call between two of them - h_seeds.hip hands the long form of its
 // command to the loop in h_mpc.hip); h_fields.hip, the boundary's selectors, calls all of them.  h_comm.hip stands alone.
 #pragma once
@@ -110,6 +110,8 @@ enum { PACK_TIME_MAJOR = 0, PACK_PROBLEM_MINOR = 1 };
 // sel != nullptr (the (G, 3) selection rows of multi-start, on the device): G = B / K columns, column g the policy of its group's winner
 MI_INTERNAL int pack_policy(mi_ilqr* h, double* dst, int steps, int order, const double* sel = nullptr, int K = 1);
 MI_INTERNAL const double* policy_u_source(const mi_ilqr* h);      // the controls the next launch would start from; nullptr: zeros
+// the rollout kernels' arguments that come from the handle (every per-problem array or the shared row, bounds, noise, dt, N, B, m_user)
+MI_INTERNAL int fill_policy_args(mi_ilqr* h, const Model* model, const double* policy, double* prow_scratch, PolicyArgs& a);
 MI_INTERNAL int set_mc_dist(mi_ilqr* h, const double* src, size_t bytes);
 MI_INTERNAL int set_mc_box(mi_ilqr* h, const double* src, size_t bytes);
 MI_INTERNAL int set_mc_observe(mi_ilqr* h, const double* src, size_t bytes);
@@ -120,6 +122,9 @@ MI_INTERNAL int set_seeds_sigma(mi_ilqr* h, const double* src, size_t bytes);
 MI_INTERNAL int run_seeds(mi_ilqr* h, const double* v, size_t bytes);
 constexpr int kNotSeedsField = 1;
 MI_INTERNAL int get_seeds_field(mi_ilqr* h, int which, double* dst, size_t bytes);
+
+// ---- h_mppi.hip: the sampling form of MI_F_SEEDS_RUN (10 doubles), which h_seeds.hip hands over before it looks at anything else
+MI_INTERNAL int run_mppi(mi_ilqr* h, const double* v);
 
 // ---- h_mpc.hip: mi_ilqr_get of the plant's and the reference's selectors; kNotPlantField for every other one
 constexpr int kNotPlantField = 1;

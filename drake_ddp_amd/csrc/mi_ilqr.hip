@@ -1,7 +1,7 @@
 // libmi_ilqr.so - host side of the C ABI declared in include/mi_ilqr.h, the core: the model table, the handle's creation, the
 // launch of the solver kernels (make_args, launch) with the solve, collect and stage entry points, the cost, initial-guess and
 // control-limit entry points, timing.  The other concerns of the host have units of their own (h_memory.hip, h_fields.hip,
-// h_policy.hip, h_mpc.hip, h_seeds.hip, h_comm.hip; host_internal.hpp declares what they share).
+// h_policy.hip, h_mpc.hip, h_seeds.hip, h_mppi.hip, h_comm.hip; host_internal.hpp declares what they share).
 //
 // The library owns the device-resident solver state of a batch (the persistent attributes of the reference class, ilqr.py:61-91,
 // with a leading batch axis), dispatches the gfx950 kernels and moves data across the boundary.  No compute happens on the host:
@@ -97,7 +97,7 @@ Model builtin(int family, size_t (*lds)(int32_t, int32_t), int (*launch)(mi_ilqr
   return r;
 }
 // wave-per-problem kernels (k_<model>.hip, k_<model>_lim.hip) and the lane-per-problem ones (k_batch.hip, k_batch_lim.hip); every
-// model's policy-rollout kernels are in k_policy.hip and, with noise, k_policy_noise.hip
+// model's policy-rollout kernels are in k_policy.hip and, with noise, k_policy_noise.hip, its sampled rollout in k_mppi.hip
 template <class M>
 Model wave_model(std::initializer_list<double> defaults) {
   return builtin<M>(0, wave_lds<M::n, M::m>,

@@ -342,6 +342,58 @@ def check_seed_args(K, B, m, sigma_u=None, seed=0, round=0, hold=1, m_dev=None, 
     return K, rows, seed, round, hold
 
 
+def check_mppi_args(S, iterations, B, m, N, sigma_u, temperature, seed=0, first_sample=0, hold=1, shift=0, m_dev=None, what="MPPIRun"):
+    """The sampling-based MPC arguments -> (S, iterations, rows, temperature, seed, first_sample, hold, shift): the integers as ints,
+    rows the contiguous (B, m_dev) float64 sigma_u rows with zeros on the padding controls (sigma_u: scalar, (m,) or (B, m)).
+    ValueError - decided here, before anything reaches the library - for an S that is no integer in [1, 2^31 - 64], an iterations or hold that is no integer in [1, 2^31), a
+    seed that is no integer in [0, 2^53), a first_sample that is no integer in [0, 2^32), first_sample + iterations S > 2^32, a shift
+    that is no integer in [0, N - 2], a temperature that is no number >= 0 (NaN included), a missing sigma_u, any other shape of it
+    and a negative, NaN or infinite entry in it."""
+    def integer(v, name, lo, end, rng):
+        ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer, float, np.floating))
+        if ok and isinstance(v, (float, np.floating)):
+            ok = bool(np.isfinite(v) and v == np.floor(v))
+        if not ok or not lo <= int(v) < end:
+            raise ValueError(f"{what}: {name} must be an integer in {rng}; got {v!r}")
+        return int(v)
+
+    S = integer(S, "S", 1, (1 << 31) - 63, "[1, 2^31 - 64]")
+    iterations = integer(iterations, "iterations", 1, 1 << 31, "[1, 2^31)")
+    if sigma_u is None:
+        raise ValueError(f"{what}: sigma_u is required")
+    _, rows, seed, _, hold = check_seed_args(1, B, m, sigma_u, seed, 0, hold, m_dev, what)
+    first_sample = integer(first_sample, "first_sample", 0, 1 << 32, "[0, 2^32)")
+    if first_sample + iterations * S > 1 << 32:
+        raise ValueError(f"{what}: first_sample + iterations S must not exceed 2^32 (iteration i draws samples first_sample + i S ..)")
+    shift = integer(shift, "shift", 0, N - 1, f"[0, {N - 2}]")
+    ok = not isinstance(temperature, (bool, np.bool_)) and isinstance(temperature, (int, float, np.integer, np.floating))
+    if not ok or not temperature >= 0.0:
+        raise ValueError(f"{what}: temperature must be a number >= 0 (0: the best sample alone); got {temperature!r}")
+    return S, iterations, rows, float(temperature), seed, first_sample, hold, shift
+
+
+class MPPIResult:
+    """What MPPIRun did (include/mi_ilqr.h: "Sampling-based MPC"): u (B, m, N-1) the final nominal plans, unshifted; per iteration and
+    problem, (I, B): best_sample - the sample of least finite cost, -1 when none was finite -, best_cost (+inf then), finite - the
+    number of samples with a finite cost - and ess, the effective sample size 1 / sum w^2 (NaN without a finite sample);
+    nominal_cost (I + 1, B): the nominal's own cost at the start of every iteration and, row I, of the final nominal; kernel_ms: the
+    run's kernels, first to last."""
+    __slots__ = ("u", "best_sample", "best_cost", "finite", "ess", "nominal_cost", "kernel_ms")
+
+    def __init__(self, u, best_sample, best_cost, finite, ess, nominal_cost, kernel_ms):
+        self.u, self.best_sample, self.best_cost, self.finite = u, best_sample, best_cost, finite
+        self.ess, self.nominal_cost, self.kernel_ms = ess, nominal_cost, kernel_ms
+
+    @classmethod
+    def from_rows(cls, u, best, cost, kernel_ms):
+        """best (I, B, 3) and cost (I + 1, B, 2) as MI_F_SEEDS_BEST / MI_F_SEEDS_COST return them."""
+        return cls(u, best[:, :, 0].astype(np.int64), np.ascontiguousarray(best[:, :, 1]), best[:, :, 2].astype(np.int64),
+                   np.ascontiguousarray(cost[:-1, :, 1]), np.ascontiguousarray(cost[:, :, 0]), kernel_ms)
+
+    def __repr__(self):
+        return f"MPPIResult(iterations={self.best_cost.shape[0]}, nominal_cost[-1]={self.nominal_cost[-1].tolist()})"
+
+
 class SeedSelection:
     """What SelectBest found in every group of K seeds (include/mi_ilqr.h: "Multi-start"), (G,) arrays: winner - the member index of
     the eligible member of least cost, -1 when no member is eligible -, its cost (+inf then) and the number of eligible members."""
@@ -1468,6 +1520,34 @@ class BatchedIterativeLQR:
             p = selections[r + 1].problem
             out[p >= 0, r] = log[p[p >= 0], r]
         return out
+
+    # ------------------------------------------------------------- sampling-based MPC (include/mi_ilqr.h: "Sampling-based MPC")
+    def MPPIRun(self, S, iterations, sigma_u, temperature, seed=0, first_sample=0, hold=1, shift=0):
+        """MPPI / predictive sampling on the device, the derivative-free counterpart of Solve: every problem improves its own nominal
+        plan - what the next Solve would start from: the guess given to SetInitialGuess, else the controls the solver holds, else
+        zeros - by `iterations` rounds of { S samples clip(u + sigma_u o z), sample 0 the unperturbed plan; open-loop rollouts costed
+        on the applied controls; weights exp(-(cost - best) / temperature) over the samples with a finite cost; their weighted
+        mean }.  temperature = 0 takes the best sample alone (the nominal's cost then never rises).  z: standard normals of (seed,
+        global sample number first_sample + i S + s, step div hold, problem, control) alone.  sigma_u: scalar, (m,) or (B, m).
+        Afterwards the final plans, shifted by `shift` steps as MPCShift shifts, are the pending guess of a cold solver: Solve()
+        polishes them, SetInitialState + MPPIRun again is the receding-horizon loop.  -> MPPIResult.  Nothing of size S crosses
+        the bus.  Not on a solver that holds a reference trajectory, nor on one of at most 4 problems on the wave-per-problem kernels."""
+        S, iterations, rows, temperature, seed, first_sample, hold, shift = check_mppi_args(
+            S, iterations, self.B, self.m, self.N, sigma_u, temperature, seed, first_sample, hold, shift, self._md)
+        self._push_problem()                                   # (x0, costs, targets; a guess given to SetInitialGuess is the nominal)
+        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_SIGMA, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
+        v = np.array([S, _capi.SEEDS_RESEED, seed, first_sample, hold, 0, iterations, shift, temperature, 0], dtype=np.float64)
+        assert v.size == _capi.SEEDS_MPPI_RUN_DOUBLES
+        rc = self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_RUN, _capi.ptr(v), v.nbytes)
+        if rc == _capi.E_UNSUPPORTED:
+            raise ValueError("MPPIRun: not on this solver - it holds a reference trajectory (SetTargetTrajectory), or it has at most 4 "
+                             "problems on the wave-per-problem kernels, which keep their inputs in host memory; use a larger batch")
+        _capi.check(rc, "mi_ilqr_set")
+        best, cost = np.empty((iterations, self.B, 3)), np.empty((iterations + 1, self.B, 2))
+        u = np.empty((self.B, self._md, self.N - 1))
+        for which, out in ((_capi.F_SEEDS_BEST, best), (_capi.F_SEEDS_COST, cost), (_capi.F_SEEDS_U_BAR, u)):
+            _capi.check(self._lib.mi_ilqr_get(self._h, which, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+        return MPPIResult.from_rows(np.ascontiguousarray(u[:, :self.m, :]), best, cost, self.seeds_kernel_ms())
 
     def seeds_kernel_ms(self):
         """Milliseconds of the kernel of the last multi-start command (HIP events of its own)."""

@@ -145,11 +145,11 @@ enum {
   MI_F_POLICY_MC_ENVELOPE_U = 36,/* (B,N-1,m,8) read-only: the same of every control row, m the device's control dimension */
   MI_F_POLICY_MC_SAFETY = 37,/* (B,3+N) read-only: ran | safe | safe_success | exits[0 .. N-1] of the last run, integers held in doubles */
   MI_F_SEEDS_SIGMA = 38,     /* (B,m) sigma_u rows of the multi-start perturbation, m the device's control dimension ("Multi-start" below) */
-  MI_F_SEEDS_RUN = 39,       /* (6,) write-only COMMAND: K | op | seed | round | hold | reserved = 0 - mi_ilqr_set RUNS perturb / select / reseed / gather; (8,): the long form, "Multi-start in the receding-horizon loop" */
-  MI_F_SEEDS_BEST = 40,      /* (G,3) read-only: winner | cost | eligible of every group of the last select, integers held in doubles; (R+1,G,3) after a long-form run */
+  MI_F_SEEDS_RUN = 39,       /* (6,) write-only COMMAND: K | op | seed | round | hold | reserved = 0 - mi_ilqr_set RUNS perturb / select / reseed / gather; (8,): the long form, "Multi-start in the receding-horizon loop"; (10,): the sampling form, "Sampling-based MPC" */
+  MI_F_SEEDS_BEST = 40,      /* (G,3) read-only: winner | cost | eligible of every group of the last select, integers held in doubles; (R+1,G,3) after a long-form run; (I,B,3) after a sampling-form run */
   MI_F_SEEDS_X_BAR = 41,     /* (G,n,N) read-only: the winners' x_bar of the last gather */
-  MI_F_SEEDS_U_BAR = 42,     /* (G,m,N-1) read-only: the winners' u_bar of the last gather, m the device's control dimension */
-  MI_F_SEEDS_COST = 43,      /* (G,) read-only: the winners' cost of the last gather */
+  MI_F_SEEDS_U_BAR = 42,     /* (G,m,N-1) read-only: the winners' u_bar of the last gather, m the device's control dimension; (B,m,N-1) after a sampling-form run */
+  MI_F_SEEDS_COST = 43,      /* (G,) read-only: the winners' cost of the last gather; (I+1,B,2) after a sampling-form run */
   MI_F_SEEDS_KERNEL_MS = 44, /* (1,) read-only: milliseconds of the kernel of the last MI_F_SEEDS_RUN, from its own HIP events */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
@@ -799,6 +799,52 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
  * the run.  A run that fails part-way leaves the reference's clock where it was.  mi_ilqr_mpc_run itself, in both forms, is untouched.
  * Splitting a run is exact: one call of R re-solves is bitwise R calls of one with `round` advanced by hand (each call starts a new
  * MPC log). */
+
+/* ---- Sampling-based MPC (ABI 10; the SAMPLING FORM of MI_F_SEEDS_RUN, 10 doubles, no new selector, no new entry point) ----
+ * MPPI / predictive sampling, the derivative-free counterpart of a solve: every problem b improves its own nominal plan u (m, N-1)
+ * from its own x0 under its own Q, R, Qf, target, model parameters and box, by `iterations` rounds of { perturb the plan S times; roll
+ * the S plans out; weight them by exp(-cost / temperature); average them }.  The loop never leaves the device.
+ *   mi_ilqr_set(MI_F_SEEDS_RUN, v, 80)       v = S | op | seed | first_sample | hold | reserved = 0 | iterations | shift | temperature |
+ *                                            reserved = 0, integers held in doubles.  op must be RESEED (2), as in the long form; sigma_u
+ *                                            comes from MI_F_SEEDS_SIGMA (not set: zeros).  S is an integer in [1, 2^31 - 64] (whole waves of
+ *                                            64 samples are counted in 32 bits), iterations and hold are integers in [1, 2^31), seed in [0, 2^53), first_sample in [0, 2^32) with first_sample + iterations S
+ *                                            <= 2^32 (the sample counter is 32 bits), shift in [0, N - 2], temperature >= 0 and no NaN
+ *                                            - else MI_ILQR_E_BAD_ARG.  A handle that holds a reference trajectory (MI_F_X_REF):
+ *                                            MI_ILQR_E_UNSUPPORTED, as mi_ilqr_policy_rollout refuses it; a handle whose inputs live in
+ *                                            host memory: MI_ILQR_E_UNSUPPORTED, as in the short form.  The 48-byte and the 64-byte
+ *                                            form are what they were; 88 bytes and more stay MI_ILQR_E_BAD_SHAPE.  A refused command
+ *                                            changes nothing.
+ * THE NOMINAL starts as what the next solve would start from: the pending guess, else u_bar, else zeros.  With I = iterations, for
+ * i = 0 .. I - 1:
+ *   ROLLOUT.  Sample s = 0 .. S - 1 of problem b applies v_s[k,t] = clip(u[k,t] + sigma_u[b,k] z, box_b): the clip on a control-limited
+ *   handle only and by comparisons; sigma z is a rounded product, the sum a rounded sum (no FMA).  z is a standard normal of
+ *   (seed, g, t div hold, b, k) alone, g = first_sample + i S + s the GLOBAL SAMPLE NUMBER: Philox4x32-10 under the key
+ *   (seed mod 2^32, seed div 2^32) at counter = (g, t div hold, b, 1024 + k / 4), Box-Muller normal k mod 4 of the block, as under
+ *   "Multi-start" (blocks 1024.. are the samples'; 0.. / 256.. / 512.. / 768.. stay the states', the controls', the Monte-Carlo draws'
+ *   and the seed perturbations').  z does not depend on S, on B, on the launch or on the layout.  SAMPLE 0 IS THE ELITE SLOT: it draws
+ *   nothing and applies clip(u); so do a zero sigma and the padding controls, bit for bit.  Each sample is rolled out open loop - no
+ *   feedback gains - and costs what mi_ilqr_policy_rollout's stage and terminal expressions give on the APPLIED control v.  A sample
+ *   that meets an infeasible step (models that can fail), a non-finite state or a non-finite cost has cost +inf.
+ *   UPDATE.  L_min is the least finite cost, ties to the lowest s; a_s = -(L_s - L_min) / temperature, w_s = exp(a_s) / sum exp(a_s)
+ *   over the finite samples only; temperature = 0 is the indicator of the argmin (predictive sampling).  u_new[k,t] = sum_s w_s v_s[k,t]:
+ *   the first finite sample's rounded product starts the sum, each later term is a rounded product added by a rounded sum; samples
+ *   without a finite cost are skipped, not multiplied by zero.  Both sums - sum exp(a_s) and the blend - run SEQUENTIALLY IN s = 0, 1, ..
+ *   S - 1, an order that is a function of S alone.  The result is clipped again on a limited handle.  A problem without a finite
+ *   sample keeps u.
+ *   LOG.  Row i: argmin sample | its cost | finite samples (no finite sample: -1 | +inf | 0), and nominal cost (sample 0's) | ESS =
+ *   1 / sum w_s^2 (NaN without a finite sample).
+ * A closing rollout of the final nominal alone (S = 1) gives row I of the nominal cost (its ESS: NaN).  The final nominal, shifted by
+ * `shift` steps as mi_ilqr_mpc_shift shifts - u_guess[t] = u[min(t + shift, N-2)] - becomes the handle's pending guess and the handle
+ * is cold, as after mi_ilqr_reset followed by mi_ilqr_set_initial(u_guess): mi_ilqr_solve polishes the plan, and a new x0 followed by
+ * the command again is the receding-horizon loop.
+ *   mi_ilqr_get(MI_F_SEEDS_BEST, dst, I*B*3*8)        argmin sample | its cost | finite samples, per iteration and problem
+ *   mi_ilqr_get(MI_F_SEEDS_COST, dst, (I+1)*B*2*8)    nominal cost | ESS (NaN in the closing row)
+ *   mi_ilqr_get(MI_F_SEEDS_U_BAR, dst, B*m*(N-1)*8)   the final nominal, unshifted, time last, m the device's control dimension
+ *   mi_ilqr_get(MI_F_SEEDS_X_BAR, ..)                 MI_ILQR_E_BAD_ARG (cleared: the run keeps no states)
+ *   mi_ilqr_get(MI_F_SEEDS_KERNEL_MS, &ms, 8)         the run's kernels, first to last, from one pair of HIP events
+ * Consequences: one call of I iterations is bitwise I calls of one iteration with first_sample advanced by S each; under temperature =
+ * 0 the nominal cost of row i + 1 is the best cost of row i bitwise, so the cost never rises; nothing of size S leaves the device and
+ * nothing of size S (N-1) is ever stored - the update regenerates every sample's applied controls from the counters. */
 
 #ifdef __cplusplus
 }
