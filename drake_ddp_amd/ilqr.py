@@ -7,6 +7,10 @@ solver section of any example script can import it as a drop-in; the `system`
 argument is a model descriptor (drake_ddp_amd.models.ModelSystem).  All compute
 is in libmi_ilqr.so (HIP, gfx950) — this file only moves arrays across the
 boundary.  ``BatchedIterativeLQR`` is the same surface with a leading batch axis.
+
+The two classes are the only place of the front end that calls the library.  What a method accepts is decided in argcheck.py
+(the ``check_*`` functions, before the first call on the handle), what it returns is built in results.py (``PolicyStats``,
+``SeedSelection``, ...); neither module needs the library, and both are re-exported here under the names they always had.
 """
 import ctypes as C
 import time
@@ -17,7 +21,11 @@ import numpy as np
 
 from . import _capi
 from . import utils_derivs_interpolation
+from .argcheck import (MC_DISTS, check_mc_args, check_mc_observe, check_model_params, check_mppi_args, check_noise_args,  # noqa: F401
+                       check_plant_args, check_rollout_args, check_seed_args, check_target_trajectory, integer)
 from .models import ModelSystem
+from .results import (MPPIResult, PlantLog, PolicyEnvelope, PolicyRollout, PolicySafety, PolicySamples, PolicyStats,  # noqa: F401
+                      SeedSelection, _chan)
 
 _KP_IDS = {"setInterval": _capi.KP_SET_INTERVAL, "adaptiveJerk": _capi.KP_ADAPTIVE_JERK,
            "iterativeError": _capi.KP_ITERATIVE_ERROR}
@@ -38,533 +46,6 @@ class _PinnedBlock:
 
     def _released(self, _ref):
         self.busy = False
-
-
-def check_model_params(params, B, n_params):
-    """SetModelParameters' argument as a contiguous (B, n_params) float64 array ((n_params,) is broadcast to rows), or None for
-    None.  ValueError for any other shape and for NaN / infinity - decided here, before anything reaches the device."""
-    if params is None:
-        return None
-    if n_params == 0:
-        raise ValueError("SetModelParameters: this model has no parameters")
-    try:
-        a = np.asarray(params, dtype=np.float64)
-    except (TypeError, ValueError) as e:
-        raise ValueError(f"SetModelParameters: not an array of numbers ({e})") from None
-    if a.shape == (n_params,):
-        a = np.broadcast_to(a, (B, n_params))
-    elif a.shape != (B, n_params):
-        raise ValueError(f"SetModelParameters: parameters must be ({B}, {n_params}) or ({n_params},); got {a.shape}")
-    if not np.isfinite(a).all():
-        raise ValueError("SetModelParameters: NaN or infinity")
-    return np.ascontiguousarray(a)
-
-
-def check_target_trajectory(x_ref, clock, B, n):
-    """SetTargetTrajectory's arguments as a contiguous (B, T, n) float64 array ((T, n) is broadcast to the batch; None for None) and
-    the clock as an int.  ValueError for any other shape, T = 0, NaN / infinity and a clock that is not an integer in [0, 2^30) -
-    decided here, before anything reaches the device."""
-    try:
-        c = int(clock)
-        ok = c == clock and 0 <= c < 2 ** 30
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"SetTargetTrajectory: clock must be an integer in [0, 2^30); got {clock!r}")
-    if x_ref is None:
-        return None, c
-    try:
-        a = np.asarray(x_ref, dtype=np.float64)
-    except (TypeError, ValueError) as e:
-        raise ValueError(f"SetTargetTrajectory: not an array of numbers ({e})") from None
-    if a.ndim == 2 and a.shape[1] == n:
-        a = np.broadcast_to(a, (B,) + a.shape)
-    elif not (a.ndim == 3 and a.shape[0] == B and a.shape[2] == n):
-        raise ValueError(f"SetTargetTrajectory: the reference must be (T, {n}) or ({B}, T, {n}); got {a.shape}")
-    if a.shape[1] < 1:
-        raise ValueError("SetTargetTrajectory: the reference needs at least one row (T >= 1)")
-    if not np.isfinite(a).all():
-        raise ValueError("SetTargetTrajectory: NaN or infinity")
-    return np.ascontiguousarray(a), c
-
-
-def check_rollout_args(x0, params, B, n, n_params):
-    """RolloutPolicy's arguments as contiguous (B, S, n) and (B, S, n_params) float64 arrays (None for params=None).
-    ValueError for a wrong rank or size and for NaN / infinity in params - decided here, before anything reaches the device.
-    A non-finite x0 is data: that sample ends before its first step."""
-    try:
-        x0 = np.asarray(x0, dtype=np.float64)
-    except (TypeError, ValueError) as e:
-        raise ValueError(f"RolloutPolicy: x0 is not an array of numbers ({e})") from None
-    if x0.ndim == 2 and x0.shape[1] == n and x0.shape[0] >= 1:
-        x0 = np.broadcast_to(x0, (B,) + x0.shape)
-    elif not (x0.ndim == 3 and x0.shape[0] == B and x0.shape[1] >= 1 and x0.shape[2] == n):
-        raise ValueError(f"RolloutPolicy: x0 must be ({B}, S, {n}) or (S, {n}) with S >= 1; got {x0.shape}")
-    S = x0.shape[1]
-    if params is not None:
-        if n_params == 0:
-            raise ValueError("RolloutPolicy: this model has no parameters")
-        try:
-            params = np.asarray(params, dtype=np.float64)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"RolloutPolicy: params is not an array of numbers ({e})") from None
-        if params.shape == (S, n_params):
-            params = np.broadcast_to(params, (B, S, n_params))
-        elif params.shape != (B, S, n_params):
-            raise ValueError(f"RolloutPolicy: params must be ({B}, {S}, {n_params}) or ({S}, {n_params}); got {params.shape}")
-        if not np.isfinite(params).all():
-            raise ValueError("RolloutPolicy: NaN or infinity in params")
-        params = np.ascontiguousarray(params)
-    return np.ascontiguousarray(x0), params
-
-
-def check_noise_args(state_noise, control_noise, seed, first_sample, common_noise, B, n, m, m_dev=None, S=None):
-    """RolloutPolicy's disturbance arguments -> (rows, stream): rows is None when both sigmas are None (no noise), else the
-    contiguous (B, n + m_dev) float64 array sigma_x | sigma_u with zeros on the padding controls (m_dev: the device's number of
-    controls, default m); stream is the float64 triple seed | first_sample | common.  state_noise: scalar, (n,) or (B, n);
-    control_noise: scalar, (m,) or (B, m); one of them None: zeros.  ValueError - decided here, before anything reaches the device -
-    for any other shape, a negative, NaN or infinite sigma, a seed that is no integer in [0, 2^53), a first_sample that is no integer
-    in [0, 2^32) or - S given - with first_sample + S > 2^32."""
-    m_dev = m if m_dev is None else int(m_dev)
-
-    def integer(v, name, bound, what):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer, float, np.floating)):
-            raise ValueError(f"RolloutPolicy: {name} must be an integer in [0, {what}); got {v!r}")
-        if isinstance(v, (float, np.floating)) and not (np.isfinite(v) and v == np.floor(v)):
-            raise ValueError(f"RolloutPolicy: {name} must be an integer in [0, {what}); got {v!r}")
-        v = int(v)
-        if not 0 <= v < bound:
-            raise ValueError(f"RolloutPolicy: {name} must be an integer in [0, {what}); got {v}")
-        return v
-
-    seed = integer(seed, "seed", 1 << 53, "2^53")
-    first_sample = integer(first_sample, "first_sample", 1 << 32, "2^32")
-    if S is not None and first_sample + int(S) > (1 << 32):
-        raise ValueError(f"RolloutPolicy: first_sample + S must not exceed 2^32; got {first_sample} + {int(S)}")
-    stream = np.array([seed, first_sample, 1.0 if common_noise else 0.0], dtype=np.float64)
-    if state_noise is None and control_noise is None:
-        return None, stream
-
-    def sigma(v, k, name):
-        if v is None:
-            return np.zeros((B, k))
-        try:
-            a = np.asarray(v, dtype=np.float64)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"RolloutPolicy: {name} is not an array of numbers ({e})") from None
-        if a.shape not in ((), (k,), (B, k)):
-            raise ValueError(f"RolloutPolicy: {name} must be a scalar, ({k},) or ({B}, {k}); got {a.shape}")
-        if not np.isfinite(a).all():
-            raise ValueError(f"RolloutPolicy: NaN or infinity in {name}")
-        if (a < 0.0).any():
-            raise ValueError(f"RolloutPolicy: negative entry in {name} (standard deviations)")
-        return np.broadcast_to(a, (B, k))
-
-    rows = np.zeros((B, n + m_dev))
-    rows[:, :n] = sigma(state_noise, n, "state_noise")
-    rows[:, n:n + m] = sigma(control_noise, m, "control_noise")
-    return rows, stream
-
-
-def check_plant_args(x, params, state_noise, control_noise, seed, common_noise, feedback, clock, B, n, m, n_params, m_dev=None):
-    """SetPlant's arguments -> (x, params, noise, stream): x the contiguous (B, n) float64 states ((n,) is broadcast to rows); params
-    None or the contiguous (B, n_params) rows ((n_params,) broadcast); noise None when both sigmas are None, else the (B, n + m_dev)
-    rows sigma_x | sigma_u of check_noise_args (the same forms: scalar, (n,) / (m,), (B, n) / (B, m)); stream the float64 quadruple
-    seed | clock | common | feedback.  ValueError - decided here, before anything reaches the device - for any other shape, NaN or
-    infinity in x or params, params for a model without parameters, a negative, NaN or infinite sigma, a seed that is no integer in
-    [0, 2^53), a clock that is no integer in [0, 2^32), common_noise or feedback that is no bool (or 0 / 1)."""
-    def array(v, name):
-        try:
-            return np.asarray(v, dtype=np.float64)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"SetPlant: {name} is not an array of numbers ({e})") from None
-
-    def rows(v, k, name):
-        a = array(v, name)
-        if a.shape == (k,):
-            a = np.broadcast_to(a, (B, k))
-        elif a.shape != (B, k):
-            raise ValueError(f"SetPlant: {name} must be ({B}, {k}) or ({k},); got {a.shape}")
-        if not np.isfinite(a).all():
-            raise ValueError(f"SetPlant: NaN or infinity in {name}")
-        return np.ascontiguousarray(a)
-
-    def flag(v, name):
-        if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and v in (0, 1)):
-            return 1.0 if v else 0.0
-        raise ValueError(f"SetPlant: {name} must be True or False; got {v!r}")
-
-    x = rows(x, n, "x")
-    if params is not None:
-        if n_params == 0:
-            raise ValueError("SetPlant: this model has no parameters")
-        params = rows(params, n_params, "params")
-    try:
-        noise, st = check_noise_args(state_noise, control_noise, seed, clock, False, B, n, m, m_dev)
-    except ValueError as e:       # (the same rules; the messages speak of this call and of the clock)
-        raise ValueError(str(e).replace("RolloutPolicy", "SetPlant").replace("first_sample", "clock")) from None
-    stream = np.array([st[0], st[1], flag(common_noise, "common_noise"), flag(feedback, "feedback")], dtype=np.float64)
-    return x, params, noise, stream
-
-
-MC_DISTS = {"normal": _capi.MC_DIST_NORMAL, "uniform": _capi.MC_DIST_UNIFORM}
-
-
-def check_mc_args(S, x0_mean, x0_spread, B, n, n_params, *, x0_dist="normal", params_mean=None, params_spread=None, params_dist="uniform",
-                  goal=None, samples=False, first_sample=0):
-    """RolloutPolicyStats' sampler arguments -> (rows, run): rows the contiguous (B, 3 n + 2 n_params) float64 array x0_mean | x0_spread |
-    goal | p_mean | p_spread (MI_F_POLICY_MC_DIST), run the float64 quintuple S | x0_dist | p_dist | sample_params | samples
-    (MI_F_POLICY_MC_RUN).  Means, spreads and goal: (k,) or (B, k); goal None: +inf everywhere (success = counted); params_mean None:
-    the parameters are not sampled (params_spread alone is refused; params_mean alone: spread zero).  ValueError - decided here, before
-    anything reaches the device - for any other shape, a NaN, a mean or spread that is not finite, a negative spread or goal, an S
-    that is no integer >= 1 or with first_sample + S > 2^32, an unknown distribution, parameters on a model without any."""
-    def rows_of(v, k, name, finite=True):
-        try:
-            a = np.asarray(v, dtype=np.float64)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"RolloutPolicyStats: {name} is not an array of numbers ({e})") from None
-        if a.shape == (k,):
-            a = np.broadcast_to(a, (B, k))
-        elif a.shape != (B, k):
-            raise ValueError(f"RolloutPolicyStats: {name} must be ({k},) or ({B}, {k}); got {a.shape}")
-        if np.isnan(a).any() or (finite and not np.isfinite(a).all()):
-            raise ValueError(f"RolloutPolicyStats: NaN{' or infinity' if finite else ''} in {name}")
-        return a
-
-    def nonneg(a, name):
-        if (a < 0.0).any():
-            raise ValueError(f"RolloutPolicyStats: negative entry in {name}")
-        return a
-
-    if isinstance(S, (bool, np.bool_)) or not isinstance(S, (int, np.integer)) or S < 1:
-        raise ValueError(f"RolloutPolicyStats: S must be an integer >= 1; got {S!r}")
-    if isinstance(first_sample, (bool, np.bool_)) or not isinstance(first_sample, (int, np.integer)) or not 0 <= first_sample < (1 << 32):
-        raise ValueError(f"RolloutPolicyStats: first_sample must be an integer in [0, 2^32); got {first_sample!r}")
-    if int(first_sample) + int(S) > (1 << 32):
-        raise ValueError(f"RolloutPolicyStats: first_sample + S must not exceed 2^32; got {int(first_sample)} + {int(S)}")
-    for name, d in (("x0_dist", x0_dist), ("params_dist", params_dist)):
-        if d not in MC_DISTS:
-            raise ValueError(f"RolloutPolicyStats: {name} must be 'normal' or 'uniform'; got {d!r}")
-    rows = np.zeros((B, 3 * n + 2 * n_params))
-    rows[:, :n] = rows_of(x0_mean, n, "x0_mean")
-    rows[:, n:2 * n] = nonneg(rows_of(x0_spread, n, "x0_spread"), "x0_spread")
-    rows[:, 2 * n:3 * n] = np.inf if goal is None else nonneg(rows_of(goal, n, "goal", finite=False), "goal")
-    sample_params = params_mean is not None
-    if params_spread is not None and not sample_params:
-        raise ValueError("RolloutPolicyStats: params_spread needs params_mean")
-    if sample_params:
-        if n_params == 0:
-            raise ValueError("RolloutPolicyStats: this model has no parameters")
-        rows[:, 3 * n:3 * n + n_params] = rows_of(params_mean, n_params, "params_mean")
-        if params_spread is not None:
-            rows[:, 3 * n + n_params:] = nonneg(rows_of(params_spread, n_params, "params_spread"), "params_spread")
-    run = np.array([int(S), MC_DISTS[x0_dist], MC_DISTS[params_dist], 1.0 if sample_params else 0.0, 1.0 if samples else 0.0], dtype=np.float64)
-    return rows, run
-
-
-class PolicySamples:
-    """The samples of a RolloutPolicyStats(..., samples=True) call: x0 (B, S, n), params (B, S, n_params) - None when the parameters
-    were not sampled -, cost (B, S) and steps (B, S) int32: what RolloutPolicy takes and returns for the same samples."""
-    __slots__ = ("x0", "params", "cost", "steps")
-
-    def __init__(self, x0, params, cost, steps):
-        self.x0, self.params, self.cost, self.steps = x0, params, cost, steps
-
-
-def check_mc_observe(envelope, controls, safe_box, B, n):
-    """RolloutPolicyStats' observing arguments -> (bits, box): bits the value of MI_F_POLICY_MC_OBSERVE (1 state envelopes, 2 control
-    envelopes), box None or the contiguous (B, 2 n) float64 rows lo | hi of MI_F_POLICY_MC_BOX.  safe_box: None or a pair (lo, hi),
-    each None - unbounded - or (n,) / (B, n) with +-inf for an unbounded component.  ValueError - decided here, before anything
-    reaches the device - for a flag that is no bool, a safe_box that is no pair, any other shape, a NaN, or lo > hi anywhere."""
-    for name, v in (("envelope", envelope), ("controls", controls)):
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError(f"RolloutPolicyStats: {name} must be True or False; got {v!r}")
-    bits = (_capi.MC_OBSERVE_X if envelope else 0) | (_capi.MC_OBSERVE_U if controls else 0)
-    if safe_box is None:
-        return bits, None
-    if not isinstance(safe_box, (tuple, list)) or len(safe_box) != 2:
-        raise ValueError("RolloutPolicyStats: safe_box must be a pair (lo, hi)")
-    box = np.empty((B, 2 * n))
-    for j, (name, v, dflt) in enumerate((("safe_box lo", safe_box[0], -np.inf), ("safe_box hi", safe_box[1], np.inf))):
-        if v is None:
-            box[:, j * n:(j + 1) * n] = dflt
-            continue
-        try:
-            a = np.asarray(v, dtype=np.float64)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"RolloutPolicyStats: {name} is not an array of numbers ({e})") from None
-        if a.shape != (n,) and a.shape != (B, n):
-            raise ValueError(f"RolloutPolicyStats: {name} must be ({n},) or ({B}, {n}); got {a.shape}")
-        if np.isnan(a).any():
-            raise ValueError(f"RolloutPolicyStats: NaN in {name}")
-        box[:, j * n:(j + 1) * n] = a
-    if (box[:, :n] > box[:, n:]).any():
-        raise ValueError("RolloutPolicyStats: safe_box has lo > hi")
-    return bits, box
-
-
-def check_seed_args(K, B, m, sigma_u=None, seed=0, round=0, hold=1, m_dev=None, what="PerturbInitialGuess"):   # noqa: A002
-    """The multi-start arguments -> (K, rows, seed, round, hold): K the group size as an int, rows None for sigma_u=None (SelectBest,
-    GatherBest) or the contiguous (B, m_dev) float64 sigma_u rows with zeros on the padding controls (m_dev: the device's number of
-    controls, default m); sigma_u: scalar, (m,) or (B, m).  ValueError - decided here, before anything reaches the library - for a K
-    that is no integer >= 1 or does not divide B, a hold that is no integer in [1, 2^31), a seed that is no integer in [0, 2^53), a
-    round that is no integer in [0, 2^32), any other shape of sigma_u and a negative, NaN or infinite entry in it."""
-    m_dev = m if m_dev is None else int(m_dev)
-
-    def integer(v, name, lo, end, rng):
-        ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer, float, np.floating))
-        if ok and isinstance(v, (float, np.floating)):
-            ok = bool(np.isfinite(v) and v == np.floor(v))
-        if not ok or not lo <= int(v) < end:
-            raise ValueError(f"{what}: {name} must be an integer in {rng}; got {v!r}")
-        return int(v)
-
-    K = integer(K, "K", 1, 1 << 31, "[1, 2^31)")
-    if B % K != 0:
-        raise ValueError(f"{what}: K must divide the batch: {B} problems are no whole number of groups of {K}")
-    seed = integer(seed, "seed", 0, 1 << 53, "[0, 2^53)")
-    round = integer(round, "round", 0, 1 << 32, "[0, 2^32)")   # noqa: A001
-    hold = integer(hold, "hold", 1, 1 << 31, "[1, 2^31)")
-    if sigma_u is None:
-        return K, None, seed, round, hold
-    try:
-        a = np.asarray(sigma_u, dtype=np.float64)
-    except (TypeError, ValueError) as e:
-        raise ValueError(f"{what}: sigma_u is not an array of numbers ({e})") from None
-    if a.shape not in ((), (m,), (B, m)):
-        raise ValueError(f"{what}: sigma_u must be a scalar, ({m},) or ({B}, {m}); got {a.shape}")
-    if not np.isfinite(a).all():
-        raise ValueError(f"{what}: NaN or infinity in sigma_u")
-    if (a < 0.0).any():
-        raise ValueError(f"{what}: negative entry in sigma_u (standard deviations)")
-    rows = np.zeros((B, m_dev))
-    rows[:, :m] = a
-    return K, rows, seed, round, hold
-
-
-def check_mppi_args(S, iterations, B, m, N, sigma_u, temperature, seed=0, first_sample=0, hold=1, shift=0, m_dev=None, what="MPPIRun"):
-    """The sampling-based MPC arguments -> (S, iterations, rows, temperature, seed, first_sample, hold, shift): the integers as ints,
-    rows the contiguous (B, m_dev) float64 sigma_u rows with zeros on the padding controls (sigma_u: scalar, (m,) or (B, m)).
-    ValueError - decided here, before anything reaches the library - for an S that is no integer in [1, 2^31 - 64], an iterations or hold that is no integer in [1, 2^31), a
-    seed that is no integer in [0, 2^53), a first_sample that is no integer in [0, 2^32), first_sample + iterations S > 2^32, a shift
-    that is no integer in [0, N - 2], a temperature that is no number >= 0 (NaN included), a missing sigma_u, any other shape of it
-    and a negative, NaN or infinite entry in it."""
-    def integer(v, name, lo, end, rng):
-        ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer, float, np.floating))
-        if ok and isinstance(v, (float, np.floating)):
-            ok = bool(np.isfinite(v) and v == np.floor(v))
-        if not ok or not lo <= int(v) < end:
-            raise ValueError(f"{what}: {name} must be an integer in {rng}; got {v!r}")
-        return int(v)
-
-    S = integer(S, "S", 1, (1 << 31) - 63, "[1, 2^31 - 64]")
-    iterations = integer(iterations, "iterations", 1, 1 << 31, "[1, 2^31)")
-    if sigma_u is None:
-        raise ValueError(f"{what}: sigma_u is required")
-    _, rows, seed, _, hold = check_seed_args(1, B, m, sigma_u, seed, 0, hold, m_dev, what)
-    first_sample = integer(first_sample, "first_sample", 0, 1 << 32, "[0, 2^32)")
-    if first_sample + iterations * S > 1 << 32:
-        raise ValueError(f"{what}: first_sample + iterations S must not exceed 2^32 (iteration i draws samples first_sample + i S ..)")
-    shift = integer(shift, "shift", 0, N - 1, f"[0, {N - 2}]")
-    ok = not isinstance(temperature, (bool, np.bool_)) and isinstance(temperature, (int, float, np.integer, np.floating))
-    if not ok or not temperature >= 0.0:
-        raise ValueError(f"{what}: temperature must be a number >= 0 (0: the best sample alone); got {temperature!r}")
-    return S, iterations, rows, float(temperature), seed, first_sample, hold, shift
-
-
-class MPPIResult:
-    """What MPPIRun did (include/mi_ilqr.h: "Sampling-based MPC"): u (B, m, N-1) the final nominal plans, unshifted; per iteration and
-    problem, (I, B): best_sample - the sample of least finite cost, -1 when none was finite -, best_cost (+inf then), finite - the
-    number of samples with a finite cost - and ess, the effective sample size 1 / sum w^2 (NaN without a finite sample);
-    nominal_cost (I + 1, B): the nominal's own cost at the start of every iteration and, row I, of the final nominal; kernel_ms: the
-    run's kernels, first to last."""
-    __slots__ = ("u", "best_sample", "best_cost", "finite", "ess", "nominal_cost", "kernel_ms")
-
-    def __init__(self, u, best_sample, best_cost, finite, ess, nominal_cost, kernel_ms):
-        self.u, self.best_sample, self.best_cost, self.finite = u, best_sample, best_cost, finite
-        self.ess, self.nominal_cost, self.kernel_ms = ess, nominal_cost, kernel_ms
-
-    @classmethod
-    def from_rows(cls, u, best, cost, kernel_ms):
-        """best (I, B, 3) and cost (I + 1, B, 2) as MI_F_SEEDS_BEST / MI_F_SEEDS_COST return them."""
-        return cls(u, best[:, :, 0].astype(np.int64), np.ascontiguousarray(best[:, :, 1]), best[:, :, 2].astype(np.int64),
-                   np.ascontiguousarray(cost[:-1, :, 1]), np.ascontiguousarray(cost[:, :, 0]), kernel_ms)
-
-    def __repr__(self):
-        return f"MPPIResult(iterations={self.best_cost.shape[0]}, nominal_cost[-1]={self.nominal_cost[-1].tolist()})"
-
-
-class SeedSelection:
-    """What SelectBest found in every group of K seeds (include/mi_ilqr.h: "Multi-start"), (G,) arrays: winner - the member index of
-    the eligible member of least cost, -1 when no member is eligible -, its cost (+inf then) and the number of eligible members."""
-    __slots__ = ("K", "winner", "cost", "eligible")
-
-    def __init__(self, K, winner, cost, eligible):
-        self.K, self.winner, self.cost, self.eligible = K, winner, cost, eligible
-
-    @classmethod
-    def from_rows(cls, K, rows):
-        return cls(int(K), rows[:, 0].astype(np.int64), np.ascontiguousarray(rows[:, 1]), rows[:, 2].astype(np.int64))
-
-    @property
-    def problem(self):
-        """(G,) the winners as problem numbers g K + winner; -1 for a group without a winner."""
-        g = np.arange(self.winner.size) * self.K
-        return np.where(self.winner >= 0, g + self.winner, -1)
-
-    def __repr__(self):
-        return f"SeedSelection(K={self.K}, winner={self.winner.tolist()}, eligible={self.eligible.tolist()})"
-
-
-def _chan(nA, meanA, m2A, nB, meanB, m2B):
-    """include/mi_ilqr.h's merge of (count, mean, M2), A the operand of the lower sample numbers; a count-0 side leaves the other's."""
-    fA, fB = nA.astype(np.float64), nB.astype(np.float64)
-    n = fA + fB
-    with np.errstate(invalid="ignore", divide="ignore"):
-        delta = meanB - meanA
-        mean = meanA + delta * (fB / n)
-        m2 = (m2A + m2B) + (delta * delta) * ((fA * fB) / n)
-    return (np.where(fB == 0, meanA, np.where(fA == 0, meanB, mean)), np.where(fB == 0, m2A, np.where(fA == 0, m2B, m2)))
-
-
-class PolicyEnvelope:
-    """Per-step statistics over the samples of a RolloutPolicyStats(..., envelope=True / controls=True) call, arrays (B, N, n) - for
-    the controls (B, N-1, m): count, the samples that held a finite value at that step (a sample that ended leaves its later
-    steps out); mean, m2 (the sum of squared deviations), min, max over those; argmin / argmax the global sample numbers of min /
-    max (-1 where count is 0, and there mean = m2 = NaN, min = +inf, max = -inf)."""
-    __slots__ = ("count", "mean", "m2", "min", "max", "argmin", "argmax")
-
-    def __init__(self, count, mean, m2, min, max, argmin, argmax):   # noqa: A002
-        self.count, self.mean, self.m2, self.min, self.max, self.argmin, self.argmax = count, mean, m2, min, max, argmin, argmax
-
-    @classmethod
-    def from_raw(cls, raw):
-        """raw (..., 8): the accumulators count | K | s1 | s2 | min | max | argmin | argmax of MI_F_POLICY_MC_ENVELOPE, finalised by
-        the header's formulas mean = K + s1 / count, M2 = max(0, s2 - s1 s1 / count)."""
-        cnt, K, s1, s2 = (raw[..., k] for k in range(4))
-        with np.errstate(invalid="ignore", divide="ignore"):
-            mean = K + s1 / cnt
-            m2 = np.maximum(0.0, s2 - s1 * s1 / cnt)
-        empty = cnt == 0
-        return cls(cnt.astype(np.int64), np.where(empty, np.nan, mean), np.where(empty, np.nan, m2), raw[..., 4].copy(), raw[..., 5].copy(),
-                   raw[..., 6].astype(np.int64), raw[..., 7].astype(np.int64))
-
-    @property
-    def var(self):
-        """The sample variance, m2 / (count - 1); NaN with fewer than two values."""
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(self.count > 1, self.m2 / (self.count - 1), np.nan)
-
-    def merge(self, other):
-        """The envelope of self's samples and those of a DISJOINT, LATER window (other): counts add, extrema by comparison with ties
-        to self - exact -, mean and m2 by Chan's merge - correct to round-off, not the bits of one call."""
-        mean, m2 = _chan(self.count, self.mean, self.m2, other.count, other.mean, other.m2)
-        lo, hi = other.min < self.min, other.max > self.max
-        return PolicyEnvelope(self.count + other.count, mean, m2, np.where(lo, other.min, self.min), np.where(hi, other.max, self.max),
-                              np.where(lo, other.argmin, self.argmin), np.where(hi, other.argmax, self.argmax))
-
-
-class PolicySafety:
-    """The safety box of a RolloutPolicyStats(..., safe_box=(lo, hi)) call: of n samples per problem `ran` held finite states at all
-    N steps, `safe` of those never left the box and `safe_success` of those also ended within `goal` of the target, (B,) each;
-    exits (B, N): the samples whose FIRST state outside the box is x_t (the box only observes: a sample goes on)."""
-    __slots__ = ("n", "ran", "safe", "safe_success", "exits")
-
-    def __init__(self, n, ran, safe, safe_success, exits):
-        self.n, self.ran, self.safe, self.safe_success, self.exits = n, ran, safe, safe_success, exits
-
-    @classmethod
-    def from_rows(cls, n, rows):
-        """rows: the (B, 3 + N) array of MI_F_POLICY_MC_SAFETY."""
-        r = rows.astype(np.int64)
-        return cls(np.asarray(n, dtype=np.int64), r[:, 0], r[:, 1], r[:, 2], r[:, 3:])
-
-    @property
-    def survival(self):
-        """(B, N): the share of the samples that have not left the box up to and including step t, 1 - cumsum(exits) / n."""
-        return 1.0 - np.cumsum(self.exits, axis=-1) / np.asarray(self.n)[..., None]
-
-    def merge(self, other):
-        """Integer counters: they add, exactly."""
-        return PolicySafety(self.n + other.n, self.ran + other.ran, self.safe + other.safe, self.safe_success + other.safe_success,
-                            self.exits + other.exits)
-
-
-class PolicyStats:
-    """What RolloutPolicyStats returns, (B,) arrays: n samples, of which `counted` ran to the end with a finite cost and `success`
-    also ended within `goal` of the target; mean, m2 (the sum of squared deviations), min, max over the counted samples; argmin /
-    argmax the global sample numbers of min / max (-1 without a counted sample); steps_total the steps of all n samples.
-    samples: None or a PolicySamples.  envelope, control_envelope: None or a PolicyEnvelope; safety: None or a PolicySafety."""
-    __slots__ = ("n", "counted", "success", "mean", "m2", "min", "max", "argmin", "argmax", "steps_total", "samples", "envelope",
-                 "control_envelope", "safety")
-
-    def __init__(self, n, counted, success, mean, m2, min, max, argmin, argmax, steps_total, samples=None, envelope=None,   # noqa: A002
-                 control_envelope=None, safety=None):
-        self.n, self.counted, self.success, self.mean, self.m2 = n, counted, success, mean, m2
-        self.min, self.max, self.argmin, self.argmax, self.steps_total, self.samples = min, max, argmin, argmax, steps_total, samples
-        self.envelope, self.control_envelope, self.safety = envelope, control_envelope, safety
-
-    @classmethod
-    def from_rows(cls, rows, samples=None):
-        """rows: the (B, 10) array of MI_F_POLICY_MC_STATS."""
-        i = lambda k: rows[:, k].astype(np.int64)   # noqa: E731
-        return cls(i(0), i(1), i(2), rows[:, 3].copy(), rows[:, 4].copy(), rows[:, 5].copy(), rows[:, 6].copy(), i(7), i(8), i(9), samples)
-
-    @property
-    def var(self):
-        """The sample variance of the counted costs, m2 / (counted - 1); NaN with fewer than two."""
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(self.counted > 1, self.m2 / (self.counted - 1), np.nan)
-
-    @property
-    def success_rate(self):
-        return self.success / self.n
-
-    def merge(self, other):
-        """Chan's merge with the result of a DISJOINT, LATER window of samples (first_sample): how a sample set split over calls or
-        ranks is put together.  self is operand A of include/mi_ilqr.h's merge; a side without a counted sample leaves the other's
-        numbers as they are; ties of min / max keep self's sample.  envelope, control_envelope and safety are joined too where both
-        sides hold them (else None): their counts, exits, extrema and argmin / argmax exactly, their mean / m2 correct to round-off
-        (Chan's merge of two finalised halves is not the one left fold's bits)."""
-        both = lambda k: None if getattr(self, k) is None or getattr(other, k) is None else getattr(self, k).merge(getattr(other, k))   # noqa: E731
-        nA, nB = self.counted.astype(np.float64), other.counted.astype(np.float64)
-        n = nA + nB
-        with np.errstate(invalid="ignore", divide="ignore"):
-            delta = other.mean - self.mean
-            mean = self.mean + delta * (nB / n)
-            m2 = (self.m2 + other.m2) + (delta * delta) * ((nA * nB) / n)
-        mean = np.where(nB == 0, self.mean, np.where(nA == 0, other.mean, mean))
-        m2 = np.where(nB == 0, self.m2, np.where(nA == 0, other.m2, m2))
-        lo, hi = other.min < self.min, other.max > self.max
-        return PolicyStats(self.n + other.n, self.counted + other.counted, self.success + other.success, mean, m2,
-                           np.where(lo, other.min, self.min), np.where(hi, other.max, self.max), np.where(lo, other.argmin, self.argmin),
-                           np.where(hi, other.argmax, self.argmax), self.steps_total + other.steps_total, None, both("envelope"),
-                           both("control_envelope"), both("safety"))
-
-
-class PlantLog:
-    """The closed loop's record (plant_log), K = num_resolves * replan_steps steps of the last MPCRun on a solver that holds a plant:
-    X (B, n, K+1) - the state at every step, the plant's current state last -, U (B, m, K) the commanded controls, stage_cost (B, K)
-    the l_k and steps (B,) the steps each plant completed in that run; NaN where a plant that ended did not get to (its X keeps
-    the state it stopped in, in column `steps` and - the current state - in the last one)."""
-    __slots__ = ("X", "U", "stage_cost", "steps")
-
-    def __init__(self, X, U, stage_cost, steps):
-        self.X, self.U, self.stage_cost, self.steps = X, U, stage_cost, steps
-
-    def _without_batch_axis(self):
-        return PlantLog(*(a[0] for a in (self.X, self.U, self.stage_cost, self.steps)))
-
-
-class PolicyRollout:
-    """What RolloutPolicy returns: cost, x_final, steps and - asked for - the trajectories X, U (else None)."""
-    __slots__ = ("cost", "x_final", "steps", "X", "U")
-
-    def __init__(self, cost, x_final, steps, X=None, U=None):
-        self.cost, self.x_final, self.steps, self.X, self.U = cost, x_final, steps, X, U
-
-    def _without_batch_axis(self):
-        return PolicyRollout(*(None if a is None else a[0] for a in (self.cost, self.x_final, self.steps, self.X, self.U)))
 
 
 class BatchedIterativeLQR:
@@ -700,8 +181,7 @@ class BatchedIterativeLQR:
                              "family")
         _capi.check(rc, "mi_ilqr_set")
         if rows is not None:               # (clearing the reference has reset the clock)
-            cl = np.array([float(c)])
-            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_REF_CLOCK, _capi.ptr(cl), cl.nbytes), "mi_ilqr_set")
+            self._send(_capi.F_REF_CLOCK, np.array([float(c)]))
         self._ref_T = 0 if rows is None else rows.shape[1]
 
     def _holds_plant(self):
@@ -714,38 +194,31 @@ class BatchedIterativeLQR:
         probe = np.empty((self.B, max(self._ref_T, 1), self.n))
         return self._lib.mi_ilqr_get(self._h, _capi.F_X_REF, _capi.ptr(probe), probe.nbytes) != _capi.E_BAD_ARG
 
+    def _refuse_tracking(self, who, why, when=True):
+        """ValueError "<who>: this solver holds a reference trajectory (SetTargetTrajectory)<why>" if it does (and `when`)."""
+        if self._tracking() and when:
+            raise ValueError(f"{who}: this solver holds a reference trajectory (SetTargetTrajectory){why}")
+
     @property
     def target_trajectory(self):
         """(B, T, n): the reference the solver holds (SetTargetTrajectory), or None."""
-        if not self._tracking():
-            return None
-        out = np.empty((self.B, self._ref_T, self.n))
-        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_X_REF, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
-        return out
+        return self._fetch(_capi.F_X_REF, (self.B, self._ref_T, self.n)) if self._tracking() else None
 
     @property
     def target_clock(self):
         """The row of the reference the next solve's window starts at (SetTargetTrajectory's clock, advanced by MPCRun); 0 without one."""
-        if not self._tracking():
-            return 0
-        out = np.empty(1)
-        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_REF_CLOCK, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
-        return int(out[0])
+        return int(self._fetch(_capi.F_REF_CLOCK, (1,))[0]) if self._tracking() else 0
 
     def SetModelParameters(self, params):
         """(B, n_params): every problem its own plant - the reference's one solver object per System, B of them in one handle
         (include/mi_ilqr.h: "Per-problem model parameters").  (n_params,): that row for every problem.  None: back to the
         parameters of the system the solver was built with.  Takes effect for the next solve; survives Reset()."""
-        rows = check_model_params(params, self.B, int(self.system.params.size))
-        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_MODEL_PARAMS, _capi.ptr(rows), 0 if rows is None else rows.nbytes),
-                    "mi_ilqr_set")
+        self._send(_capi.F_MODEL_PARAMS, check_model_params(params, self.B, int(self.system.params.size)))
 
     @property
     def model_params(self):
         """(B, n_params): the parameters each problem is solved with (the system's own row repeated unless SetModelParameters gave others)."""
-        out = np.empty((self.B, int(self.system.params.size)))
-        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_MODEL_PARAMS, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
-        return out
+        return self._fetch(_capi.F_MODEL_PARAMS, (self.B, int(self.system.params.size)))
 
     def SetRunningCost(self, Q, R):
         """(n, n) and (m, m): one pair for the batch (the reference's arguments).  (B, n, n) / (B, m, m): every problem its own
@@ -953,6 +426,18 @@ class BatchedIterativeLQR:
         arr = _capi.as_f64(arr, shape)
         _capi.check(self._lib.mi_ilqr_set(self._h, which, _capi.ptr(arr), arr.nbytes), "mi_ilqr_set")
 
+    def _send(self, which, a):
+        """A checked, contiguous array to a selector as it is; None: the selector's "no such rows" (no pointer, 0 bytes)."""
+        _capi.check(self._lib.mi_ilqr_set(self._h, which, _capi.ptr(a), 0 if a is None else a.nbytes), "mi_ilqr_set")
+
+    def _fetch(self, which, shape, dtype=np.float64):
+        """A selector into a fresh pageable array as the device holds it (the pinned pool and the cut of padding controls: _get);
+        any dtype but float64 goes through mi_ilqr_get_int."""
+        out = np.empty(shape, dtype=dtype)
+        entry = "mi_ilqr_get" if dtype is np.float64 else "mi_ilqr_get_int"
+        _capi.check(getattr(self._lib, entry)(self._h, which, _capi.ptr(out), out.nbytes), entry)
+        return out
+
     # state attributes with the reference's names (batched)
     x_bar = property(lambda s: s._get(_capi.F_X_BAR, (s.B, s.n, s.N)))
     u_bar = property(lambda s: s._get(_capi.F_U_BAR, (s.B, s.m, s.N - 1)))
@@ -998,8 +483,7 @@ class BatchedIterativeLQR:
         linearize the line search's first trial while it is rolled out), early rounds whose trial was accepted, candidate-group rounds
         (mid-size kernels: the helpers roll out line-search candidates 4 .. beside the leader's four) - (B,6) int64;
         zeros when the launch was not clustered (mi_ilqr.h: MI_I64_CLUSTER_WORDS)."""
-        w = np.empty((self.B, _capi.CLUSTER_WORDS), dtype=np.uint64)
-        _capi.check(self._lib.mi_ilqr_get_int(self._h, _capi.I64_CLUSTER_WORDS, _capi.ptr(w), w.nbytes), "mi_ilqr_get_int")
+        w = self._fetch(_capi.I64_CLUSTER_WORDS, (self.B, _capi.CLUSTER_WORDS), np.uint64)
         u = np.uint64
         ea_open, ea_hit, groups = w[:, 5] >> u(32), w[:, 5] & u(0xffffffff), w[:, 7]
         return np.stack([w[:, 2] & u(0xffff), (w[:, 3] >> u(32)) - ea_open - groups, (w[:, 3] >> u(8)) & u(0xffffff), ea_open, ea_hit, groups], axis=1).astype(np.int64)
@@ -1116,9 +600,7 @@ class BatchedIterativeLQR:
         On a solver that holds a plant (SetPlant) this is the CLOSED loop: before every re-solve the plant advances replan_steps
         steps under the policy of the previous solve, and the re-solve starts from the plant's state instead of the prediction
         x_bar[:, replan_steps] (include/mi_ilqr.h: "Closed-loop MPC"); `plant_log` has the plant's record."""
-        if self._tracking() and target_step is not None:
-            raise ValueError("MPCRun: this solver holds a reference trajectory (SetTargetTrajectory) - it is the reference that "
-                             "moves the target, replan_steps rows per re-solve; target_step must be None")
+        self._refuse_tracking("MPCRun", self._MOVES_THE_TARGET, target_step is not None)
         ts = None
         steps = None if target_step is None else np.asarray(target_step, dtype=np.float64)
         per_problem = self._per_problem_targets() or (steps is not None and steps.shape == (self.B, self.n) and steps.size != self.n)
@@ -1132,14 +614,22 @@ class BatchedIterativeLQR:
         stats = _capi.Stats()
         _capi.check(self._lib.mi_ilqr_mpc_run(self._h, int(num_resolves), int(replan_steps), _capi.ptr(ts), C.byref(stats)),
                     "mi_ilqr_mpc_run")
-        if per_problem:                # the targets as the loop left them (x_nom_b + step_b added num_resolves times)
-            out = np.empty((self.B, self.n))
-            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_X_NOM, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
-            self.x_nom = out
+        self._check_internal(self._mpc_done(num_resolves, replan_steps, per_problem, stats))
+        return stats
+
+    _MOVES_THE_TARGET = " - it is the reference that moves the target, replan_steps rows per re-solve; target_step must be None"
+    _CONSTANT_TARGET = ", and the policy kernels cost a rollout against a constant target only; SetTargetTrajectory(None) first"
+
+    def _mpc_done(self, num_resolves, replan_steps, per_problem, stats=None):
+        """What MPCRun and MPCRunMultiStart do behind the loop: read back the per-problem targets as it left them (x_nom_b + step_b
+        added num_resolves times), keep the statistics - None: the last re-solve's are collected - and the loop's sizes -> stats."""
+        if per_problem:
+            self.x_nom = self._fetch(_capi.F_X_NOM, (self.B, self.n))
+        if stats is None:
+            stats = _capi.Stats()
+            _capi.check(self._lib.mi_ilqr_collect_stats(self._h, C.byref(stats)), "mi_ilqr_collect_stats")
         self.stats = stats
-        self._mpc_resolves = int(num_resolves)
-        self._mpc_replan = int(replan_steps)
-        self._check_internal(stats)
+        self._mpc_resolves, self._mpc_replan = int(num_resolves), int(replan_steps)
         return stats
 
     @property
@@ -1201,9 +691,7 @@ class BatchedIterativeLQR:
         noisy = state_noise is not None or control_noise is not None
         rows, stream = check_noise_args(state_noise, control_noise, seed, first_sample, common_noise, self.B, self.n, self.m,
                                         self._md if noisy else None, x0.shape[1] if noisy else None)
-        if self._tracking():
-            raise ValueError("RolloutPolicy: this solver holds a reference trajectory (SetTargetTrajectory), and the policy kernels "
-                             "cost a rollout against a constant target only; SetTargetTrajectory(None) first")
+        self._refuse_tracking("RolloutPolicy", self._CONSTANT_TARGET)
         self._push_costs()
         self._set_policy_noise(rows, stream)
         B, S = self.B, x0.shape[1]
@@ -1218,13 +706,10 @@ class BatchedIterativeLQR:
 
     def _set_policy_noise(self, rows, stream):
         """The disturbances of the next policy launch: the stream always, the sigma rows or - None - their absence."""
-        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_STREAM, _capi.ptr(stream), stream.nbytes), "mi_ilqr_set")
-        if rows is not None:
-            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_NOISE, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
-            self._policy_noise_set = True
-        elif getattr(self, "_policy_noise_set", False):
-            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_NOISE, None, 0), "mi_ilqr_set")
-            self._policy_noise_set = False
+        self._send(_capi.F_POLICY_STREAM, stream)
+        if rows is not None or getattr(self, "_policy_noise_set", False):
+            self._send(_capi.F_POLICY_NOISE, rows)
+            self._policy_noise_set = rows is not None
 
     def RolloutPolicyStats(self, S, x0_mean, x0_spread, *, x0_dist="normal", params_mean=None, params_spread=None, params_dist="uniform",
                            goal=None, state_noise=None, control_noise=None, seed=0, first_sample=0, common_noise=False, samples=False,
@@ -1253,51 +738,35 @@ class BatchedIterativeLQR:
         noisy = state_noise is not None or control_noise is not None
         noise, stream = check_noise_args(state_noise, control_noise, seed, first_sample, common_noise, self.B, self.n, self.m,
                                          self._md if noisy else None, int(S))
-        if self._tracking():
-            raise ValueError("RolloutPolicyStats: this solver holds a reference trajectory (SetTargetTrajectory), and the policy kernels "
-                             "cost a rollout against a constant target only; SetTargetTrajectory(None) first")
+        self._refuse_tracking("RolloutPolicyStats", self._CONSTANT_TARGET)
         self._push_costs()
         self._set_policy_noise(noise, stream)
-        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_MC_DIST, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
-        before = np.empty(1)
-        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_OBSERVE, _capi.ptr(before), 8), "mi_ilqr_get")
-
-        def observe(v):
-            word = np.array([float(v)])
-            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_MC_OBSERVE, _capi.ptr(word), 8), "mi_ilqr_set")
-
-        set_box = lambda r: _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_MC_BOX, _capi.ptr(r), 0 if r is None else r.nbytes), "mi_ilqr_set")   # noqa: E731
+        self._send(_capi.F_POLICY_MC_DIST, rows)
+        before = self._fetch(_capi.F_POLICY_MC_OBSERVE, (1,))
         try:
             if before[0] != bits:
-                observe(bits)
+                self._send(_capi.F_POLICY_MC_OBSERVE, np.array([float(bits)]))
             if box is not None:
-                set_box(box)
-            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_POLICY_MC_RUN, _capi.ptr(run), run.nbytes), "mi_ilqr_set")
+                self._send(_capi.F_POLICY_MC_BOX, box)
+            self._send(_capi.F_POLICY_MC_RUN, run)
         finally:
             if before[0] != bits:
-                observe(before[0])
+                self._send(_capi.F_POLICY_MC_OBSERVE, np.array([float(before[0])]))
             if box is not None:
-                set_box(None)                                      # (this class leaves no box on the handle between calls)
-        out = np.empty((self.B, _capi.MC_FIELDS))
-        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_STATS, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+                self._send(_capi.F_POLICY_MC_BOX, None)             # (this class leaves no box on the handle between calls)
+        out = self._fetch(_capi.F_POLICY_MC_STATS, (self.B, _capi.MC_FIELDS))
         env = cenv = safety = None
         if envelope:
-            raw = np.empty((self.B, self.N, self.n, _capi.MC_ENV_FIELDS))
-            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_ENVELOPE, _capi.ptr(raw), raw.nbytes), "mi_ilqr_get")
-            env = PolicyEnvelope.from_raw(raw)
+            env = PolicyEnvelope.from_raw(self._fetch(_capi.F_POLICY_MC_ENVELOPE, (self.B, self.N, self.n, _capi.MC_ENV_FIELDS)))
         if controls:
-            raw = np.empty((self.B, self.N - 1, self._md, _capi.MC_ENV_FIELDS))
-            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_ENVELOPE_U, _capi.ptr(raw), raw.nbytes), "mi_ilqr_get")
+            raw = self._fetch(_capi.F_POLICY_MC_ENVELOPE_U, (self.B, self.N - 1, self._md, _capi.MC_ENV_FIELDS))
             cenv = PolicyEnvelope.from_raw(raw[:, :, :self.m])
         if box is not None:
-            raw = np.empty((self.B, 3 + self.N))
-            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_SAFETY, _capi.ptr(raw), raw.nbytes), "mi_ilqr_get")
-            safety = PolicySafety.from_rows(np.full(self.B, int(S), dtype=np.int64), raw)
+            safety = PolicySafety.from_rows(np.full(self.B, int(S), dtype=np.int64), self._fetch(_capi.F_POLICY_MC_SAFETY, (self.B, 3 + self.N)))
         smp = None
         if samples:
             n = self.n
-            raw = np.empty((self.B, int(S), n + n_params + 2))
-            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_MC_SAMPLES, _capi.ptr(raw), raw.nbytes), "mi_ilqr_get")
+            raw = self._fetch(_capi.F_POLICY_MC_SAMPLES, (self.B, int(S), n + n_params + 2))
             smp = PolicySamples(np.ascontiguousarray(raw[:, :, :n]),
                                 np.ascontiguousarray(raw[:, :, n:n + n_params]) if params_mean is not None else None,
                                 np.ascontiguousarray(raw[:, :, n + n_params]), raw[:, :, n + n_params + 1].astype(np.int32))
@@ -1316,77 +785,69 @@ class BatchedIterativeLQR:
         MPCRun advances (plant_clock).  Survives Reset(); ClearPlant() returns to the open loop."""
         x, params, noise, stream = check_plant_args(x, params, state_noise, control_noise, seed, common_noise, feedback, clock, self.B, self.n,
                                                     self.m, int(self.system.params.size), self._md)
-        if self._tracking():
-            raise ValueError("SetPlant: this solver holds a reference trajectory (SetTargetTrajectory), and the plant kernels know "
-                             "constant targets only; SetTargetTrajectory(None) first")
-        st = lambda which, a: _capi.check(self._lib.mi_ilqr_set(self._h, which, _capi.ptr(a), 0 if a is None else a.nbytes), "mi_ilqr_set")   # noqa: E731
+        self._refuse_tracking("SetPlant", ", and the plant kernels know constant targets only; SetTargetTrajectory(None) first")
         if int(self.system.params.size):
-            st(_capi.F_PLANT_PARAMS, params)
-        st(_capi.F_PLANT_NOISE, noise)
-        st(_capi.F_PLANT_STREAM, stream)
-        st(_capi.F_PLANT_STATE, x)
+            self._send(_capi.F_PLANT_PARAMS, params)
+        self._send(_capi.F_PLANT_NOISE, noise)
+        self._send(_capi.F_PLANT_STREAM, stream)
+        self._send(_capi.F_PLANT_STATE, x)
 
     def ClearPlant(self):
         """No plant: MPCRun is the open loop again, bitwise what it is on a solver that never had one."""
         for which in (_capi.F_PLANT_STATE, _capi.F_PLANT_NOISE) + ((_capi.F_PLANT_PARAMS,) if int(self.system.params.size) else ()):
-            _capi.check(self._lib.mi_ilqr_set(self._h, which, None, 0), "mi_ilqr_set")
-
-    def _plant_get(self, which, shape):
-        out = np.empty(shape)
-        _capi.check(self._lib.mi_ilqr_get(self._h, which, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
-        return out
+            self._send(which, None)
 
     @property
     def plant_state(self):
         """(B, n): the plants' current states."""
-        return self._plant_get(_capi.F_PLANT_STATE, (self.B, self.n))
+        return self._fetch(_capi.F_PLANT_STATE, (self.B, self.n))
 
     @property
     def plant_clock(self):
         """Plant steps taken so far (SetPlant's clock, advanced by every closed-loop MPCRun)."""
-        return int(self._plant_get(_capi.F_PLANT_STREAM, (4,))[1])
+        return int(self._fetch(_capi.F_PLANT_STREAM, (4,))[1])
 
     @property
     def plant_log(self):
         """The record of the last closed-loop MPCRun: a PlantLog."""
         K, n, md = self._mpc_resolves * self._mpc_replan, self.n, self._md
-        rows = self._plant_get(_capi.F_PLANT_LOG, (self.B, K, n + md + 1))
-        X = np.concatenate([np.moveaxis(rows[:, :, :n], 1, 2), self._plant_get(_capi.F_PLANT_STATE, (self.B, n))[:, :, None]], axis=2)
+        rows = self._fetch(_capi.F_PLANT_LOG, (self.B, K, n + md + 1))
+        X = np.concatenate([np.moveaxis(rows[:, :, :n], 1, 2), self._fetch(_capi.F_PLANT_STATE, (self.B, n))[:, :, None]], axis=2)
         U = np.ascontiguousarray(np.moveaxis(rows[:, :, n:n + self.m], 1, 2))
         steps = (~np.isnan(rows[:, :, n:n + self.m]).any(axis=2)).sum(axis=1).astype(np.int32)
         return PlantLog(X, U, np.ascontiguousarray(rows[:, :, n + md]), steps)
 
     def plant_kernel_ms(self):
         """Milliseconds of the plant kernels of the last closed-loop MPCRun, summed (HIP events of their own)."""
-        return float(self._plant_get(_capi.F_PLANT_KERNEL_MS, (1,))[0])
+        return float(self._fetch(_capi.F_PLANT_KERNEL_MS, (1,))[0])
 
     def policy_mc_passes(self):
         """Passes over windows of sample groups the last RolloutPolicyStats call took (1 unless the samples outgrew the window)."""
-        out = np.empty(1, dtype=np.int32)
-        _capi.check(self._lib.mi_ilqr_get_int(self._h, _capi.I_POLICY_MC_PASSES, _capi.ptr(out), 4), "mi_ilqr_get_int")
-        return int(out[0])
+        return int(self._fetch(_capi.I_POLICY_MC_PASSES, (1,), np.int32)[0])
 
     def policy_kernel_ms(self):
         """Milliseconds of the rollout kernel of the last RolloutPolicy call (HIP events of its own)."""
-        out = np.empty(1)
-        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_POLICY_KERNEL_MS, _capi.ptr(out), 8), "mi_ilqr_get")
-        return float(out[0])
+        return float(self._fetch(_capi.F_POLICY_KERNEL_MS, (1,))[0])
 
     # ------------------------------------------------------------- multi-start (include/mi_ilqr.h: "Multi-start")
-    def _seeds_run(self, op, K, rows=None, seed=0, round=0, hold=1):   # noqa: A002
+    def _seeds_command(self, rows, *command):
+        """The sigma_u rows - None: none are sent -, then the command vector to MI_F_SEEDS_RUN -> the library's answer to the command:
+        what it means is the caller's to say."""
         if rows is not None:
-            _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_SIGMA, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
-        v = np.array([K, op, seed, round, hold, 0], dtype=np.float64)
-        rc = self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_RUN, _capi.ptr(v), v.nbytes)
+            self._send(_capi.F_SEEDS_SIGMA, rows)
+        v = np.array(command, dtype=np.float64)
+        assert v.size in (_capi.SEEDS_RUN_DOUBLES, _capi.SEEDS_MPC_RUN_DOUBLES, _capi.SEEDS_MPPI_RUN_DOUBLES)
+        return self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_RUN, _capi.ptr(v), v.nbytes)
+
+    def _seeds_run(self, op, K, rows=None, seed=0, round=0, hold=1):   # noqa: A002
+        rc = self._seeds_command(rows, K, op, seed, round, hold, 0)
         if rc == _capi.E_UNSUPPORTED:
             raise ValueError("multi-start: a solver of at most 4 problems on the wave-per-problem kernels keeps its inputs in host "
                              "memory and has no seed groups to join; use a larger batch")
         _capi.check(rc, "mi_ilqr_set")
 
     def _seeds_best(self, K):
-        rows = np.empty((self.B // K, 3))
-        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_SEEDS_BEST, _capi.ptr(rows), rows.nbytes), "mi_ilqr_get")
-        return SeedSelection.from_rows(K, rows)
+        return SeedSelection.from_rows(K, self._fetch(_capi.F_SEEDS_BEST, (self.B // K, 3)))
 
     def PerturbInitialGuess(self, K, sigma_u, seed=0, round=0, hold=1):   # noqa: A002
         """Read the batch as B / K groups of K consecutive problems - the same problem under K guesses - and draw the guesses on
@@ -1425,17 +886,15 @@ class BatchedIterativeLQR:
         K = check_seed_args(K, self.B, self.m, what="GatherBest")[0]
         self._seeds_run(_capi.SEEDS_GATHER, K)
         G = self.B // K
-        x, u, c = np.empty((G, self.n, self.N)), np.empty((G, self._md, self.N - 1)), np.empty(G)
-        for which, out in ((_capi.F_SEEDS_X_BAR, x), (_capi.F_SEEDS_U_BAR, u), (_capi.F_SEEDS_COST, c)):
-            _capi.check(self._lib.mi_ilqr_get(self._h, which, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+        x, u, c = (self._fetch(which, shape) for which, shape in ((_capi.F_SEEDS_X_BAR, (G, self.n, self.N)),
+                                                                  (_capi.F_SEEDS_U_BAR, (G, self._md, self.N - 1)), (_capi.F_SEEDS_COST, (G,))))
         return x, np.ascontiguousarray(u[:, :self.m, :]), c, self._seeds_best(K)
 
     def SolveMultiStart(self, K, rounds, sigma_u, seed=0, hold=1, shrink=1.0):
         """Multi-start on the device: PerturbInitialGuess -> Solve -> (ReseedFromBest with sigma_u shrink^r at round r -> Solve)
         x (rounds - 1) -> GatherBest.  -> (x_bar (G, n, N), u_bar (G, m, N-1), cost (G,), selections): the winners of the last
         round and the SeedSelection of every round, the last one the gather's."""
-        if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, (int, np.integer)) or rounds < 1:
-            raise ValueError(f"SolveMultiStart: rounds must be an integer >= 1; got {rounds!r}")
+        rounds = integer(rounds, "SolveMultiStart", "rounds", 1, None, ">= 1", floats=False)
         if not (isinstance(shrink, (int, float, np.integer, np.floating)) and np.isfinite(shrink) and shrink >= 0.0):
             raise ValueError(f"SolveMultiStart: shrink must be a finite number >= 0; got {shrink!r}")
         sigma = check_seed_args(K, self.B, self.m, sigma_u, seed, 0, hold, self._md, "SolveMultiStart")[1]
@@ -1445,7 +904,7 @@ class BatchedIterativeLQR:
         selections = []
         self.PerturbInitialGuess(K, sigma, seed, 0, hold)
         self.Solve()
-        for r in range(1, int(rounds)):
+        for r in range(1, rounds):
             selections.append(self.ReseedFromBest(K, sigma * float(shrink) ** r, seed, r, hold))
             self.Solve()
         x, u, c, sel = self.GatherBest(K)
@@ -1469,23 +928,18 @@ class BatchedIterativeLQR:
         K, rows, seed, round, hold = check_seed_args(K, self.B, self.m, sigma_u, seed, round, hold, self._md, what)   # noqa: A001
         if rows is None:
             raise ValueError(f"{what}: sigma_u is required")
-        for name, v, lo, end in (("num_resolves", num_resolves, 1, 1 << 31), ("replan_steps", replan_steps, 1, self.N - 1)):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) < end:
-                raise ValueError(f"{what}: {name} must be an integer in [{lo}, {end}); got {v!r}")
-        if round + int(num_resolves) > 1 << 32:
+        num_resolves = integer(num_resolves, what, "num_resolves", 1, 1 << 31, f"in [1, {1 << 31})", floats=False)
+        replan_steps = integer(replan_steps, what, "replan_steps", 1, self.N - 1, f"in [1, {self.N - 1})", floats=False)
+        if round + num_resolves > 1 << 32:
             raise ValueError(f"{what}: round + num_resolves must not exceed 2^32 (re-solve r draws at round + r)")
-        if self._tracking() and target_step is not None:
-            raise ValueError(f"{what}: this solver holds a reference trajectory (SetTargetTrajectory) - it is the reference that "
-                             "moves the target, replan_steps rows per re-solve; target_step must be None")
+        self._refuse_tracking(what, self._MOVES_THE_TARGET, target_step is not None)
         steps = None if target_step is None else np.asarray(target_step, dtype=np.float64)
         if steps is not None and steps.shape not in ((self.n,), (self.B, self.n)):
             raise ValueError(f"{what}: target_step must be ({self.n},) or ({self.B}, {self.n}); got {steps.shape}")
         per_problem = self._per_problem_targets() or steps is not None
         if per_problem:                # the long form carries no shared step: every problem's target moves by its own row
             self._set_field(_capi.F_TARGET_STEP, np.zeros((self.B, self.n)) if steps is None else np.broadcast_to(steps, (self.B, self.n)))
-        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_SIGMA, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
-        v = np.array([K, _capi.SEEDS_RESEED, seed, round, hold, 0, int(num_resolves), int(replan_steps)], dtype=np.float64)
-        rc = self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_RUN, _capi.ptr(v), v.nbytes)
+        rc = self._seeds_command(rows, K, _capi.SEEDS_RESEED, seed, round, hold, 0, num_resolves, replan_steps)
         if rc == _capi.E_UNSUPPORTED:
             raise ValueError(f"{what}: not on this solver - at most 4 problems on the wave-per-problem kernels keep their inputs in "
                              "host memory and have no seed groups to join")
@@ -1493,20 +947,9 @@ class BatchedIterativeLQR:
             raise ValueError(f"{what}: the solver holds no solve to select on (Solve() first; a reseed or a Reset() since then leaves "
                              "none), or the reference's clock would pass its end")
         _capi.check(rc, "mi_ilqr_set")
-        if per_problem:                # the targets as the loop left them
-            out = np.empty((self.B, self.n))
-            _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_X_NOM, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
-            self.x_nom = out
-        stats = _capi.Stats()
-        _capi.check(self._lib.mi_ilqr_collect_stats(self._h, C.byref(stats)), "mi_ilqr_collect_stats")
-        self.stats = stats
-        self._mpc_resolves = int(num_resolves)
-        self._mpc_replan = int(replan_steps)
-        self._check_internal(stats)
-        G = self.B // K
-        log = np.empty((int(num_resolves) + 1, G, 3))
-        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_SEEDS_BEST, _capi.ptr(log), log.nbytes), "mi_ilqr_get")
-        return [SeedSelection.from_rows(K, log[r]) for r in range(int(num_resolves) + 1)]
+        self._check_internal(self._mpc_done(num_resolves, replan_steps, per_problem))
+        log = self._fetch(_capi.F_SEEDS_BEST, (num_resolves + 1, self.B // K, 3))
+        return [SeedSelection.from_rows(K, log[r]) for r in range(num_resolves + 1)]
 
     def mpc_winner_log(self, selections):
         """(G, R, n + 2): for re-solve r the `mpc_log` row x0 | cost | iterations of the member that selection r + 1 names - the
@@ -1535,25 +978,19 @@ class BatchedIterativeLQR:
         S, iterations, rows, temperature, seed, first_sample, hold, shift = check_mppi_args(
             S, iterations, self.B, self.m, self.N, sigma_u, temperature, seed, first_sample, hold, shift, self._md)
         self._push_problem()                                   # (x0, costs, targets; a guess given to SetInitialGuess is the nominal)
-        _capi.check(self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_SIGMA, _capi.ptr(rows), rows.nbytes), "mi_ilqr_set")
-        v = np.array([S, _capi.SEEDS_RESEED, seed, first_sample, hold, 0, iterations, shift, temperature, 0], dtype=np.float64)
-        assert v.size == _capi.SEEDS_MPPI_RUN_DOUBLES
-        rc = self._lib.mi_ilqr_set(self._h, _capi.F_SEEDS_RUN, _capi.ptr(v), v.nbytes)
+        rc = self._seeds_command(rows, S, _capi.SEEDS_RESEED, seed, first_sample, hold, 0, iterations, shift, temperature, 0)
         if rc == _capi.E_UNSUPPORTED:
             raise ValueError("MPPIRun: not on this solver - it holds a reference trajectory (SetTargetTrajectory), or it has at most 4 "
                              "problems on the wave-per-problem kernels, which keep their inputs in host memory; use a larger batch")
         _capi.check(rc, "mi_ilqr_set")
-        best, cost = np.empty((iterations, self.B, 3)), np.empty((iterations + 1, self.B, 2))
-        u = np.empty((self.B, self._md, self.N - 1))
-        for which, out in ((_capi.F_SEEDS_BEST, best), (_capi.F_SEEDS_COST, cost), (_capi.F_SEEDS_U_BAR, u)):
-            _capi.check(self._lib.mi_ilqr_get(self._h, which, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
+        best = self._fetch(_capi.F_SEEDS_BEST, (iterations, self.B, 3))
+        cost = self._fetch(_capi.F_SEEDS_COST, (iterations + 1, self.B, 2))
+        u = self._fetch(_capi.F_SEEDS_U_BAR, (self.B, self._md, self.N - 1))
         return MPPIResult.from_rows(np.ascontiguousarray(u[:, :self.m, :]), best, cost, self.seeds_kernel_ms())
 
     def seeds_kernel_ms(self):
         """Milliseconds of the kernel of the last multi-start command (HIP events of its own)."""
-        out = np.empty(1)
-        _capi.check(self._lib.mi_ilqr_get(self._h, _capi.F_SEEDS_KERNEL_MS, _capi.ptr(out), 8), "mi_ilqr_get")
-        return float(out[0])
+        return float(self._fetch(_capi.F_SEEDS_KERNEL_MS, (1,))[0])
 
     # ------------------------------------------------------------- multi-GPU helper
     def best_cost_allreduce(self):
@@ -1602,12 +1039,6 @@ class IterativeLinearQuadraticRegulator(BatchedIterativeLQR):
         assert u_guess.shape == (self.m, self.N - 1)          # ilqr.py:155
         self._u_guess = u_guess
 
-    def _log_rows(self, which, rows):
-        """The leading `rows` rows of a per-iteration record of the last solve (mi_ilqr.h: partial reads of MI_F_HIST / MI_F_ITER_CYCLES)."""
-        out = np.empty((rows, 4), dtype=np.float64)
-        _capi.check(self._lib.mi_ilqr_get(self._h, which, _capi.ptr(out), out.nbytes), "mi_ilqr_get")
-        return out
-
     x_bar = property(lambda s: s._get(_capi.F_X_BAR, (s.n, s.N)))
     u_bar = property(lambda s: s._get(_capi.F_U_BAR, (s.m, s.N - 1)))
     K = property(lambda s: s._get(_capi.F_K, (s.m, s.n, s.N - 1)))
@@ -1637,7 +1068,8 @@ class IterativeLinearQuadraticRegulator(BatchedIterativeLQR):
             self.stats = stats
             iters, status = int(self.iterations[0]), int(self.status[0])
             r0 = max(1, min(iters, self.hist_cap))
-            hist, iter_cyc = self._log_rows(_capi.F_HIST, r0), self._log_rows(_capi.F_ITER_CYCLES, r0)
+            # (the leading rows of the per-iteration records: mi_ilqr.h, partial reads of MI_F_HIST / MI_F_ITER_CYCLES)
+            hist, iter_cyc = self._fetch(_capi.F_HIST, (r0, 4)), self._fetch(_capi.F_ITER_CYCLES, (r0, 4))
             loop_cycles = float(self.stage_cycles[0, 3])
         total_time = time.time() - st
         self.solve_wall_s = total_time
@@ -1646,7 +1078,7 @@ class IterativeLinearQuadraticRegulator(BatchedIterativeLQR):
         sec_per_cycle = stats.kernel_ms * 1e-3 / max(loop_cycles, 1.0)
         rows = min(iters, self.hist_cap)
         if rows > len(hist):                                          # a long solve: the rest of the log (the reference prints every row, ilqr.py:704)
-            hist, iter_cyc = self._log_rows(_capi.F_HIST, rows), self._log_rows(_capi.F_ITER_CYCLES, rows)
+            hist, iter_cyc = self._fetch(_capi.F_HIST, (rows, 4)), self._fetch(_capi.F_ITER_CYCLES, (rows, 4))
         t_iter = iter_cyc[:rows] * sec_per_cycle                      # columns: fp (line search), derivs, bp, iteration
         if rows:                                                      # like the reference: the LAST iteration's stopwatches
             self.time_fp, self.time_getDerivs, self.time_backwardsPass = (float(v) for v in t_iter[-1, :3])

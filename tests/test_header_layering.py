@@ -1,7 +1,8 @@
 """The layering of the native headers (drake_ddp_amd/csrc/*.hpp; DESIGN.md, "Source layout"): every header compiles as the only
 include of a translation unit, and the `#include "..."` lines keep the kernel families apart - no family header includes
 another, the host (host.hpp, host_internal.hpp and every host unit) includes none of them, policy_rollout.hpp names what it uses.  Compile-only
-(-fsyntax-only) and text checks: needs hipcc, no GPU."""
+(-fsyntax-only) and text checks: needs hipcc, no GPU.  At the end, the same for the Python front end: which module of
+drake_ddp_amd/{argcheck, results, ilqr}.py may import which."""
 import os
 import re
 import subprocess
@@ -111,3 +112,47 @@ def test_the_communicator_alone_includes_rccl_and_dlfcn():
 def test_each_launch_header_serves_one_family():
     for launch, family in (("launch_small.hpp", "ilqr_small.hpp"), ("launch_large.hpp", "ilqr_large.hpp"), ("launch_batch.hpp", "ilqr_batch.hpp")):
         assert set(includes(launch)) & FAMILY == {family}, (launch, includes(launch))
+
+
+# ---------------------------------------------------------------- the Python front end ("The Python side")
+PACKAGE = os.path.join(ROOT, "drake_ddp_amd")
+MOVED = ("check_model_params", "check_target_trajectory", "check_rollout_args", "check_noise_args", "check_plant_args", "check_mc_args",
+         "check_mc_observe", "check_seed_args", "check_mppi_args", "MC_DISTS", "PolicySamples", "MPPIResult", "SeedSelection",
+         "PolicyEnvelope", "PolicySafety", "PolicyStats", "PlantLog", "PolicyRollout", "_chan")
+
+
+def python_imports(module):
+    """-> (modules imported from outside the package, names imported from the package) by drake_ddp_amd/<module>.py, anywhere in it."""
+    import ast
+    with open(os.path.join(PACKAGE, module + ".py")) as f:
+        tree = ast.parse(f.read())
+    outside, inside = set(), set()
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Import):
+            outside |= {a.name.split(".")[0] for a in node.names}
+        elif isinstance(node, ast.ImportFrom) and node.level == 0:
+            (inside if node.module.split(".")[0] == "drake_ddp_amd" else outside).add(node.module)
+        elif isinstance(node, ast.ImportFrom):
+            inside |= {node.module} if node.module else {a.name for a in node.names}
+    return outside, inside
+
+
+def test_results_and_argcheck_need_neither_the_library_nor_ctypes():
+    assert python_imports("results") == ({"numpy"}, set())
+    assert python_imports("argcheck") == ({"numpy"}, {"_capi"})
+    with open(os.path.join(PACKAGE, "argcheck.py")) as f:
+        assert "load(" not in f.read()
+    child = ("import sys; import drake_ddp_amd.argcheck, drake_ddp_amd.results; from drake_ddp_amd import _capi; "
+             "assert _capi._lib is None; assert 'drake_ddp_amd.ilqr' not in sys.modules")
+    r = subprocess.run([sys.executable, "-c", child], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout[-2000:]
+
+
+def test_ilqr_hands_on_every_name_that_moved():
+    from drake_ddp_amd import argcheck, ilqr, results
+    for name in MOVED:
+        home = argcheck if name.startswith("check_") or name == "MC_DISTS" else results
+        assert getattr(ilqr, name) is getattr(home, name), name
+    for name in ("shard_range", "allreduce_min", "allreduce_min_async", "_PinnedBlock", "BatchedIterativeLQR", "IterativeLinearQuadraticRegulator"):
+        assert hasattr(ilqr, name), name
+    assert {"argcheck", "results"} <= python_imports("ilqr")[1]
