@@ -196,6 +196,7 @@ extern "C" {
 
 int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }      // (solve slots: what follows reads the current one, on its stream)
   if (const int rc = get_plant_field(h, which, dst, bytes); rc != kNotPlantField) return rc;
   if (const int rc = get_seeds_field(h, which, dst, bytes); rc != kNotSeedsField) return rc;      // (the last command's results, host copies)
   if (const RowField r = row_field(h, which); r.store) return store_read(h, *r.store, r.shared_row, dst, bytes);   // (host mirrors)
@@ -250,6 +251,7 @@ int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
 
 int mi_ilqr_get_async(mi_ilqr_t* h, int which, void* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   if (const int rc = get_plant_field(h, which, static_cast<double*>(dst), bytes); rc != kNotPlantField) return rc;   // (done when the call returns)
   if (const RowField r = row_field(h, which); r.store) {       // (host mirrors: the copy is done when the call returns)
     if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) {
@@ -276,6 +278,7 @@ int mi_ilqr_get_async(mi_ilqr_t* h, int which, void* dst, size_t bytes) {
 
 int mi_ilqr_get_int(mi_ilqr_t* h, int which, int32_t* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   if (which == MI_I64_CLUSTER_WORDS && (!h->cluster_sync || !h->last_clustered)) {
     // the header's promise: zeros when the last solve / MPC launch was not clustered (the device words would be an older launch's),
     // and for handles of the other kernel families, which have no such words
@@ -302,6 +305,7 @@ int mi_ilqr_get_int(mi_ilqr_t* h, int which, int32_t* dst, size_t bytes) {
 
 int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
   if (!h) return MI_ILQR_E_BAD_ARG;
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }      // (uploads and commands alike: on the current solve slot's stream, behind both)
   switch (which) {       // the selectors with rules of their own for src: most take src == NULL with bytes == 0 (back to shared mode / none)
     case MI_F_MODEL_PARAMS: return set_param_rows(h, h->params, src, bytes);
     case MI_F_COST_MATRICES: return set_cost_rows(h, src, bytes);
@@ -329,6 +333,7 @@ int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
   if (!f.ptr || f.is_int) return MI_ILQR_E_BAD_ARG;
   if (bytes != f.bytes) return MI_ILQR_E_BAD_SHAPE;
   HIPCHK(hipSetDevice(h->d.device_id));
+  if (which == MI_F_X0) inputs_touched(h);
   if (is_state_field(which)) { int rc = materialize_zero_state(h); if (rc != MI_ILQR_OK) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
   int rows = 0, len = 0;
@@ -347,6 +352,10 @@ int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
 
 int mi_ilqr_device_ptr(mi_ilqr_t* h, int which, void** ptr, size_t* bytes) {
   if (!h || !ptr) return MI_ILQR_E_BAD_ARG;
+  // the state fields and x0 are those of the current solve slot (the solve enqueued last): ordered on its stream behind both, and
+  // x0 possibly written through the pointer
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
+  if (which == MI_F_X0) inputs_touched(h);
   if (const RowStore* s = row_field(h, which).store) {         // per-problem mode only: the (B, width) device rows
     if (!s->synced) return MI_ILQR_E_BAD_ARG;
     *ptr = s->rows;

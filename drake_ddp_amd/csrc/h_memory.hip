@@ -196,17 +196,17 @@ int stage_h2d(mi_ilqr* h, void* dst, const void* src, size_t bytes) {
   }
   if (!h->pin_in) {
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->pin_in), 4 * kSmall, hipHostMallocDefault));
-    HIPCHK(hipEventCreateWithFlags(&h->pin_ev, hipEventDisableTiming));
+    for (hipEvent_t& e : h->pin_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     h->pin_off = 0;
   }
   if (h->pin_off + bytes > 4 * kSmall) {          // the block is used as a ring; wrap once the copies in flight are done
-    HIPCHK(hipEventSynchronize(h->pin_ev));
+    for (hipEvent_t e : h->pin_ev) HIPCHK(hipEventSynchronize(e));      // (on either solve slot's stream; never recorded: done)
     h->pin_off = 0;
   }
   char* stage = h->pin_in + h->pin_off;
   std::memcpy(stage, src, bytes);
   HIPCHK(hipMemcpyAsync(dst, stage, bytes, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipEventRecord(h->pin_ev, h->stream));
+  HIPCHK(hipEventRecord(h->pin_ev[h->stream == h->slots[1].stream ? 1 : 0], h->stream));
   h->pin_off += (bytes + 255) & ~(size_t)255;
   return MI_ILQR_OK;
 }

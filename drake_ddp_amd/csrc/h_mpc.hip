@@ -385,6 +385,8 @@ int mi_ilqr_mpc_shift(mi_ilqr_t* h, int32_t replan_steps) {
   if (!h) return MI_ILQR_E_BAD_ARG;
   if (replan_steps < 1 || replan_steps >= h->N - 1) return MI_ILQR_E_BAD_ARG;
   HIPCHK(hipSetDevice(h->d.device_id));
+  const SlotHold hold(h);            // (solve slots: joined, and every launch below stays on the current one)
+  if (hold.rc != MI_ILQR_OK) return hold.rc;
   int rc;
   if ((rc = materialize_zero_state(h)) != MI_ILQR_OK) return rc;
   if ((rc = materialize_u(h)) != MI_ILQR_OK) return rc;
@@ -405,6 +407,8 @@ int mi_ilqr_mpc_shift(mi_ilqr_t* h, int32_t replan_steps) {
 int mi_ilqr_mpc_run(mi_ilqr_t* h, int32_t num_resolves, int32_t replan_steps, const double* target_step, mi_ilqr_stats* stats) {
   if (!h) return MI_ILQR_E_BAD_ARG;
   if (num_resolves < 1 || replan_steps < 1 || replan_steps >= h->N - 1) return MI_ILQR_E_BAD_ARG;
+  const SlotHold hold(h);            // (solve slots: joined, and every launch below stays on the current one)
+  if (hold.rc != MI_ILQR_OK) return hold.rc;
   if (h->targets.synced && target_step) return MI_ILQR_E_BAD_ARG;   // the steps are the field MI_F_TARGET_STEP then
   const bool tracking = h->reference.synced;     // a reference trajectory: the window moves, replan_steps rows per re-solve
   if (tracking && target_step) return MI_ILQR_E_BAD_ARG;
@@ -508,6 +512,7 @@ int mi_ilqr_get_mpc_log(mi_ilqr_t* h, double* dst, size_t bytes) {
   if (!h || !dst || !h->mpc_log) return MI_ILQR_E_BAD_ARG;
   if (bytes != (size_t)h->B * h->mpc_resolves * (h->n + 2) * 8) return MI_ILQR_E_BAD_SHAPE;
   HIPCHK(hipSetDevice(h->d.device_id));
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(dst, h->mpc_log, bytes, hipMemcpyDeviceToHost));
   return MI_ILQR_OK;

@@ -328,6 +328,7 @@ int run_policy_mc(mi_ilqr* h, const double* v, size_t bytes) {
 extern "C" int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const double* params, double* cost, double* x_final,
                                       int32_t* steps, double* X, double* U) {
   if (!h || S < 1 || !x0 || !cost) return MI_ILQR_E_BAD_ARG;
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   const Model* model = model_of(h->d.model_id);
   const size_t B = h->B, n = h->n, m = h->m, N = h->N, np = model->p.n_params, Sz = (size_t)S, W = n + m + m * n;
   // (the unsupported calls before the bad arguments, as ever: a refused call gets the code it always got)

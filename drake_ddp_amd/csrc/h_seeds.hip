@@ -65,6 +65,8 @@ int set_seeds_sigma(mi_ilqr* h, const double* src, size_t bytes) {
 // MI_F_SEEDS_RUN.  The kernel runs on the handle's stream behind whatever is enqueued there, the call synchronizes once.  A refused
 // command changes nothing; a select or gather leaves the solver's state alone.
 int run_seeds(mi_ilqr* h, const double* v, size_t bytes) {
+  const SlotHold hold(h);            // (solve slots: joined, and every launch below stays on the current one)
+  if (hold.rc != MI_ILQR_OK) return hold.rc;
   if (bytes == 10 * 8) return run_mppi(h, v);                     // the sampling form: h_mppi.hip, the results kept behind the same selectors
   SeedsRun r;
   int rc = seeds_validate(h, v, bytes, r);

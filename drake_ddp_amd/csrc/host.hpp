@@ -32,10 +32,45 @@ struct RowStore {
   bool synced = false;
 };
 
+// A solve slot ("Solve slots"): one set of the arrays a MODE_SOLVE launch of the wave-per-problem kernels writes, and
+// the stream it runs on.  Slot 0 is what mi_ilqr_create allocates; slot 1 is allocated by the first cold pipelined solve that has a
+// solve in flight to overlap with (mi_ilqr.hip: ensure_second_slot).
+struct SolveSlot {
+  double *x_bar = nullptr, *u_bar = nullptr, *K = nullptr, *kappa = nullptr, *dV = nullptr, *fx = nullptr, *fu = nullptr;
+  double *hist = nullptr, *iter_cyc = nullptr, *s2 = nullptr;
+  long long* prof = nullptr;
+  int32_t *kp_count = nullptr, *kp_list = nullptr, *done_counter = nullptr;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev = nullptr;         // "everything enqueued on this slot's stream so far" for the other stream to wait on
+};
+
+// The two device copies of an input of mi_ilqr_set_initial (x0, u_guess): copy i is what a solve on slot i reads.  `version` says
+// which writes a copy holds (-1: nothing to vouch for), `latest` the copy written last - what the handle's x0 / u_guess alias.
+struct InputCopies {
+  double* copy[2] = {nullptr, nullptr};
+  long long version[2] = {0, -1};
+  long long writes = 0;
+  int latest = 0;
+  bool read_across[2] = {false, false};   // copy i was read by a device copy on the OTHER slot's stream since it was written
+};
+
 struct mi_ilqr {
   mi_ilqr_desc d;
   int n, m, N, B;
+  // the stream of the CURRENT solve slot (slots[solve_slot].stream): what every entry point but a pipelined cold solve works on
   hipStream_t stream = nullptr;
+  // Solve slots.  The state fields below (x_bar .. fu, hist, iter_cyc, prof, kp_count, kp_list, done_counter, s2) and `stream`
+  // alias the current slot (select_solve_slot), like ev0 .. ls_trials alias the current ring slot.
+  SolveSlot slots[2];
+  int n_slots = 1;                 // MI_ILQR_SOLVE_SLOTS (1: the single-slot behaviour), 2 for the wave-per-problem family
+  int solve_slot = 0;              // the current slot: that of the solve enqueued last
+  bool second_slot_ready = false;
+  bool other_pending = false;      // the other slot's stream holds work the current stream is not ordered behind
+  bool fork_needed = true;         // the current stream may hold work the other stream is not ordered behind
+  int hold = 0;                    // > 0: inside an entry point whose launches all stay on the current slot (SlotHold)
+  int inflight = 0;                // solves enqueued since the host last waited for the handle
+  InputCopies in_x0, in_u;
+  double* u_one_copy[2] = {nullptr, nullptr};   // device copies of a shared (m, N-1) initial guess, one per slot's stream
   // Per-launch records (kernel start/stop events + aggregate statistics) live in a ring, so that up to
   // kStatsRing solves can be enqueued back to back (mi_ilqr_solve_async) before anything is collected;
   // ev0/ev1/h_stats/d_stats alias the slot of the most recent launch.
@@ -64,10 +99,9 @@ struct mi_ilqr {
   int32_t *iters_ring = nullptr, *status_ring = nullptr, *ls_ring = nullptr;
   long long stats_done = 0;      // solves with sequence number < stats_done have their DevStats record
   bool in_async_solve = false;
-  double* u_one = nullptr;         // device copy of a shared (m, N-1) initial guess
   char* pin_in = nullptr;          // page-locked staging ring of small host -> device inputs (stage_h2d)
   size_t pin_off = 0;
-  hipEvent_t pin_ev = nullptr;
+  hipEvent_t pin_ev[2] = {nullptr, nullptr};   // the last staged copy on each solve slot's stream
   long long* prof = nullptr;
   int32_t* done_counter = nullptr;   // wave-per-problem kernels: tickets of the in-kernel statistics epilogue
   mi::DevStats* h_stats = nullptr;   // pinned host memory, device-mapped
@@ -201,6 +235,7 @@ struct Switches {
   int early;             // MI_ILQR_EARLY: early linearization by the helpers (default 1)
   int ls_groups;         // MI_ILQR_LS_GROUPS: candidate groups (default 1)
   int mc_pass_groups;    // MI_ILQR_MC_PASS_GROUPS: groups of 64 samples per pass of the on-device Monte-Carlo, forced when > 0 (tests)
+  int solve_slots;       // MI_ILQR_SOLVE_SLOTS: 1 = pipelined cold solves run one at a time on one stream (default 2: DESIGN.md 6)
 };
 MI_INTERNAL inline const Switches& switches() {
   static const Switches s = [] {
@@ -211,7 +246,7 @@ MI_INTERNAL inline const Switches& switches() {
     return Switches{on("MI_ILQR_NO_HELPER"), on("MI_ILQR_SEQ_BACKWARD"), on("MI_ILQR_SEQ_ROLLOUT"),
                     !stats ? -1 : (stats[0] == '1' ? 1 : 0), (spec >= 0 && spec <= 2) ? spec : 0, num("MI_ILQR_CLUSTER", 0),
                     num("MI_ILQR_CLUSTER_ORDER", 2), num("MI_ILQR_EARLY", 1), num("MI_ILQR_LS_GROUPS", 1),
-                    num("MI_ILQR_MC_PASS_GROUPS", 0)};
+                    num("MI_ILQR_MC_PASS_GROUPS", 0), num("MI_ILQR_SOLVE_SLOTS", 2) == 1 ? 1 : 2};
   }();
   return s;
 }
@@ -232,6 +267,16 @@ static inline void select_stats_slot(mi_ilqr* h, int slot) {
   h->cur_slot = slot;
   const size_t o = (size_t)slot * h->B;
   h->cost = h->cost_ring + o; h->iters = h->iters_ring + o; h->status = h->status_ring + o; h->ls_trials = h->ls_ring + o;
+}
+
+// The state fields and the stream alias solve slot `slot` from here on; the inputs alias their latest copies.
+static inline void select_solve_slot(mi_ilqr* h, int slot) {
+  const SolveSlot& s = h->slots[slot];
+  h->x_bar = s.x_bar; h->u_bar = s.u_bar; h->K = s.K; h->kappa = s.kappa; h->dV = s.dV; h->fx = s.fx; h->fu = s.fu;
+  h->hist = s.hist; h->iter_cyc = s.iter_cyc; h->s2 = s.s2; h->prof = s.prof; h->kp_count = s.kp_count; h->kp_list = s.kp_list;
+  h->done_counter = s.done_counter;
+  h->stream = s.stream;
+  h->solve_slot = slot;
 }
 
 namespace mi_host {

@@ -32,6 +32,32 @@ MI_INTERNAL int materialize_u(mi_ilqr* h);
 MI_INTERNAL int reduce_stats(mi_ilqr* h, int first_slot, int count);     // DevStats records of `count` ring slots: one launch
 MI_INTERNAL int set_cost_rows(mi_ilqr* h, const double* src, size_t bytes);   // MI_F_COST_MATRICES (classified like mi_ilqr_set_cost's)
 
+// Solve slots (host.hpp: SolveSlot).  Only mi_ilqr_solve_async puts a launch on the other slot, and only a cold
+// MODE_SOLVE launch of the wave-per-problem kernels; only mi_ilqr_set_initial(_shared) writes on the other slot's stream.  Every
+// other entry point that reads or writes solver state, or hands out a pointer or the stream, calls join_slots first: the current
+// slot's stream then waits - on the device, never the host - for what the other slot's stream still holds, and the entry point
+// works on the current slot as if there were one.  Two flag tests when there is nothing to join.
+MI_INTERNAL int join_slots_now(mi_ilqr* h);
+MI_INTERNAL inline int join_slots(mi_ilqr* h) { return (!h->other_pending && h->fork_needed) ? MI_ILQR_OK : join_slots_now(h); }
+// ... and call this once the host has waited for the current stream behind a join: nothing of the handle is in flight
+MI_INTERNAL inline void slots_idle(mi_ilqr* h) { h->inflight = 0; h->fork_needed = false; }
+// An entry point that may WRITE x0 / u_guess in place (through the handle's aliases: kernels of the MPC, multi-start and sampling
+// loops, mi_ilqr_set, a caller holding mi_ilqr_device_ptr's pointer): the copy the aliases name is the only one to vouch for.
+MI_INTERNAL inline void inputs_touched(mi_ilqr* h) {
+  h->in_x0.version[1 - h->in_x0.latest] = -1;
+  h->in_u.version[1 - h->in_u.latest] = -1;
+}
+// The entry points that enqueue solves of their own (the MPC, multi-start and sampling loops) or launch behind the policy: joined,
+// and every launch until the end of the scope stays on the current slot.
+struct MI_INTERNAL SlotHold {
+  explicit SlotHold(mi_ilqr* h_) : h(h_), rc(join_slots(h_)) { ++h->hold; inputs_touched(h); }
+  ~SlotHold() { --h->hold; }
+  SlotHold(const SlotHold&) = delete;
+  SlotHold& operator=(const SlotHold&) = delete;
+  mi_ilqr* h;
+  int rc;
+};
+
 // costmat and its host mirror are Q | R | Qf | x_nom: the length of the matrices, and the shared x_nom (host mirror) behind them
 MI_INTERNAL inline size_t cost_len(const mi_ilqr* h) { return 2 * (size_t)h->n * h->n + (size_t)h->m * h->m; }
 MI_INTERNAL inline const double* shared_x_nom(const mi_ilqr* h) { return h->h_costmat.data() + cost_len(h); }

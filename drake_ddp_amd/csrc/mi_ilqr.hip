@@ -250,6 +250,7 @@ KArgs make_args(const mi_ilqr* h) {
 // longer known-zero for the fields the mode writes, and u_bar is materialized.
 // DevStats records of every enqueued solve that has none yet: ONE launch, a workgroup per pending ring slot.
 int reduce_pending_stats(mi_ilqr* h) {
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }      // (the pending slots' solves ran on both streams)
   long long first = h->stats_done;
   if (h->seq - first > mi_ilqr::kStatsRing) first = h->seq - mi_ilqr::kStatsRing;    // older slots were overwritten
   const int count = (int)(h->seq - first);
@@ -257,6 +258,104 @@ int reduce_pending_stats(mi_ilqr* h) {
   h->stats_done = h->seq;
   return MI_ILQR_OK;
 }
+
+// ---- solve slots (host.hpp: SolveSlot, InputCopies; host_internal.hpp: join_slots)
+// Stream `to` waits, on the device, for everything enqueued on stream `from` so far.
+int order_behind(mi_ilqr* h, int from, int to) {
+  HIPCHK(hipEventRecord(h->slots[from].ev, h->slots[from].stream));
+  HIPCHK(hipStreamWaitEvent(h->slots[to].stream, h->slots[from].ev, 0));
+  return MI_ILQR_OK;
+}
+
+// Before anything is enqueued on the OTHER slot's stream: it follows whatever the current stream got from the entry points that
+// joined (uploads of costs or targets, a warm solve, an MPC loop ...) - one event after such work, none between two pipelined solves.
+int fork_to_other(mi_ilqr* h) {
+  if (h->fork_needed) {
+    const int rc = order_behind(h, h->solve_slot, 1 - h->solve_slot);
+    if (rc != MI_ILQR_OK) return rc;
+    h->fork_needed = false;
+  }
+  h->other_pending = true;
+  return MI_ILQR_OK;
+}
+
+// The second slot, allocated by the first launch that can use it: its arrays zeroed like slot 0's at create, the second copies of
+// the inputs (nothing to vouch for yet), its stream.
+int ensure_second_slot(mi_ilqr* h) {
+  if (h->second_slot_ready) return MI_ILQR_OK;
+  const size_t n = h->n, m = h->m, N = h->N, B = h->B, cap = (size_t)h->d.hist_cap;
+  SolveSlot& s = h->slots[1];
+  int rc = MI_ILQR_OK;
+  auto zeroed = [&](auto*& p, size_t count) { if (rc == MI_ILQR_OK && !p) rc = dev_alloc(h, p, count, true); };
+  zeroed(s.x_bar, B * n * N);
+  zeroed(s.u_bar, B * m * (N - 1));
+  zeroed(s.K, B * m * n * (N - 1));
+  zeroed(s.kappa, B * m * (N - 1));
+  zeroed(s.dV, B * (N - 1));
+  zeroed(s.fx, B * n * n * (N - 1));
+  zeroed(s.fu, B * n * m * (N - 1));
+  zeroed(s.hist, B * cap * 4);
+  zeroed(s.iter_cyc, B * cap * 4);
+  zeroed(s.prof, B * 4);
+  zeroed(s.kp_count, B);
+  zeroed(s.kp_list, B * (N - 1));
+  zeroed(s.done_counter, 1);
+  if (h->slots[0].s2) zeroed(s.s2, B);
+  zeroed(h->in_x0.copy[1], B * n);
+  zeroed(h->in_u.copy[1], B * m * (N - 1));
+  if (rc != MI_ILQR_OK) return rc;
+  HIPCHK(hipStreamSynchronize(nullptr));      // (the zeros went through the null stream, which the slots' streams do not follow)
+  if (!s.stream) HIPCHK(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+  for (SolveSlot& q : h->slots) if (!q.ev) HIPCHK(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
+  h->second_slot_ready = true;
+  return MI_ILQR_OK;
+}
+
+// A launch on slot t reads copy t of the inputs: brought up to date, on t's stream, when the latest write went to the other copy (the
+// first launch on the slot, or a mi_ilqr_set_initial that could not tell where the next solve would go).
+int sync_input(mi_ilqr* h, InputCopies& in, int t, size_t bytes) {
+  if (in.version[t] != in.version[in.latest]) {
+    const int src = in.latest;
+    const int rc = order_behind(h, src, t);
+    if (rc != MI_ILQR_OK) return rc;
+    HIPCHK(hipMemcpyAsync(in.copy[t], in.copy[src], bytes, hipMemcpyDeviceToDevice, h->slots[t].stream));
+    in.version[t] = in.version[src];
+    in.read_across[src] = true;
+  }
+  in.latest = t;
+  return MI_ILQR_OK;
+}
+int sync_inputs(mi_ilqr* h, int t) {
+  int rc = sync_input(h, h->in_x0, t, (size_t)h->B * h->n * 8);
+  if (rc == MI_ILQR_OK) rc = sync_input(h, h->in_u, t, (size_t)h->B * h->m * (h->N - 1) * 8);
+  h->x0 = h->in_x0.copy[h->in_x0.latest]; h->u_guess = h->in_u.copy[h->in_u.latest];
+  return rc;
+}
+
+// mi_ilqr_set_initial(_shared) write "the inputs of the NEXT solve" and return at once.  The slot whose copy and stream the write
+// goes to is the one that solve will take as far as the handle can tell now: the other one while solves are in flight on a handle
+// that overlaps them, else the current one.  A wrong guess costs overlap, not correctness (sync_inputs).
+int input_slot(const mi_ilqr* h) {
+  const bool other = h->second_slot_ready && h->n_slots == 2 && !h->sink_x && h->hold == 0 && h->inflight > 0;
+  return other ? 1 - h->solve_slot : h->solve_slot;
+}
+// ... and the write itself, between begin and end: on slot w's stream (h->stream names it meanwhile), behind every solve that reads
+// copy w - those run on the same stream - and behind a device copy that read it from the other one.
+struct InputWrite {
+  mi_ilqr* h;
+  int w;
+  hipStream_t keep;
+  int rc = MI_ILQR_OK;
+  explicit InputWrite(mi_ilqr* h_) : h(h_), w(input_slot(h_)), keep(h_->stream) {
+    if (w != h->solve_slot) rc = fork_to_other(h);
+    for (InputCopies* in : {&h->in_x0, &h->in_u})
+      if (rc == MI_ILQR_OK && in->read_across[w]) { rc = order_behind(h, 1 - w, w); in->read_across[w] = false; }
+    h->stream = h->slots[w].stream;
+  }
+  ~InputWrite() { h->stream = keep; }
+  double* begin(InputCopies& in) const { return in.copy[w]; }
+  void end(InputCopies& in, double*& alias) const { in.version[w] = ++in.writes; in.latest = w; alias = in.copy[w]; }
+};
 
 double bytes_per_iteration(int n, int m, int N, int ls) {
   const double roll = 2.0 * n * N + (3.0 * m + (double)m * n) * (N - 1) + n + 1;
@@ -368,6 +467,19 @@ int create_resources(mi_ilqr* h, bool lxu_hbm) {
     h->costmat_synced = true;
   }
   HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  {
+    // slot 0 is what was allocated above.  Which handles get a second one, lazily: the wave-per-problem family - its SOLVE kernel has
+    // no synchronisation between workgroups but the statistics ticket (a slot's own) -, more than four problems (tiny batches read
+    // their inputs from mapped host memory and serialize by design), and at most four launches' worth of one wave per SIMD:
+    // beyond that a batch's own later workgroups fill the SIMDs its finished problems leave.
+    SolveSlot& s = h->slots[0];
+    s.x_bar = h->x_bar; s.u_bar = h->u_bar; s.K = h->K; s.kappa = h->kappa; s.dV = h->dV; s.fx = h->fx; s.fu = h->fu;
+    s.hist = h->hist; s.iter_cyc = h->iter_cyc; s.prof = h->prof; s.kp_count = h->kp_count; s.kp_list = h->kp_list;
+    s.done_counter = h->done_counter; s.stream = h->stream;
+    h->in_x0.copy[0] = h->x0; h->in_u.copy[0] = h->u_guess;
+    const bool family = !large && !batch_minor && B > 4;
+    h->n_slots = (switches().solve_slots == 2 && family && h->n_cus > 0 && B <= 16 * (size_t)h->n_cus) ? 2 : 1;
+  }
   for (int i = 0; i < mi_ilqr::kStatsRing; ++i) {
     HIPCHK(hipEventCreate(&h->ring_ev0[i]));
     HIPCHK(hipEventCreate(&h->ring_ev1[i]));
@@ -514,6 +626,7 @@ void fill_stats(mi_ilqr* h, int slot, mi_ilqr_stats* st) {
 int upload_stage_in(mi_ilqr* h, const double* v) {
   if (!v) return MI_ILQR_E_BAD_ARG;
   HIPCHK(hipSetDevice(h->d.device_id));
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(h->stage_in, v, (size_t)h->B * 8, hipMemcpyHostToDevice));
   return MI_ILQR_OK;
@@ -528,6 +641,17 @@ int reduce_stats(mi_ilqr* h, int first_slot, int count) {
   return MI_ILQR_OK;
 }
 
+int join_slots_now(mi_ilqr* h) {
+  if (h->other_pending) {
+    HIPCHK(hipSetDevice(h->d.device_id));
+    const int rc = order_behind(h, 1 - h->solve_slot, h->solve_slot);
+    if (rc != MI_ILQR_OK) return rc;
+    h->other_pending = false;
+  }
+  h->fork_needed = true;
+  return MI_ILQR_OK;
+}
+
 const Model* model_of(int id) {
   if (id >= 0 && id < kNumBuiltins) return &kBuiltins[id];
   const int s_ = id - MI_MODEL_PLUGIN_BASE;
@@ -536,6 +660,7 @@ const Model* model_of(int id) {
 
 int launch(mi_ilqr* h, int mode) {
   HIPCHK(hipSetDevice(h->d.device_id));
+  if (!h->in_async_solve) { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }   // (mi_ilqr_solve_async has chosen the slot)
   if (h->costs.synced && h->batch_minor && !h->targets.synced) { const int rc = refresh_lane_target_rows(h); if (rc != MI_ILQR_OK) return rc; }
   // any launch other than a pipelined solve reuses the current ring slot: settle the statistics still owed first
   if (!h->in_async_solve) { const int rc = reduce_pending_stats(h); if (rc != MI_ILQR_OK) return rc; }
@@ -549,6 +674,7 @@ int launch(mi_ilqr* h, int mode) {
 // of it, materialize the zeros first.
 int materialize_zero_state(mi_ilqr* h) {
   if (!h->cold) return MI_ILQR_OK;
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   const size_t n = h->n, m = h->m, N = h->N, B = h->B;
   HIPCHK(hipMemsetAsync(h->x_bar, 0, B * n * N * 8, h->stream));
   HIPCHK(hipMemsetAsync(h->K, 0, B * m * n * (N - 1) * 8, h->stream));
@@ -562,6 +688,7 @@ int materialize_zero_state(mi_ilqr* h) {
 }
 
 int materialize_u(mi_ilqr* h) {
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   if (h->u_zero && !h->u_pending) HIPCHK(hipMemsetAsync(h->u_bar, 0, (size_t)h->B * h->m * (h->N - 1) * 8, h->stream));
   h->u_zero = false;
   if (!h->u_pending) return MI_ILQR_OK;
@@ -757,7 +884,7 @@ int mi_ilqr_create(const mi_ilqr_desc* desc, mi_ilqr_t** out) {
 void mi_ilqr_destroy(mi_ilqr_t* h) {
   if (!h) return;
   (void)hipSetDevice(h->d.device_id);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (const SolveSlot& s : h->slots) if (s.stream) (void)hipStreamSynchronize(s.stream);
   for (void* p : h->owned) (void)hipFree(p);
   if (h->host_records) (void)hipHostFree(h->host_records);
   if (h->h_ring) (void)hipHostFree(h->h_ring);
@@ -766,7 +893,8 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
     if (h->ring_ev0[i]) (void)hipEventDestroy(h->ring_ev0[i]);
     if (h->ring_ev1[i]) (void)hipEventDestroy(h->ring_ev1[i]);
   }
-  if (h->pin_ev) (void)hipEventDestroy(h->pin_ev);
+  for (hipEvent_t e : h->pin_ev) if (e) (void)hipEventDestroy(e);
+  for (const SolveSlot& s : h->slots) if (s.ev) (void)hipEventDestroy(s.ev);
   if (h->policy_ev0) (void)hipEventDestroy(h->policy_ev0);
   if (h->policy_ev1) (void)hipEventDestroy(h->policy_ev1);
   for (hipEvent_t e : h->mc_events) (void)hipEventDestroy(e);
@@ -774,7 +902,8 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
   if (h->seeds_ev1) (void)hipEventDestroy(h->seeds_ev1);
   if (h->plant_ev0) (void)hipEventDestroy(h->plant_ev0);
   if (h->plant_ev1) (void)hipEventDestroy(h->plant_ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  if (!h->slots[0].stream && h->stream) (void)hipStreamDestroy(h->stream);      // (a create that failed before the slots were set up)
+  for (const SolveSlot& s : h->slots) if (s.stream) (void)hipStreamDestroy(s.stream);
   delete h;
 }
 
@@ -805,6 +934,8 @@ int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const doubl
     h->h_costmat.swap(cm);
   }
   h->costmat_synced = false;                                  // (a failed copy must not leave the mirror believed)
+  // (joined only here: matrices the caller repeats between pipelined solves leave their overlap alone)
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   const int rc = stage_h2d(h, h->costmat, h->h_costmat.data(), h->h_costmat.size() * 8);    // Q | R | Qf | x_nom: one copy
   h->costmat_synced = rc == MI_ILQR_OK;
   return rc;
@@ -814,21 +945,29 @@ int mi_ilqr_set_initial(mi_ilqr_t* h, const double* x0, const double* u_guess) {
   if (!h) return MI_ILQR_E_BAD_ARG;
   HIPCHK(hipSetDevice(h->d.device_id));
   if (h->host_inputs) return host_inputs_write(h, x0, u_guess, false);
-  if (x0) { const int rc = stage_h2d(h, h->x0, x0, (size_t)h->B * h->n * 8); if (rc != MI_ILQR_OK) return rc; }
+  const InputWrite wr(h);
+  if (wr.rc != MI_ILQR_OK) return wr.rc;
+  if (x0) {
+    const int rc = stage_h2d(h, wr.begin(h->in_x0), x0, (size_t)h->B * h->n * 8);
+    if (rc != MI_ILQR_OK) return rc;
+    wr.end(h->in_x0, h->x0);
+  }
   if (u_guess) {
     const size_t cnt = (size_t)h->B * h->m * (h->N - 1);
+    double* const dst = wr.begin(h->in_u);
     int rows = 0, len = 0;
     if (needs_relayout(h, MI_F_U_BAR, &rows, &len)) {
       int rc = ensure_scratch(h, cnt * 8);
       if (rc != MI_ILQR_OK) return rc;
       HIPCHK(hipStreamSynchronize(h->stream));
       HIPCHK(hipMemcpy(h->scratch, u_guess, cnt * 8, hipMemcpyHostToDevice));
-      if ((rc = relayout(h, h->scratch, h->u_guess, rows, len, true)) != MI_ILQR_OK) return rc;
+      if ((rc = relayout(h, h->scratch, dst, rows, len, true)) != MI_ILQR_OK) return rc;
       HIPCHK(hipStreamSynchronize(h->stream));
     } else {
-      const int rc = stage_h2d(h, h->u_guess, u_guess, cnt * 8);
+      const int rc = stage_h2d(h, dst, u_guess, cnt * 8);
       if (rc != MI_ILQR_OK) return rc;
     }
+    wr.end(h->in_u, h->u_guess);
     h->u_pending = true;
     h->u_zero = false;
   }
@@ -839,13 +978,21 @@ int mi_ilqr_set_initial_shared(mi_ilqr_t* h, const double* x0, const double* u_g
   if (!h) return MI_ILQR_E_BAD_ARG;
   HIPCHK(hipSetDevice(h->d.device_id));
   if (h->host_inputs) return host_inputs_write(h, x0, u_guess_one, true);
-  if (x0) { const int rc = stage_h2d(h, h->x0, x0, (size_t)h->B * h->n * 8); if (rc != MI_ILQR_OK) return rc; }
+  const InputWrite wr(h);
+  if (wr.rc != MI_ILQR_OK) return wr.rc;
+  if (x0) {
+    const int rc = stage_h2d(h, wr.begin(h->in_x0), x0, (size_t)h->B * h->n * 8);
+    if (rc != MI_ILQR_OK) return rc;
+    wr.end(h->in_x0, h->x0);
+  }
   if (u_guess_one) {
     const size_t one = (size_t)h->m * (h->N - 1);
-    int rc = h->u_one ? MI_ILQR_OK : dev_alloc(h, h->u_one, one);
-    if (rc == MI_ILQR_OK) rc = stage_h2d(h, h->u_one, u_guess_one, one * 8);
-    if (rc == MI_ILQR_OK) rc = broadcast_u(h, h->u_one, h->u_guess);
+    double*& u_one = h->u_one_copy[wr.w];        // (the staged sequence: one per stream, the broadcast behind an earlier write may not have run yet)
+    int rc = u_one ? MI_ILQR_OK : dev_alloc(h, u_one, one);
+    if (rc == MI_ILQR_OK) rc = stage_h2d(h, u_one, u_guess_one, one * 8);
+    if (rc == MI_ILQR_OK) rc = broadcast_u(h, u_one, wr.begin(h->in_u));
     if (rc != MI_ILQR_OK) return rc;
+    wr.end(h->in_u, h->u_guess);
     h->u_pending = true;
     h->u_zero = false;
   }
@@ -863,6 +1010,7 @@ int mi_ilqr_set_result_sink(mi_ilqr_t* h, double* x_bar_host, double* u_bar_host
   if (!h) return MI_ILQR_E_BAD_ARG;
   if (h->large || h->batch_minor) return MI_ILQR_E_UNSUPPORTED;     // (their kernel layouts are not the boundary's)
   HIPCHK(hipSetDevice(h->d.device_id));
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
   h->sink_x = h->sink_u = h->sink_cost = nullptr;
   if (!x_bar_host && !u_bar_host && !cost_host) return MI_ILQR_OK;
@@ -944,11 +1092,15 @@ int mi_ilqr_set_control_limits(mi_ilqr_t* h, const double* u_min, const double* 
     if (lo != lo || hi != hi || lo > hi) return MI_ILQR_E_BAD_ARG;   // NaN, or an empty box
   }
   HIPCHK(hipSetDevice(h->d.device_id));
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   if (!h->s2) {
     int rc = h->ulim ? MI_ILQR_OK : dev_alloc(h, h->ulim, (size_t)B * 2 * m);
-    if (rc == MI_ILQR_OK) rc = dev_alloc(h, h->s2, (size_t)B);
+    for (int i = 0; i < (h->second_slot_ready ? 2 : 1); ++i) {          // S2 is solver state: one array per solve slot
+      if (rc == MI_ILQR_OK && !h->slots[i].s2) rc = dev_alloc(h, h->slots[i].s2, (size_t)B);
+      if (rc == MI_ILQR_OK) HIPCHK(hipMemsetAsync(h->slots[i].s2, 0, (size_t)B * 8, h->stream));
+    }
     if (rc != MI_ILQR_OK) return rc;
-    HIPCHK(hipMemsetAsync(h->s2, 0, (size_t)B * 8, h->stream));
+    h->s2 = h->slots[h->solve_slot].s2;
   }
   std::vector<double> box((size_t)B * 2 * m);     // (B, 2, m): u_min | u_max, shared bounds broadcast here
   for (int b = 0; b < B; ++b) {
@@ -971,12 +1123,32 @@ int mi_ilqr_rearm_initial_guess(mi_ilqr_t* h) {
 int mi_ilqr_synchronize(mi_ilqr_t* h) {
   if (!h) return MI_ILQR_E_BAD_ARG;
   HIPCHK(hipSetDevice(h->d.device_id));
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
+  slots_idle(h);
   return MI_ILQR_OK;
 }
 
 int mi_ilqr_solve_async(mi_ilqr_t* h) {
   if (!h) return MI_ILQR_E_BAD_ARG;
+  HIPCHK(hipSetDevice(h->d.device_id));
+  // A cold solve reads no solver state, so between two of them only their outputs collide: it takes the OTHER solve slot - arrays and
+  // stream - and shares the device with the solve before it.  With nothing in flight there is nothing to share it with.
+  bool overlap = h->n_slots == 2 && h->cold && !h->sink_x && h->hold == 0 && h->inflight > 0;
+  if (overlap && ensure_second_slot(h) != MI_ILQR_OK) {
+    (void)hipGetLastError();
+    h->n_slots = 1;                      // (no room for a second slot: one at a time, as before)
+    overlap = false;
+  }
+  if (overlap) {
+    int rc = fork_to_other(h);
+    if (rc != MI_ILQR_OK) return rc;
+    select_solve_slot(h, 1 - h->solve_slot);
+    if ((rc = sync_inputs(h, h->solve_slot)) != MI_ILQR_OK) return rc;
+  } else {
+    const int rc = join_slots(h);
+    if (rc != MI_ILQR_OK) return rc;
+  }
   const int slot = (int)(h->seq++ % mi_ilqr::kStatsRing);
   select_stats_slot(h, slot);
   // pipelined solves: the events ride on one launch in `time_every` (every other entry point times its launches)
@@ -990,6 +1162,7 @@ int mi_ilqr_solve_async(mi_ilqr_t* h) {
   if (stats_in_kernel(h) && h->stats_done == h->seq - 1) h->stats_done = h->seq;
   h->cold = false;
   h->u_pending = false;
+  ++h->inflight;
   return MI_ILQR_OK;
 }
 
@@ -998,6 +1171,7 @@ int mi_ilqr_collect_stats(mi_ilqr_t* h, mi_ilqr_stats* st) {
   HIPCHK(hipSetDevice(h->d.device_id));
   { const int rc = reduce_pending_stats(h); if (rc != MI_ILQR_OK) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
+  slots_idle(h);
   fill_stats(h, (int)(h->h_stats - h->h_ring), st);
   return MI_ILQR_OK;
 }
@@ -1007,6 +1181,7 @@ int mi_ilqr_collect_stats_n(mi_ilqr_t* h, int32_t count, mi_ilqr_stats* st) {
   HIPCHK(hipSetDevice(h->d.device_id));
   { const int rc = reduce_pending_stats(h); if (rc != MI_ILQR_OK) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
+  slots_idle(h);
   for (int i = 0; i < count; ++i) fill_stats(h, (int)((h->seq - count + i) % mi_ilqr::kStatsRing), st + i);
   return MI_ILQR_OK;
 }
@@ -1069,6 +1244,7 @@ int mi_ilqr_last_kernel_ms(mi_ilqr_t* h, float* ms) {
   if (!h || !ms) return MI_ILQR_E_BAD_ARG;
   if (!h->last_timed) { *ms = 0.0f; return MI_ILQR_OK; }
   HIPCHK(hipSetDevice(h->d.device_id));
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipEventElapsedTime(ms, h->ev0, h->ev1));
   return MI_ILQR_OK;
@@ -1078,6 +1254,7 @@ int mi_ilqr_get_cycles(mi_ilqr_t* h, int64_t* dst, size_t bytes) {
   if (!h || !dst) return MI_ILQR_E_BAD_ARG;
   if (bytes != (size_t)h->B * 4 * 8) return MI_ILQR_E_BAD_SHAPE;
   HIPCHK(hipSetDevice(h->d.device_id));
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(dst, h->prof, bytes, hipMemcpyDefault));
   return MI_ILQR_OK;
@@ -1085,6 +1262,8 @@ int mi_ilqr_get_cycles(mi_ilqr_t* h, int64_t* dst, size_t bytes) {
 
 int mi_ilqr_get_stream(mi_ilqr_t* h, void** hip_stream) {
   if (!h || !hip_stream) return MI_ILQR_E_BAD_ARG;
+  // the current slot's stream, ordered behind the other one's: work a caller enqueues on it follows every solve enqueued so far
+  { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }
   *hip_stream = reinterpret_cast<void*>(h->stream);
   return MI_ILQR_OK;
 }

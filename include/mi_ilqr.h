@@ -359,7 +359,12 @@ int mi_ilqr_set_cost(mi_ilqr_t* h, const double* Q, const double* R, const doubl
  * on the handle's stream (the call returns at once, behind a solve that is still running); wave-per-problem handles of up to four
  * problems keep x0 / u_guess in mapped host memory that the kernels read directly (no copy engine in front of a single-problem
  * solve), so there the call WAITS for a solve still in flight before it overwrites them - a caller that pipelines
- * solve_async / set_initial / collect on such a handle serializes at set_initial. */
+ * solve_async / set_initial / collect on such a handle serializes at set_initial.
+ * Handles whose pipelined cold solves share the device (mi_ilqr_solve_async, "Solve slots") hold TWO device copies of x0 and of
+ * u_guess: the write goes to the copy the next solve will read, on that solve's stream, so it waits - on the device, never the
+ * host - only for solves that still read that copy, and a solve_async -> set_initial -> solve_async -> ... pipeline overlaps
+ * like one that re-arms resident inputs.  A solve that follows without a set_initial reads what was written last.  x0 alone or
+ * u_guess alone is fine: each input has its own copies. */
 int mi_ilqr_set_initial(mi_ilqr_t* h, const double* x0, const double* u_guess);
 
 /* The same with ONE control sequence u_guess_one (m,N-1) for every problem of the batch - the argument the
@@ -405,7 +410,18 @@ int mi_ilqr_rearm_initial_guess(mi_ilqr_t* h);
  * kernel on the handle's stream - ONE dispatch: every solve leaves its per-problem cost / iterations / status /
  * line-search trials in its own slot of a 32-deep ring, and _collect_stats(_n) reduces all slots still owed
  * their batch statistics in one launch, synchronizes and returns them (more than 32 uncollected solves:
- * the oldest are overwritten). */
+ * the oldest are overwritten).
+ * Solve slots.  A handle of the wave-per-problem family with 4 < B <= 16 x (compute units) owns two solve slots: two sets of the
+ * arrays a solve writes (x_bar, u_bar, K, kappa, dV, fx, fu, the iteration log and its cycles, the stopwatches, the key-point
+ * list and counts, S2 of a limited handle), each with a stream.  A COLD _solve_async (after mi_ilqr_reset) reads no solver state,
+ * so with a solve already in flight it takes the other slot and the two launches share the device: the second one's wavefronts
+ * land on the SIMDs the first one's finished problems have left (one launch is one wave per SIMD and lasts as long as its slowest
+ * problem).  The second slot is allocated by the first solve that can use it; a handle that never pipelines cold solves never
+ * pays for it.  Results are bit for bit those of one solve at a time.  Every other launch - a warm solve, a handle with a result
+ * sink, the other kernel families, mpc_run, the stage entries - and every entry point that reads or writes solver state or hands
+ * out a pointer or the stream first JOINS: the current slot's stream (that of the solve enqueued last) waits on the device for the
+ * other one's, then the call works on the current slot as if there were one.  A warm solve continues from the solve enqueued last.
+ * MI_ILQR_SOLVE_SLOTS=1 in the environment (read once per process) gives every handle one slot: one solve at a time. */
 int mi_ilqr_solve(mi_ilqr_t* h, mi_ilqr_stats* stats);
 int mi_ilqr_solve_async(mi_ilqr_t* h);
 int mi_ilqr_collect_stats(mi_ilqr_t* h, mi_ilqr_stats* stats);
@@ -486,7 +502,12 @@ int mi_ilqr_solve_into(mi_ilqr_t* h, double* x_bar, double* u_bar, double* cost,
 /* Raw device pointer of a double field (for zero-copy consumers, e.g. a torch tensor
  * view feeding the RCCL best-cost reduction), and the handle's stream.  The per-problem result scalars
  * (MI_F_COST, MI_I_ITERS, MI_I_STATUS, MI_I_LS_TRIALS) rotate through a ring, one slot per
- * mi_ilqr_solve / mi_ilqr_solve_async: ask for their pointer again after each solve. */
+ * mi_ilqr_solve / mi_ilqr_solve_async: ask for their pointer again after each solve.  The same holds for the state fields
+ * (MI_F_X_BAR .. MI_F_FU, MI_F_HIST, MI_F_ITER_CYCLES, the key-point fields, MI_I64_STAGE_CYCLES) and MI_F_X0 of a handle with two
+ * solve slots (mi_ilqr_solve_async): the pointer is that of the solve enqueued last - ask again after each solve.
+ * mi_ilqr_get_stream: the stream of the solve enqueued last, made to wait (on the device) for the other slot's stream first - work
+ * a caller enqueues on it runs behind every solve enqueued so far, and a later solve of the handle behind that work.  Ask again
+ * after each solve here as well. */
 int mi_ilqr_device_ptr(mi_ilqr_t* h, int which, void** ptr, size_t* bytes);
 int mi_ilqr_get_stream(mi_ilqr_t* h, void** hip_stream);
 int mi_ilqr_synchronize(mi_ilqr_t* h);
@@ -521,13 +542,17 @@ int mi_ilqr_allreduce_min_wait(mi_ilqr_comm_t* c, double* values, int32_t count)
  * of the reference's time_fp / time_getDerivs / time_backwardsPass (ilqr.py:364-372,696-699). */
 int mi_ilqr_get_cycles(mi_ilqr_t* h, int64_t* dst, size_t bytes);
 
-/* HIP-event duration of the most recent kernel launch on the handle's stream (0 if that launch was not timed). */
+/* HIP-event duration of the most recent kernel launch of the handle (0 if that launch was not timed).  For a pipelined cold solve
+ * that shared the device with its neighbours (mi_ilqr_solve_async, "Solve slots") this is the span of that dispatch WHILE it
+ * shares the device, not the time it would take alone. */
 int mi_ilqr_last_kernel_ms(mi_ilqr_t* h, float* ms);
 
 /* Which launches carry their start/stop events: every one (every = 1, the default), the first of every `every`
  * solves, or none (every = 0).  The events ride on the solve kernel's own dispatch packet, but a profiled dispatch
  * still serializes a pipelined stream by ~5 us; a caller that enqueues solves back to back (mi_ilqr_solve_async)
- * and wants kernel_ms only as a sample asks for one in k.  Untimed launches report kernel_ms = 0. */
+ * and wants kernel_ms only as a sample asks for one in k.  Untimed launches report kernel_ms = 0.  Timed launches overlap like
+ * the others on a handle with two solve slots; kernel_ms of an overlapped launch is its span while it shares the device (the
+ * exclusive kernel time is what MI_ILQR_SOLVE_SLOTS=1 measures). */
 int mi_ilqr_set_timing(mi_ilqr_t* h, int32_t every);
 
 /* Algorithmic bytes of one iteration of one problem with `ls` line-search trials. */
