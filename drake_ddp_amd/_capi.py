@@ -58,6 +58,15 @@ SEEDS_RUN_DOUBLES, SEEDS_MPC_RUN_DOUBLES = 6, 8
 # the sampling form ("Sampling-based MPC"): (10,) S | SEEDS_RESEED | seed | first_sample | hold | 0 | iterations | shift | temperature | 0;
 # F_SEEDS_BEST then holds (iterations, B, 3), F_SEEDS_COST (iterations + 1, B, 2), F_SEEDS_U_BAR (B, m, N - 1)
 SEEDS_MPPI_RUN_DOUBLES = 10
+# parameter identification (mi_ilqr.h: "Parameter identification"): (B, T, 2n+m) rows x | u | x_next | (B, n+1) w | count | (B, n_params+1)
+# theta0 | mu0 | (2, n_params) lower | upper | write-only command (6+P,) iterations | ftol | fd_rel | fd_floor | apply | P | free.. |
+# read-only (B, n_params+7) theta | cost0 | cost | mu | iterations | accepted | status | count | read-only (B, P+P*P) g | H |
+# read-only (1,) ms of the run's kernels
+F_FIT_DATA, F_FIT_WEIGHTS, F_FIT_START, F_FIT_BOUNDS, F_FIT_RUN, F_FIT_RESULT, F_FIT_NORMAL, F_FIT_KERNEL_MS = 45, 46, 47, 48, 49, 50, 51, 52
+FIT_CONVERGED, FIT_MAX_ITERS, FIT_STALLED, FIT_BAD_DATA = 0, 1, 2, 3
+FIT_MAX_FREE = 8            # MI_FIT_MAX_FREE
+FIT_RUN_DOUBLES = 6         # ... + P
+FIT_RESULT_EXTRA = 7        # the columns of F_FIT_RESULT behind theta
 I_ITERS, I_STATUS, I_LS_TRIALS, I_KP_COUNT, I_KP_LIST = 100, 101, 102, 103, 104
 I_POLICY_MC_PASSES = 105    # (1,) passes over windows of sample groups of the last on-device Monte-Carlo run
 I64_STAGE_CYCLES = 200

@@ -266,3 +266,91 @@ def check_mppi_args(S, iterations, B, m, N, sigma_u, temperature, seed=0, first_
     if not ok or not temperature >= 0.0:
         raise ValueError(f"{what}: temperature must be a number >= 0 (0: the best sample alone); got {temperature!r}")
     return S, iterations, sigma, float(temperature), seed, first_sample, hold, shift
+
+
+def check_fit_args(x, u, x_next, B, n, m, n_params, *, free, params0, count=None, weights=None, damping=1e-3, bounds=None, iterations=20,
+                   ftol=1e-12, fd_rel=1e-6, fd_floor=1e-8, apply=False, m_dev=None, what="FitModelParameters"):
+    """The parameter-identification arguments -> (data, wrows, start, brows, run): data the contiguous (B, T, 2 n + m_dev) float64 rows
+    x | u | x_next with zeros on the padding controls and in the rows past a problem's count (MI_F_FIT_DATA), wrows the (B, n + 1)
+    rows w | count, start the (B, n_params + 1) rows theta0 | mu0, brows None or the (2, n_params) rows lower | upper, run the
+    float64 vector iterations | ftol | fd_rel | fd_floor | apply | P | free.. (MI_F_FIT_RUN).  x, x_next: (B, T, n), u: (B, T, m),
+    T >= 1; free: strictly increasing indices below n_params, between 1 and 8 of them; count: None - T - or (B,) integers in
+    [0, T]; weights: None - ones - or (n,) / (B, n), >= 0; params0: (B, n_params) or (n_params,) (the caller resolves None to the
+    rows the solver holds); damping: a scalar or (B,), > 0; bounds: None or a pair (lo, hi), each None or (n_params,), +-inf allowed.
+    ValueError - decided here, before anything reaches the library - for a model without parameters, any other rank or shape, a
+    NaN or an infinity in a row a problem uses, in weights, params0 or damping, a NaN in bounds or lo > hi, a free list that is
+    empty, too long, not increasing or out of range, a count outside [0, T], an iterations that is no integer in [0, 2^20], an ftol
+    that is no number >= 0, an fd_rel or fd_floor that is no number > 0, an apply that is no bool."""
+    who = what
+    if n_params == 0:
+        raise ValueError(f"{who}: this model has no parameters")
+    arrs = []
+    T = None
+    for name, v, k in (("x", x, n), ("u", u, m), ("x_next", x_next, n)):
+        a = numbers(v, who, name)
+        if a.ndim != 3 or a.shape[0] != B or a.shape[2] != k or a.shape[1] < 1 or (T is not None and a.shape[1] != T):
+            raise ValueError(f"{who}: {name} must be ({B}, {'T' if T is None else T}, {k}) with T >= 1; got {a.shape}")
+        T = a.shape[1]
+        arrs.append(a)
+    try:
+        free = list(free)
+    except TypeError:
+        raise ValueError(f"{who}: free must be a list of parameter indices; got {free!r}") from None
+    if not 1 <= len(free) <= _capi.FIT_MAX_FREE:
+        raise ValueError(f"{who}: free must hold between 1 and {_capi.FIT_MAX_FREE} parameter indices; got {len(free)}")
+    free = [integer(v, who, f"free[{i}]", 0, n_params, f"in [0, {n_params - 1}]") for i, v in enumerate(free)]
+    if any(b_ <= a_ for a_, b_ in zip(free, free[1:])):
+        raise ValueError(f"{who}: free must be strictly increasing; got {free}")
+    if count is None:
+        cnt = np.full(B, T, dtype=np.int64)
+    else:
+        c = numbers(count, who, "count")
+        if c.shape != (B,) or not np.isfinite(c).all() or (c != np.floor(c)).any() or (c < 0).any() or (c > T).any():
+            raise ValueError(f"{who}: count must be ({B},) integers in [0, {T}]; got {count!r}")
+        cnt = c.astype(np.int64)
+    used = np.arange(T)[None, :] < cnt[:, None]
+    for name, a in zip(("x", "u", "x_next"), arrs):
+        if not np.isfinite(a[used]).all():
+            raise ValueError(f"{who}: NaN or infinity in {name}")
+    md = m if m_dev is None else int(m_dev)
+    data = np.zeros((B, T, 2 * n + md))
+    data[:, :, :n], data[:, :, n:n + m], data[:, :, n + md:] = arrs
+    data[~used] = 0.0
+    wrows = np.empty((B, n + 1))
+    wrows[:, :n] = 1.0 if weights is None else rows(weights, who, "weights", B, n, nonneg="")
+    wrows[:, n] = cnt
+    start = np.empty((B, n_params + 1))
+    if params0 is None:
+        raise ValueError(f"{who}: params0 is required")
+    start[:, :n_params] = rows(params0, who, "params0", B, n_params, b_first=True)
+    d = numbers(damping, who, "damping")
+    if d.shape not in ((), (B,)) or not np.isfinite(d).all() or not (d > 0.0).all():
+        raise ValueError(f"{who}: damping must be a scalar or ({B},), finite and > 0; got {damping!r}")
+    start[:, n_params] = d
+    brows = None
+    if bounds is not None:
+        if not isinstance(bounds, (tuple, list)) or len(bounds) != 2:
+            raise ValueError(f"{who}: bounds must be a pair (lo, hi)")
+        brows = np.empty((2, n_params))
+        for j, (name, v, dflt) in enumerate((("bounds lo", bounds[0], -np.inf), ("bounds hi", bounds[1], np.inf))):
+            if v is None:
+                brows[j] = dflt
+                continue
+            a = numbers(v, who, name)
+            if a.shape != (n_params,):
+                raise ValueError(f"{who}: {name} must be ({n_params},); got {a.shape}")
+            if np.isnan(a).any():
+                raise ValueError(f"{who}: NaN in {name}")
+            brows[j] = a
+        if (brows[0] > brows[1]).any():
+            raise ValueError(f"{who}: bounds has lo > hi")
+    iterations = integer(iterations, who, "iterations", 0, (1 << 20) + 1, "in [0, 2^20]")
+    nums = {}
+    for name, v, strict in (("ftol", ftol, False), ("fd_rel", fd_rel, True), ("fd_floor", fd_floor, True)):
+        ok = not isinstance(v, _BOOL) and isinstance(v, _INT + _FLOAT) and np.isfinite(v) and (v > 0.0 if strict else v >= 0.0)
+        if not ok:
+            raise ValueError(f"{who}: {name} must be a finite number {'> 0' if strict else '>= 0'}; got {v!r}")
+        nums[name] = float(v)
+    apply = flag(apply, who, "apply")   # noqa: A001
+    run = np.array([iterations, nums["ftol"], nums["fd_rel"], nums["fd_floor"], 1.0 if apply else 0.0, len(free)] + free, dtype=np.float64)
+    return np.ascontiguousarray(data), wrows, start, brows, run

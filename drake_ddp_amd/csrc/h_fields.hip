@@ -199,6 +199,7 @@ int mi_ilqr_get(mi_ilqr_t* h, int which, double* dst, size_t bytes) {
   { const int rc = join_slots(h); if (rc != MI_ILQR_OK) return rc; }      // (solve slots: what follows reads the current one, on its stream)
   if (const int rc = get_plant_field(h, which, dst, bytes); rc != kNotPlantField) return rc;
   if (const int rc = get_seeds_field(h, which, dst, bytes); rc != kNotSeedsField) return rc;      // (the last command's results, host copies)
+  if (const int rc = get_fit_field(h, which, dst, bytes); rc != kNotFitField) return rc;          // (the same of parameter identification)
   if (const RowField r = row_field(h, which); r.store) return store_read(h, *r.store, r.shared_row, dst, bytes);   // (host mirrors)
   if (which == MI_F_POLICY_STREAM) {
     if (bytes != 3 * 8) return MI_ILQR_E_BAD_SHAPE;
@@ -327,6 +328,7 @@ int mi_ilqr_set(mi_ilqr_t* h, int which, const double* src, size_t bytes) {
     case MI_F_X_REF: return set_reference(h, src, bytes);
     case MI_F_REF_CLOCK: return set_ref_clock(h, src, bytes);
   }
+  if (const int rc = set_fit_field(h, which, src, bytes); rc != kNotFitField) return rc;           // (MI_F_FIT_*: h_fit.hip)
   if (!src) return MI_ILQR_E_BAD_ARG;
   if (which == MI_F_X_NOM || which == MI_F_TARGET_STEP) return set_target_field(h, which, src, bytes);
   Field f = field_of(h, which);

@@ -221,6 +221,17 @@ struct mi_ilqr {
   hipEvent_t seeds_ev0 = nullptr, seeds_ev1 = nullptr;
   bool seeds_ran = false;
   double seeds_ms = 0.0;
+  // parameter identification (MI_F_FIT_*; fit.hpp, h_fit.hip).  fit_data: the (B, fit_T, 2 n + m) transitions on the device,
+  // grow-only, fit_data_cap doubles.  fit_weights (B, n + 1) w | count, fit_start (B, n_params + 1) theta0 | mu0, fit_bounds
+  // (2, n_params): what the setters left, on the host (empty: the defaults); they go to the device with a command.  fit_result
+  // (B, n_params + 7) / fit_normal (B, P + P P): the last command's results on the host (empty: none yet).  fit_ev0 / fit_ev1: the
+  // command's own event pair.  Nothing of this is read or written by a solve.
+  double* fit_data = nullptr;
+  size_t fit_data_cap = 0;
+  int fit_T = 0;
+  std::vector<double> fit_weights, fit_start, fit_bounds, fit_result, fit_normal;
+  hipEvent_t fit_ev0 = nullptr, fit_ev1 = nullptr;
+  double fit_ms = 0.0;
 };
 
 // Run-time switches for A/B runs (README): the environment is read once per process.
@@ -306,6 +317,9 @@ constexpr int kModePolicyMC = 0x504d43;
 // mi_ilqr_set(MI_F_SEEDS_RUN) in its sampling form: the launch entry takes a MppiArgs (below) and launches mppi_rollout_kernel<M>
 // (mppi.hpp), one lane per sample of the perturbed nominal plan, whatever the handle's kernel family.
 constexpr int kModeSampledRollout = 0x4d5050;
+// mi_ilqr_set(MI_F_FIT_RUN): the launch entry takes a FitArgs (below) and launches fit_normal_kernel<M> (fit.hpp), one lane per
+// (transition, finite-difference slot), whatever the handle's kernel family.
+constexpr int kModeFitNormal = 0x464954;
 constexpr int kMaxBatchPluginN = 6;      // family-0 models up to this n also get the lane-per-problem kernels
 
 // The dynamic-LDS ceiling of a kernel is raised once per (kernel, device), to the hardware maximum - not
@@ -505,6 +519,44 @@ MI_INTERNAL int launch_mppi_stage(mi_ilqr* h, const double* src, double* nom, in
 MI_INTERNAL int launch_mppi_handover(mi_ilqr* h, const double* nom, double* u_guess, double* tl, const double* cost1, double* costlog, int B,
                                      int m, int N, int layout, int shift, hipEvent_t ev1);
 
+// Parameter identification (fit.hpp; k_fit.hip; h_fit.hip), the command of MI_F_FIT_RUN.  A problem's state between the launches is
+// one record of kFitStride doubles on the device: theta | the trial row | the kept normal equations, laid out like a partial row
+// (below) from kFitC on | mu | trials so far | accepted trials | status (kFitRunning until the problem has finished) | the first
+// cost | whether the trial row came out of a factorisation that succeeded.
+constexpr int kFitMaxFree = MI_FIT_MAX_FREE;
+// a partial row, and the kept normal equations: c | g (P) | the upper triangle of H, row after row
+constexpr int fit_row_len(int P) { return 1 + P + P * (P + 1) / 2; }
+constexpr int kFitTheta = 0, kFitTrial = MI_ILQR_MAX_PARAMS, kFitC = 2 * MI_ILQR_MAX_PARAMS;
+constexpr int kFitMu = kFitC + fit_row_len(kFitMaxFree), kFitIters = kFitMu + 1, kFitAccepted = kFitMu + 2, kFitStatus = kFitMu + 3;
+constexpr int kFitCost0 = kFitMu + 4, kFitTrialOk = kFitMu + 5, kFitStride = 96;
+static_assert(kFitTrialOk < kFitStride, "a problem's record holds every field");
+constexpr double kFitRunning = -1.0;
+constexpr double kFitMuMin = 1e-12, kFitMuMax = 1e12;
+// Arguments of fit_normal_kernel<M>: device pointers.
+struct FitArgs {
+  const double* data;         // (B, T, 2 n + m): rows x | u | x_next
+  const double* weights;      // (B, n + 1): w | count
+  const double* state;        // (B, kFitStride): the point to evaluate is the TRIAL row; a problem whose status is not kFitRunning is skipped
+  double* partial;            // (B, waves, fit_row_len(P)): one row per (problem, wave)
+  double dt, fd_rel, fd_floor;
+  int32_t B, T, P, log2G, waves;   // G = 1 << log2G slots per transition, waves = ceil(T / (64 / G)) per problem
+  int32_t free_idx[kFitMaxFree];
+  hipEvent_t ev0, ev1;        // start / stop events riding on the launch, or nullptr
+};
+template <class M> MI_INTERNAL int launch_fit_normal(mi_ilqr* h, const FitArgs& a);                  // fit.hpp; k_fit.hip
+// ... and of fit_update_kernel (no model), one wave per problem: the fold, the decision, the next trial
+struct FitUpdateArgs {
+  double* state;              // (B, kFitStride)
+  const double* partial;      // (B, waves, fit_row_len(P))
+  const double* bounds;       // (2, n_params): lower | upper
+  double ftol;
+  int32_t B, P, n_params, waves;
+  int32_t first, last;        // first: the rows are the normal equations at theta0; last: the closing decision, no further trial
+  int32_t free_idx[kFitMaxFree];
+  hipEvent_t ev0, ev1;
+};
+MI_INTERNAL int launch_fit_update(mi_ilqr* h, const FitUpdateArgs& a);
+
 // Arguments of plant_advance_kernel<M> (plant_advance.hpp), all device pointers.  "Problem-minor": element e of problem b at e * B + b.
 struct PlantArgs {
   const double* policy;       // (steps, n + m + m n, B) problem-minor: row j = x_bar_j | u_bar_j | K_j (m x n, row-major), the first `steps` columns
@@ -552,6 +604,7 @@ int model_entry(mi_ilqr* h, int mode, const void* kargs) {
     return a.r.noise ? launch_policy_mc_noise<M>(h, a) : launch_policy_mc<M>(h, a);
   }
   if (mode == kModeSampledRollout) return launch_mppi_rollout<M>(h, *static_cast<const MppiArgs*>(kargs));
+  if (mode == kModeFitNormal) return launch_fit_normal<M>(h, *static_cast<const FitArgs*>(kargs));
   if (mode == kModePlantAdvance) {
     const PlantArgs& a = *static_cast<const PlantArgs*>(kargs);
     return a.noise ? launch_plant_advance_noise<M>(h, a) : launch_plant_advance<M>(h, a);

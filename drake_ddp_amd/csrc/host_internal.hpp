@@ -2,7 +2,7 @@
 // in the unit named above each group, all of it hidden from the dynamic symbol table.  Host units only: no k_*.hip unit, no
 // launch_*.hpp, no family header and not the plugin template includes this header, and it includes no family header.
 // The calls go one way: h_memory.hip calls nothing of the others; mi_ilqr.hip (the core) calls h_memory.hip, and of h_fields.hip the
-// field table alone; h_policy.hip, h_mpc.hip, h_seeds.hip and h_mppi.hip call the core and h_memory.hip (the plant its policy's pack, the seeds
+// field table alone; h_policy.hip, h_mpc.hip, h_seeds.hip, h_mppi.hip and h_fit.hip call the core and h_memory.hip (the plant its policy's pack, the seeds
 // its rule for the controls a launch starts from, and - the one call between two of them - h_seeds.hip hands the long form of its
 // command to the loop in h_mpc.hip); h_fields.hip, the boundary's selectors, calls all of them.  h_comm.hip stands alone.
 #pragma once
@@ -151,6 +151,12 @@ MI_INTERNAL int get_seeds_field(mi_ilqr* h, int which, double* dst, size_t bytes
 
 // ---- h_mppi.hip: the sampling form of MI_F_SEEDS_RUN (10 doubles), which h_seeds.hip hands over before it looks at anything else
 MI_INTERNAL int run_mppi(mi_ilqr* h, const double* v);
+
+// ---- h_fit.hip: parameter identification (MI_F_FIT_*) - the setters and the command behind mi_ilqr_set, the results behind
+// mi_ilqr_get; kNotFitField for every other selector.  Calls the core (the model table) and h_memory.hip, like h_mppi.hip.
+constexpr int kNotFitField = 1;
+MI_INTERNAL int set_fit_field(mi_ilqr* h, int which, const double* src, size_t bytes);
+MI_INTERNAL int get_fit_field(mi_ilqr* h, int which, double* dst, size_t bytes);
 
 // ---- h_mpc.hip: mi_ilqr_get of the plant's and the reference's selectors; kNotPlantField for every other one
 constexpr int kNotPlantField = 1;

@@ -902,6 +902,8 @@ void mi_ilqr_destroy(mi_ilqr_t* h) {
   if (h->seeds_ev1) (void)hipEventDestroy(h->seeds_ev1);
   if (h->plant_ev0) (void)hipEventDestroy(h->plant_ev0);
   if (h->plant_ev1) (void)hipEventDestroy(h->plant_ev1);
+  if (h->fit_ev0) (void)hipEventDestroy(h->fit_ev0);
+  if (h->fit_ev1) (void)hipEventDestroy(h->fit_ev1);
   if (!h->slots[0].stream && h->stream) (void)hipStreamDestroy(h->stream);      // (a create that failed before the slots were set up)
   for (const SolveSlot& s : h->slots) if (s.stream) (void)hipStreamDestroy(s.stream);
   delete h;

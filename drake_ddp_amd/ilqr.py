@@ -21,10 +21,10 @@ import numpy as np
 
 from . import _capi
 from . import utils_derivs_interpolation
-from .argcheck import (MC_DISTS, check_mc_args, check_mc_observe, check_model_params, check_mppi_args, check_noise_args,  # noqa: F401
-                       check_plant_args, check_rollout_args, check_seed_args, check_target_trajectory, integer)
+from .argcheck import (MC_DISTS, check_fit_args, check_mc_args, check_mc_observe, check_model_params, check_mppi_args,  # noqa: F401
+                       check_noise_args, check_plant_args, check_rollout_args, check_seed_args, check_target_trajectory, integer)
 from .models import ModelSystem
-from .results import (MPPIResult, PlantLog, PolicyEnvelope, PolicyRollout, PolicySafety, PolicySamples, PolicyStats,  # noqa: F401
+from .results import (MPPIResult, ParamFit, PlantLog, PolicyEnvelope, PolicyRollout, PolicySafety, PolicySamples, PolicyStats,  # noqa: F401
                       SeedSelection, _chan)
 
 _KP_IDS = {"setInterval": _capi.KP_SET_INTERVAL, "adaptiveJerk": _capi.KP_ADAPTIVE_JERK,
@@ -992,6 +992,38 @@ class BatchedIterativeLQR:
         """Milliseconds of the kernel of the last multi-start command (HIP events of its own)."""
         return float(self._fetch(_capi.F_SEEDS_KERNEL_MS, (1,))[0])
 
+    # ------------------------------------------------------------- parameter identification (include/mi_ilqr.h: "Parameter identification")
+    def FitModelParameters(self, x, u, x_next, *, free, count=None, weights=None, params0=None, damping=1e-3, bounds=None, iterations=20,
+                           ftol=1e-12, fd_rel=1e-6, fd_floor=1e-8, apply=False):   # noqa: A002
+        """From logged transitions to the rows SetModelParameters takes, on the device: every problem b fits the parameters `free`
+        (strictly increasing indices, at most 8; the others stay at params0) of its own row to its own transitions x[b, j], u[b, j]
+        -> x_next[b, j] - (B, T, n), (B, T, m), (B, T, n); rows need not be consecutive in time - by Levenberg-Marquardt on the
+        weighted one-step prediction error sum_j r_j' W r_j, with central differences of the model's step over the parameters
+        (steps fd_rel max(|theta_k|, fd_floor)).  count: (B,) the leading rows each problem uses (None: all T; plant_log's `steps`
+        goes straight in).  weights: (n,) or (B, n), the diagonal of W (None: ones).  params0: (B, n_params) or (n_params,); None:
+        the rows the solver holds (model_params).  damping: the first mu, a scalar or (B,).  bounds: (lo, hi), each (n_params,) or
+        None, +-inf allowed: every trial's free entries are clipped into them.  iterations counts trials; a problem stops earlier
+        when an accepted trial lowers the cost by no more than ftol times it.  apply=True makes the fitted rows the solver's
+        per-problem parameters, exactly as SetModelParameters(fit.params) would; apply=False touches nothing a solve uses.
+        -> ParamFit.  Nothing of size T crosses the bus after the upload."""
+        np_ = int(self.system.params.size)
+        p0 = params0 if params0 is not None or np_ == 0 else self.model_params
+        data, wrows, start, brows, run = check_fit_args(x, u, x_next, self.B, self.n, self.m, np_, free=free, params0=p0, count=count,
+                                                        weights=weights, damping=damping, bounds=bounds, iterations=iterations, ftol=ftol,
+                                                        fd_rel=fd_rel, fd_floor=fd_floor, apply=apply, m_dev=self._md)
+        self._send(_capi.F_FIT_DATA, data)
+        self._send(_capi.F_FIT_WEIGHTS, wrows)
+        self._send(_capi.F_FIT_START, start)
+        self._send(_capi.F_FIT_BOUNDS, brows)
+        self._send(_capi.F_FIT_RUN, run)
+        P = int(run[5])
+        return ParamFit.from_rows(self._fetch(_capi.F_FIT_RESULT, (self.B, np_ + _capi.FIT_RESULT_EXTRA)),
+                                  self._fetch(_capi.F_FIT_NORMAL, (self.B, P + P * P)), np_, P, self.fit_kernel_ms())
+
+    def fit_kernel_ms(self):
+        """Milliseconds of the kernels of the last FitModelParameters call, first to last (HIP events of its own)."""
+        return float(self._fetch(_capi.F_FIT_KERNEL_MS, (1,))[0])
+
     # ------------------------------------------------------------- multi-GPU helper
     def best_cost_allreduce(self):
         """min over all ranks of the best converged cost — the ONE collective of the
@@ -1129,6 +1161,19 @@ class IterativeLinearQuadraticRegulator(BatchedIterativeLQR):
             raise ValueError(f"RolloutPolicy: x0 must be (S, {self.n}); got {np.shape(x0)}")
         return super().RolloutPolicy(x0, params, trajectories, state_noise=state_noise, control_noise=control_noise, seed=seed,
                                      first_sample=first_sample, common_noise=common_noise)._without_batch_axis()
+
+    def FitModelParameters(self, x, u, x_next, *, count=None, weights=None, params0=None, damping=1e-3, bounds=None, **kw):
+        """x, x_next (T, n), u (T, m), count None or an integer, weights None or (n,), params0 None or (n_params,), damping a scalar:
+        BatchedIterativeLQR.FitModelParameters with the leading batch axis dropped, in the arguments and in the ParamFit."""
+        for name, v in (("x", x), ("u", u), ("x_next", x_next)):
+            if np.ndim(v) != 2:
+                raise ValueError(f"FitModelParameters: {name} must be (T, {self.m if name == 'u' else self.n}); got {np.shape(v)}")
+        for name, v, nd in (("count", count, 0), ("weights", weights, 1), ("params0", params0, 1), ("damping", damping, 0)):
+            if v is not None and np.ndim(v) != nd:
+                raise ValueError(f"FitModelParameters: {name} must be {'a scalar' if nd == 0 else 'one row'}; got shape {np.shape(v)}")
+        return super().FitModelParameters(np.asarray(x)[None], np.asarray(u)[None], np.asarray(x_next)[None],
+                                          count=None if count is None else [count], weights=weights, params0=params0, damping=damping,
+                                          bounds=bounds, **kw)._without_batch_axis()
 
     def SetTargetTrajectory(self, x_ref, clock=0):
         """x_ref (T, n) or None: BatchedIterativeLQR.SetTargetTrajectory."""

@@ -36,6 +36,36 @@ class MPPIResult:
         return f"MPPIResult(iterations={self.best_cost.shape[0]}, nominal_cost[-1]={self.nominal_cost[-1].tolist()})"
 
 
+class ParamFit:
+    """What FitModelParameters found (include/mi_ilqr.h: "Parameter identification"): params (B, n_params) - the rows
+    SetModelParameters takes -; cost0, cost (B,): the weighted squared one-step prediction error at the start and at params; damping
+    (B,): the Levenberg-Marquardt mu to carry into a following call; iterations - trials made -, accepted, status (FIT_CONVERGED /
+    FIT_MAX_ITERS / FIT_STALLED / FIT_BAD_DATA of _capi) and count - the rows each problem used -, (B,) integers; gradient (B, P) and
+    normal_matrix (B, P, P): g = sum J' W r and H = sum J' W J at params, over the free parameters in the order of `free`;
+    kernel_ms: the run's kernels, first to last.  inv(normal_matrix) cost / (count n - P) is the usual covariance estimate of the
+    fitted entries; it is the caller's to form."""
+    __slots__ = ("params", "cost0", "cost", "damping", "iterations", "accepted", "status", "count", "gradient", "normal_matrix", "kernel_ms")
+
+    def __init__(self, params, cost0, cost, damping, iterations, accepted, status, count, gradient, normal_matrix, kernel_ms):
+        self.params, self.cost0, self.cost, self.damping = params, cost0, cost, damping
+        self.iterations, self.accepted, self.status, self.count = iterations, accepted, status, count
+        self.gradient, self.normal_matrix, self.kernel_ms = gradient, normal_matrix, kernel_ms
+
+    @classmethod
+    def from_rows(cls, result, normal, n_params, P, kernel_ms):
+        """result (B, n_params + 7) and normal (B, P + P P) as MI_F_FIT_RESULT / MI_F_FIT_NORMAL return them."""
+        col = lambda k: np.ascontiguousarray(result[:, n_params + k])   # noqa: E731
+        icol = lambda k: result[:, n_params + k].astype(np.int64)   # noqa: E731
+        return cls(np.ascontiguousarray(result[:, :n_params]), col(0), col(1), col(2), icol(3), icol(4), icol(5), icol(6),
+                   np.ascontiguousarray(normal[:, :P]), np.ascontiguousarray(normal[:, P:]).reshape(-1, P, P), kernel_ms)
+
+    def _without_batch_axis(self):
+        return ParamFit(*(getattr(self, k)[0] for k in self.__slots__[:-1]), self.kernel_ms)
+
+    def __repr__(self):
+        return f"ParamFit(status={np.asarray(self.status).tolist()}, cost={np.asarray(self.cost).tolist()})"
+
+
 class SeedSelection:
     """What SelectBest found in every group of K seeds (include/mi_ilqr.h: "Multi-start"), (G,) arrays: winner - the member index of
     the eligible member of least cost, -1 when no member is eligible -, its cost (+inf then) and the number of eligible members."""

@@ -38,6 +38,7 @@ extern "C" {
                                    8: MI_STATUS_FLAG_INDEFINITE, on_indefinite = 1 inverts with partial pivoting, asymmetric costs for n <= 32,
                                       the diagnostic field MI_I64_CLUSTER_WORDS */
 #define MI_ILQR_MAX_PARAMS 16
+#define MI_FIT_MAX_FREE 8        /* free parameters of one MI_F_FIT_RUN ("Parameter identification" below) */
 #define MI_ILQR_CLUSTER_WORDS 40 /* 64-bit words per problem of the diagnostic field MI_I64_CLUSTER_WORDS */
 
 /* Error codes (0 = OK).  The Python wrapper maps them onto the exception types
@@ -107,6 +108,9 @@ enum { MI_STATUS_CONVERGED = 0, MI_STATUS_MAX_ITERS = 1, MI_STATUS_LINESEARCH_FA
                                   mpc_run) met such a Quu, inverted it with partial pivoting like the reference and carried on;
                                   `status & ~MI_STATUS_FLAG_INDEFINITE` is the solve's outcome.  Counted in stats.n_not_pd too */ };
 
+/* Per-problem outcome of a parameter fit (MI_F_FIT_RESULT's status column; "Parameter identification" below). */
+enum { MI_FIT_CONVERGED = 0, MI_FIT_MAX_ITERS = 1, MI_FIT_STALLED = 2, MI_FIT_BAD_DATA = 3 };
+
 /* Selector for mi_ilqr_get / mi_ilqr_set / mi_ilqr_device_ptr. */
 enum {
   MI_F_X_BAR = 0, MI_F_U_BAR = 1, MI_F_K = 2, MI_F_KAPPA = 3, MI_F_DV = 4, MI_F_FX = 5, MI_F_FU = 6,
@@ -151,6 +155,15 @@ enum {
   MI_F_SEEDS_U_BAR = 42,     /* (G,m,N-1) read-only: the winners' u_bar of the last gather, m the device's control dimension; (B,m,N-1) after a sampling-form run */
   MI_F_SEEDS_COST = 43,      /* (G,) read-only: the winners' cost of the last gather; (I+1,B,2) after a sampling-form run */
   MI_F_SEEDS_KERNEL_MS = 44, /* (1,) read-only: milliseconds of the kernel of the last MI_F_SEEDS_RUN, from its own HIP events */
+  /* parameter identification, values 45 .. 52: counted on from the selector before them */
+  MI_F_FIT_DATA = MI_F_SEEDS_KERNEL_MS + 1, /* (B,T,2n+m) logged transitions, rows x | u | x_next, T from the byte count ("Parameter identification" below) */
+  MI_F_FIT_WEIGHTS = MI_F_SEEDS_KERNEL_MS + 2, /* (B,n+1) w | count: the diagonal of the residual norm and the rows of MI_F_FIT_DATA problem b uses */
+  MI_F_FIT_START = MI_F_SEEDS_KERNEL_MS + 3, /* (B,n_params+1) theta0 | mu0: the parameter rows the fit starts from and its first damping */
+  MI_F_FIT_BOUNDS = MI_F_SEEDS_KERNEL_MS + 4, /* (2,n_params) lower | upper bounds of the parameters, +-inf = unbounded */
+  MI_F_FIT_RUN = MI_F_SEEDS_KERNEL_MS + 5, /* (6+P,) write-only COMMAND: iterations | ftol | fd_rel | fd_floor | apply | P | free[0..P-1] - mi_ilqr_set RUNS the fit */
+  MI_F_FIT_RESULT = MI_F_SEEDS_KERNEL_MS + 6, /* (B,n_params+7) read-only: theta | cost0 | cost | mu | iterations | accepted | status | count of the last run */
+  MI_F_FIT_NORMAL = MI_F_SEEDS_KERNEL_MS + 7, /* (B,P+P*P) read-only: g | H (P x P, row-major, symmetric) at the returned theta */
+  MI_F_FIT_KERNEL_MS = MI_F_SEEDS_KERNEL_MS + 8, /* (1,) read-only: milliseconds of the last run's kernels, first to last, from its own HIP events */
   /* int32 fields (mi_ilqr_get_int) */
   MI_I_ITERS = 100,     /* (B,) iterations of the last solve                            */
   MI_I_STATUS = 101,    /* (B,)                                                         */
@@ -870,6 +883,55 @@ int mi_ilqr_policy_rollout(mi_ilqr_t* h, int32_t S, const double* x0, const doub
  * Consequences: one call of I iterations is bitwise I calls of one iteration with first_sample advanced by S each; under temperature =
  * 0 the nominal cost of row i + 1 is the best cost of row i bitwise, so the cost never rises; nothing of size S leaves the device and
  * nothing of size S (N-1) is ever stored - the update regenerates every sample's applied controls from the counters. */
+
+/* ---- Parameter identification (ABI 10; selectors MI_F_FIT_* of mi_ilqr_set / mi_ilqr_get, no new entry point) ----
+ * From logged transitions (x_j, u_j, x_next_j) to the parameter rows MI_F_MODEL_PARAMS takes: every problem b fits the FREE entries
+ * of its own parameter row theta to its own rows by Levenberg-Marquardt on the one-step prediction error, on the device.  A model
+ * without parameters answers MI_ILQR_E_UNSUPPORTED to every selector below.  A refused call changes nothing.
+ *   mi_ilqr_set(MI_F_FIT_DATA, rows, B*T*(2n+m)*8)    row j of problem b = x_j | u_j | x_next_j, m the device's control dimension
+ *                                            (padding controls: zeros).  T >= 1 from the byte count, T < 2^24.  Rows need not be
+ *                                            consecutive in time.  Every entry finite (rows past a problem's count too: zeros will do)
+ *                                            - else MI_ILQR_E_BAD_ARG.  Setting the data drops MI_F_FIT_WEIGHTS (its counts refer to T).
+ *   mi_ilqr_set(MI_F_FIT_WEIGHTS, rows, B*(n+1)*8)    row b = w (n) | count: w finite and >= 0, the diagonal W of the residual norm;
+ *                                            count an integer in [0, T]: problem b uses its first count rows.  Not set (NULL, 0 bytes):
+ *                                            ones | T.  Needs the data: before it, MI_ILQR_E_BAD_ARG.
+ *   mi_ilqr_set(MI_F_FIT_START, rows, B*(n_params+1)*8)   row b = theta0 | mu0: finite, mu0 > 0.  Not set (NULL, 0 bytes): the rows
+ *                                            MI_F_MODEL_PARAMS returns | 1e-3.
+ *   mi_ilqr_set(MI_F_FIT_BOUNDS, rows, 2*n_params*8)  lower | upper, no NaN, lower <= upper.  Not set (NULL, 0 bytes): -inf | +inf.
+ *   mi_ilqr_set(MI_F_FIT_RUN, v, (6+P)*8)    v = iterations | ftol | fd_rel | fd_floor | apply | P | free[0] .. free[P-1], integers held
+ *                                            in doubles: iterations in [0, 2^20], ftol >= 0, fd_rel > 0, fd_floor > 0, apply 0 or 1,
+ *                                            P in [1, MI_FIT_MAX_FREE], free strictly increasing indices below n_params - else
+ *                                            MI_ILQR_E_BAD_ARG; a byte count that is not (6+P)*8 for the P it holds: MI_ILQR_E_BAD_SHAPE.
+ *                                            No data: MI_ILQR_E_BAD_ARG.
+ * THE ALGORITHM, independently per problem.  With theta the problem's row and f the model's step:
+ *   r_j = x_next_j - f(x_j, u_j; theta);  J_j[:, i] = (f(.; theta + h_k e_k) - f(.; theta - h_k e_k)) / (2 h_k), k = free[i],
+ *   h_k = fd_rel max(|theta_k|, fd_floor) at the point being evaluated;
+ *   c = sum_j r_j' W r_j, g = sum_j J_j' W r_j, H = sum_j J_j' W J_j over the first count rows: the NORMAL EQUATIONS at theta.
+ *   A TRIAL: (H + mu D) delta = g by Cholesky, D_ii = H_ii where H_ii > 0, else 1; theta' = clip(theta + delta) on the free entries,
+ *   by comparisons.  A factorisation that meets a pivot that is not positive or not finite is a rejected trial.  ACCEPTED when
+ *   c(theta') is finite and c(theta') < c(theta): theta <- theta', the normal equations become those of theta', mu <- max(mu / 10,
+ *   1e-12).  Else mu <- min(10 mu, 1e12) and the next trial is solved from the kept H, g.  `iterations` counts trials.
+ *   enum { MI_FIT_CONVERGED = 0,   an accepted trial with c - c' <= ftol c, or c' == 0
+ *          MI_FIT_MAX_ITERS = 1,   `iterations` trials without either end
+ *          MI_FIT_STALLED = 2,     a rejected trial with mu already at 1e12
+ *          MI_FIT_BAD_DATA = 3 }   count == 0 (cost +inf), or c(theta0) not finite (cost as computed): theta is theta0, untouched
+ *   A finished problem is frozen while the rest of the batch goes on.  A prediction that is not finite makes that evaluation's cost
+ *   non-finite; the models' feasibility bounds are not consulted (one-step prediction, not a rollout).
+ * ON THE DEVICE.  fit_normal_kernel<M> (one per model, plugins included): one lane per (transition, slot), slot 0 the evaluation at
+ * theta, slot i the pair theta +- h e_free[i-1]; G = P + 1 rounded up to a power of two slots per transition, 64 / G transitions per
+ * wave, grid B x ceil(T / (64 / G)); every wave leaves one row c | g | upper(H), summed over its transitions by a butterfly of fixed
+ * order.  fit_update_kernel (no model), one wave per problem: folds the rows left to right in wave order - an order that is a
+ * function of T and P alone -, decides, moves mu and solves the next trial.  A run of I iterations is normal(theta0), I x {update,
+ * normal(trial)} and the closing update: I + 1 launches of each on the handle's stream, ordered behind every solve in flight, no
+ * host synchronisation between them.  Nothing of a problem's result depends on B, on the other problems or on the handle's layout.
+ * apply = 1 makes the fitted rows the handle's per-problem parameter rows, exactly what mi_ilqr_set(MI_F_MODEL_PARAMS, theta) would
+ * leave; apply = 0 reads and writes nothing a solve uses.
+ *   mi_ilqr_get(MI_F_FIT_RESULT, dst, B*(n_params+7)*8)   row b = theta | cost0 | cost | mu | iterations | accepted | status | count:
+ *                                            cost0 = c(theta0), cost = c(theta); mu: the damping to carry into a following run
+ *   mi_ilqr_get(MI_F_FIT_NORMAL, dst, B*(P+P*P)*8)        row b = g | H at the returned theta (BAD_DATA by count == 0: zeros)
+ *   mi_ilqr_get(MI_F_FIT_KERNEL_MS, &ms, 8)               the run's kernels, first to last, from one pair of HIP events
+ *   Before any run the three answer MI_ILQR_E_BAD_ARG; mi_ilqr_set on them and mi_ilqr_get(MI_F_FIT_RUN) too.
+ * With these a caller forms inv(H) cost / (count n - P) as the covariance of the fitted entries. */
 
 #ifdef __cplusplus
 }
